@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the VPP + rSGM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Metric (BASELINE.json): Mdisparities/s = frames * H * W * D / wall-seconds / 1e6 for
@@ -50,6 +50,8 @@ N_SIMD = 1024                    # 256 CUs x 4 SIMDs
 # VOP3P, three-operand VOP3, v_bcnt, DPP) instructions priced with the rates tools/valu_bench.hip measured on gfx950
 # (profiles/r02_valu_issue_rates.txt)
 VALU_CYCLES_PER_INST = 3.3
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together, .npy headers included
+DUMP_SAMPLE_SEED = 0
 
 
 def parse(argv=None):
@@ -81,7 +83,15 @@ def parse(argv=None):
                          "ms_per_step_sustained, never as value")
     ap.add_argument("--spawn-check", action="store_true",
                     help="rank processes only form the process group (gloo, CPU) and report the frame plan: launcher self-test")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step handed its caller to DIR/<name>.npy as float32: "
+                         "disparity (the gathered maps when N > 1) and occlusion_mask (rank 0's frames; not with --no-occ).  "
+                         "An array larger than its share of %d bytes is a fixed, seeded sample of its flattened elements"
+                         % DUMP_BUDGET_BYTES)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -409,6 +419,26 @@ def cpu_baseline_simd_parallel(frames_per_process=8):
                        "from the first start to the last end")
 
 
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: numpy array} to dirname/<name>.npy as float32.  Each array gets an even share of `budget`; one larger than
+    its share is replaced by a sample of its flattened elements at positions drawn without replacement by a generator seeded
+    with DUMP_SAMPLE_SEED, in ascending order: the same positions on every run for the same shape, so that two builds can be
+    compared element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    header = 128   # an .npy header of a 1-D or 3-D array
+    keep = (budget // len(arrays) - header) // 4
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        what = "x".join(map(str, a.shape))
+        if a.size > keep:
+            pos = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pos]
+            what = f"{keep} sampled elements of {what}"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        print(f"[bench] wrote {os.path.join(dirname, name + '.npy')}: {what}", file=sys.stderr)
+
+
 def kernel_source_sha():
     """Identity of the HIP sources the PMC profile belongs to (profiles go stale when a kernel changes)."""
     h = hashlib.sha256()
@@ -554,6 +584,7 @@ def run_rank(args):
     outs = [torch.empty((B, H, W), dtype=torch.float32, device=dev) for _ in range(n_out)]
     occ_buf = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     pending = [None] * n_out  # gathers in flight, one per output buffer
+    last_gather = [None]      # --dump-outputs: the gather of the latest step (its result outlives drain())
     nstep = [0]
 
     # the inputs are resident: everything uploaded above is complete once this event is (it lets the pipelined front stage
@@ -584,6 +615,8 @@ def run_rank(args):
         local_step(outs[k], use_occ)
         if world > 1 and not args.no_gather:
             pending[k] = vdist.gather_disparities_async(outs[k], n_total, dst=0)  # every rank calls step() equally often
+            if args.dump_outputs:
+                last_gather[0] = pending[k]
 
     gather_wait = [0.0]   # host seconds the step loop spent waiting for a gather (the exposed part of the exchange)
 
@@ -641,6 +674,13 @@ def run_rank(args):
     dt_local = timed(args.steps, step)
     gather_ms_local = gather_wait[0] / args.steps * 1e3
     eng.status()   # raises if a fused aggregation launch of the timed region lost its lock step (its disparities would be void)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before later loops overwrite the buffers (`timed` ended with a device-wide synchronize)
+        disp = last_gather[0].result() if last_gather[0] is not None else outs[(nstep[0] - 1) % n_out]
+        arrays = {"disparity": disp.cpu().numpy()}
+        if use_occ:
+            arrays["occlusion_mask"] = occ_buf.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     dt = dt_local
     rank_ms = [dt_local / args.steps * 1e3]
     rank_gather_ms = [gather_ms_local]

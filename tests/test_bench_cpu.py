@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -90,3 +92,33 @@ def test_all_cores_simd_cpu_leg_counts_its_frames_and_times_only_the_compute():
     assert 0.3 * n * per_core < r["value"] <= 1.05 * n * per_core     # between badly skewed and perfectly parallel
     import oracle
     assert not oracle.get_simd()                                         # the parent's checker stays scalar
+
+
+def test_steps_below_one_are_refused():
+    assert bench.parse(["--steps", "3"]).steps == 3
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_fits_the_budget_at_the_headline_shape_and_samples_the_same_elements_every_run(tmp_path):
+    """`--dump-outputs`: the headline batch (32 x 540 x 960, disparity and mask) fits in 64 MB as fixed, seeded samples of the
+    flattened arrays, the same positions on every run; an array within its share is written whole, shape kept."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    disp = rng.random((32, 540, 960), dtype=np.float32) * 192
+    occ = (disp > 96).astype(np.uint8)
+    small = rng.random((2, 6, 7), dtype=np.float32)
+    runs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in runs:
+        bench.dump_outputs(d, {"disparity": disp, "occlusion_mask": occ})
+    assert sum(os.path.getsize(os.path.join(runs[0], f)) for f in os.listdir(runs[0])) <= 64_000_000
+    n = disp.size
+    for name, a in (("disparity", disp), ("occlusion_mask", occ)):
+        got = [np.load(os.path.join(d, name + ".npy")) for d in runs]
+        assert got[0].dtype == np.float32 and 0 < got[0].size < n
+        assert np.array_equal(got[0], got[1])
+        pos = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(n, got[0].size, replace=False))
+        assert np.array_equal(got[0], a.reshape(-1)[pos].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "c"), {"disparity": small})
+    whole = np.load(str(tmp_path / "c" / "disparity.npy"))
+    assert whole.shape == small.shape and np.array_equal(whole, small)
