@@ -304,7 +304,9 @@ int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPar
 void vppx_fstream_destroy(vppx_fstream *fs);
 /* One frame in (host arrays of the stream's H x W x C).  Returns when the frame has been copied: the arrays may be
  * reused at once.  The frame that completes a batch also queues the batch's upload, kernels and download (no waiting).
- * Fails with VPPX_E_INVALID_ARG when `depth` whole batches are waiting to be popped. */
+ * Fails with VPPX_E_INVALID_ARG when `depth` whole batches are waiting to be popped.  When submitting the completed batch
+ * fails, the error is returned but the frame HAS been taken: the next push or vppx_fstream_flush submits that batch again
+ * (a push copies nothing until it has), so vppx_fstream_counts never reports more than `batch` frames filling. */
 int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ);
 /* Submit the frames pushed so far as a (smaller) batch: end of the sequence, or a latency bound. */
 int vppx_fstream_flush(vppx_fstream *fs);
@@ -412,6 +414,9 @@ int vppx_batch_quantum(vppx_ctx *ctx, int H, int W, int dmax);
 /* Number of consecutive parts the last fused call (vppx_vpp_rsgm_dev / vppx_occ_vpp_rsgm_dev) ran as: a batch larger than
  * one round of the lock-step kernel runs as parts of one round each (VPPX_CHUNK); 1 = the whole batch at once. */
 int vppx_last_call_parts(vppx_ctx *ctx);
+/* Pieces per line of the last, part-filled layer of waves in the last launch of the W / E register-window kernel (its lines are
+ * cut into 2..8 pieces that hand the path state on through memory when that evens out the SIMDs' load); 1 = nothing was cut. */
+int vppx_we_last_pieces(vppx_ctx *ctx);
 /* Per-stage hipEvent timing of the last vppx_vpp_rsgm_dev/vppx_rsgm_dev call when stage
  * timing is enabled: fills ms[0..n) and returns the number of stages; names via
  * vppx_stage_name(i). */
@@ -432,7 +437,10 @@ const char *vppx_stage_name(int i);
  *   VPPX_VARIANT        comma-separated tokens that select alternative kernels with identical results, each run by
  *                       tests/test_gpu_variants.py: sum_general, sum_gl8, sum_trap0, sum_trap1 (fused sum / WTA kernel), gw4, gw8,
  *                       gw16 (lanes per pixel of the line-parallel kernel), we_line (W / E on the line-parallel kernel), we_after (W / E never next to
- *                       an under-filled lock-step launch), we_lq0, we_lq1 (W / E kernel: left-view operands per step / per quad of steps), we_whole (W / E kernel: no line of the last layer of waves is cut into pieces; tests: we_layer=N takes a layer to be N waves, we_mute makes every later piece give up waiting and compute its line from the start),
+ *                       an under-filled lock-step launch), we_lq0, we_lq1 (W / E kernel: left-view operands per step / per quad of steps), we_whole (W / E kernel: no line of the last layer of waves is cut into pieces; tests: we_layer=N takes a layer to be N waves, we_mute makes every later piece give up waiting and compute its line from the start, we_stale fills the
+ *                       hand-off records of every cut launch with the dword the next launch's flags accept),
+ *                       tests only: fs_fail_submit=K (the K-th batch submit of a frame stream fails with "injected submit failure",
+ *                       before it enqueues anything), fs_fail_from=K (every submit from the K-th on),
  *                       maxdist_lds, maxdist_global (one-wave maxDistance kernels) */
 
 #ifdef __cplusplus

@@ -280,15 +280,28 @@ def test_trapezoid_ring_at_d256_every_width(engines, B, H, W):
 # (D, B, H, W, layer): `we_layer=N` makes the W/E launcher take a layer of waves to be N (the device's SIMD count on a real launch), so
 # that small launches have a part-filled last layer whose lines are cut into pieces: 2 x B x Hp / 4 line quads = whole layers + a tail;
 # c pieces per tail line, c in 2..8 with the smallest ceil(tail * c / layer) / c, if that is below 0.9 (launch_we12).
-_SPLIT_CASES = [
-    (192, 8, 20, 96, 60),      # 128 line quads = 2 x 60 + 8: 2 pieces of 4 groups, both boundaries inside the d > x columns
-    (192, 8, 20, 330, 90),     # 128 = 90 + 38: 7 pieces of 4 groups over 28 (load 3 / 7)
-    (192, 9, 37, 200, 100),    # 216 = 2 x 100 + 16: 2 pieces over 18 groups, the last of them a part of a group (208 columns)
-    (128, 8, 33, 150, 89),     # D = 128 (8 steps per group): 192 = 2 x 89 + 14: 2 pieces over 20 groups
-    (256, 8, 12, 420, 61),     # D = 256 (16 steps per group): 64 = 61 + 3: 2 pieces over 27 groups
+_SPLIT_CASES = [  # (tail line quads, pieces) as launch_we12 picks them (_we_cut; the test asserts the pieces through we_last_pieces)
+    (192, 8, 20, 96, 60),      # 128 line quads = 2 x 60 + 8: 7 pieces over 8 groups, boundaries inside the d > x columns
+    (192, 8, 20, 330, 90),     # 128 = 90 + 38: 7 pieces of 4 groups over 28
+    (192, 9, 37, 200, 100),    # 216 = 2 x 100 + 16: 6 pieces over 18 groups, the last of them a part of a group (208 columns)
+    (128, 8, 33, 150, 89),     # D = 128 (8 steps per group): 192 = 2 x 89 + 14: 6 pieces over 20 groups
+    (256, 8, 12, 420, 61),     # D = 256 (16 steps per group): 64 = 61 + 3: 8 pieces over 27 groups
     (192, 16, 60, 130, 200),   # 512 = 2 x 200 + 112: 7 pieces (load 4 / 7) over 12 groups: one group each, the last takes six
     (192, 12, 28, 160, 97),    # 192 = 97 + 95: a tail of nearly a whole layer -- nothing is cut (same results either way)
 ]
+
+
+def _we_cut(D, B, H, W, layer):
+    """(tail line quads, pieces per tail line, DPL) that launch_we12 picks for a layer of `layer` waves; pieces = 1: nothing is cut."""
+    Hp, Wp, dpl = -(-H // 16) * 16, -(-W // 16) * 16, D // 16
+    nunits, ngroups = B * 2 * (Hp // 4), -(-Wp // dpl)
+    tail, pieces, best = nunits % layer, 1, 0.9
+    if nunits > layer and tail > 0:
+        for c in range(2, min(8, ngroups) + 1):
+            load = -(-tail * c // layer) / c
+            if load < best - 1e-9:
+                best, pieces = load, c
+    return tail, pieces, dpl
 
 
 @pytest.mark.parametrize("D,B,H,W,layer", _SPLIT_CASES)
@@ -299,9 +312,10 @@ def test_we_lines_cut_into_pieces_equal_whole_lines(D, B, H, W, layer, lq):
     8-path layout, frame 0 the oracle's; and when no piece ever publishes (`we_mute`) every later piece gives up and computes its
     line from the start: same values again."""
     import torch
-    cut = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_layer={layer}")
+    # (we_after: W/E behind the lock-step launch -- next to an under-filled one, as these small batches are, no line is cut)
+    cut = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_after,we_layer={layer}")
     whole = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_whole")
-    mute = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_layer={layer},we_mute")
+    mute = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_after,we_layer={layer},we_mute")
     eight = _env_engine(VPPX_VERT=0)
     b = synth.make_batch(B, H, W, D, 0.05, seed=7700 + W)
     args = [torch.from_numpy(np.ascontiguousarray(b[k])).to(cut.device) for k in ("left", "right", "hints")]
@@ -313,8 +327,58 @@ def test_we_lines_cut_into_pieces_equal_whole_lines(D, B, H, W, layer, lq):
             eng.synchronize()
         outs.append(o)
     assert cut.uses_vert() == 3 and whole.uses_vert() == 3 and mute.uses_vert() == 3 and eight.uses_vert() == 0
+    pieces = _we_cut(D, B, H, W, layer)[1]
+    assert cut.we_last_pieces() == pieces and mute.we_last_pieces() == pieces and whole.we_last_pieces() == 1, pieces
     for o, name in zip(outs[:3], ("cut", "whole", "mute")):
         assert torch.equal(o, outs[3]), (name, int((o != outs[3]).sum()))
     oracle.init_rand(5)
     lo, ro = oracle.vpp(b["left"][0], b["right"][0], b["hints"][0])
     assert np.array_equal(oracle.compute_rsgm(b["left"][0], lo, ro, **kw), outs[0][0].cpu().numpy())
+
+
+# One engine, one layer size (we_layer=60): the first call allocates the hand-off buffer (the largest record area of the list), the
+# record area then shrinks three times -- each launch's flags lie inside the record area the launch before it left -- and grows
+# twice; D and (tail, pieces, DPL) change from every call to the next.
+_GEOMETRY_WALK = [(256, 7, 20, 330), (192, 6, 20, 260), (128, 9, 20, 200), (256, 4, 20, 96), (192, 8, 28, 130), (128, 7, 28, 330)]
+_WALK_ORACLE = {}
+
+
+@pytest.mark.parametrize("lq", ["we_lq0", "we_lq1"])
+def test_we_split_survives_geometry_changes(lq):
+    """The W/E hand-off buffer is only cleared when it is (re)allocated, and where a cut launch's flags lie depends on (tail lines,
+    pieces, DPL): after a launch of another geometry they can sit on the earlier launch's path-state records.  `we_stale` makes
+    that the worst case -- behind every cut launch its record area holds the dword the next launch's flags accept -- so a piece
+    that trusts a stale flag starts from a forged state.  Every call must be cut (`we_last_pieces`), equal whole lines and the
+    8-path layout bit for bit, and frame 0 the oracle."""
+    import torch
+    layer = 60
+    walk = _GEOMETRY_WALK
+    cuts = [_we_cut(D, B, H, W, layer) for D, B, H, W in walk]
+    rec = [t * (p - 1) * 64 * (d // 2) for t, p, d in cuts]
+    assert all(p > 1 for _, p, _ in cuts) and all(a != b for a, b in zip(cuts, cuts[1:])), cuts
+    assert rec[0] == max(rec) and rec[1] > rec[2] > rec[3] < rec[4] < rec[5], rec
+    assert all(rec[i + 1] < rec[i] for i in range(3))   # the shrinking calls' flags lie in the record area before them
+    cut = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_after,we_layer={layer},we_stale")
+    whole = _env_engine(VPPX_VERT=3, VPPX_VARIANT=f"{lq},we_whole")
+    eight = _env_engine(VPPX_VERT=0)
+    kw = dict(p1=9, p2min=14, gamma=41, alpha=0.5)
+    try:
+        for i, (D, B, H, W) in enumerate(walk):
+            b = synth.make_batch(B, H, W, D, 0.05, seed=7800 + i)
+            args = [torch.from_numpy(np.ascontiguousarray(b[k])).to(cut.device) for k in ("left", "right", "hints")]
+            outs = []
+            for eng in (cut, whole, eight):
+                outs.append(eng.vpp_rsgm(*args, seed=6 + i, rsgm_kw=dict(kw, dmax=D)))
+                eng.synchronize()
+            assert cut.uses_vert() == 3 and whole.uses_vert() == 3 and eight.uses_vert() == 0, i
+            assert cut.we_last_pieces() == cuts[i][1] and whole.we_last_pieces() == 1, (i, cut.we_last_pieces(), cuts[i])
+            assert torch.equal(outs[1], outs[2]), (i, "whole")
+            assert torch.equal(outs[0], outs[2]), (i, "cut", int((outs[0] != outs[2]).sum()))
+            if i not in _WALK_ORACLE:
+                oracle.init_rand(6 + i)
+                lo, ro = oracle.vpp(b["left"][0], b["right"][0], b["hints"][0])
+                _WALK_ORACLE[i] = oracle.compute_rsgm(b["left"][0], lo, ro, dmax=D, **kw)
+            assert np.array_equal(_WALK_ORACLE[i], outs[0][0].cpu().numpy()), i
+    finally:
+        for eng in (cut, whole, eight):
+            eng.ctx.close()

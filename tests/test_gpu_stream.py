@@ -270,3 +270,96 @@ def test_batched_engine_call_with_per_frame_range_and_a_single_valued_frame():
         eng.vpp_rsgm(L[f:f + 1], R[f:f + 1], Hn[f:f + 1], l_vpp=l1, r_vpp=r1, seed=9 + f, vpp_kw=kw, rsgm_kw=dict(dmax=D))
         eng.synchronize()
         assert torch.equal(l1[0], lv[f]) and torch.equal(r1[0], rv[f]), f
+
+
+def _fs_env(variant, *a, **kw):
+    """A FrameStream whose context reads VPPX_VARIANT=`variant` at creation (None: no variant)."""
+    from vppstereo_amd.pipeline import FrameStream
+    old = os.environ.get("VPPX_VARIANT")
+    try:
+        if variant is not None:
+            os.environ["VPPX_VARIANT"] = variant
+        return FrameStream(*a, **kw)
+    finally:
+        if old is None:
+            os.environ.pop("VPPX_VARIANT", None)
+        else:
+            os.environ["VPPX_VARIANT"] = old
+
+
+def _drain(fs, got):
+    while True:
+        r = fs.pop()
+        if r is None:
+            return
+        got.append(r)
+
+
+@pytest.mark.parametrize("depth,batch", [(2, 4), (3, 5), (4, 3), (3, 1)])
+def test_stream_after_one_failed_submit_keeps_every_frame(depth, batch):
+    """VPPX_VARIANT=fs_fail_submit=2: the push that completes the second batch raises ("injected submit failure") but has taken
+    its frame; the caller catches it and keeps pushing.  The next push submits that batch first (the native stream never copies a
+    frame past a full batch's planes), so the disparities that come out, in order, equal a stream without the failure, and
+    `counts()` never reports more than `batch` frames filling."""
+    H, W, D, seed = 36, 100, 64, 5
+    n = 3 * batch + 2
+    frames = _frames(n, H, W, D, 0.05, 300)
+    kw = dict(batch=batch, depth=depth, seed=seed, rsgm_kw=dict(dmax=D))
+    with _fs_env(None, H, W, 3, **kw) as ref:
+        want = list(ref.run(iter(frames)))
+    got, failures = [], []
+    with _fs_env("fs_fail_submit=2", H, W, 3, **kw) as fs:
+        for f, fr in enumerate(frames):
+            try:
+                fs.push(*fr)
+            except Exception as e:
+                assert "injected submit failure" in str(e), e
+                failures.append(f)
+            c = fs.counts()
+            assert c[0] == f + 1 and c[1] <= batch, (f, c)
+            assert (fs._pushed, fs._fill) == (c[0], c[1]), (f, c)   # the wrapper's bookkeeping in step with the native stream's
+            while len(fs._inflight) >= depth:   # keep the ring from filling (what `run` does)
+                got.append(fs.pop())
+        fs.flush()
+        _drain(fs, got)
+        assert fs.counts()[:3] == (n, 0, 0) and fs.pending == 0
+    assert failures == [2 * batch - 1], failures
+    assert len(got) == n
+    for f in range(n):
+        assert np.array_equal(got[f], want[f]), f
+
+
+def test_stream_whose_submits_keep_failing_takes_no_more_frames():
+    """VPPX_VARIANT=fs_fail_from=2: the first batch goes through; the push that completes the second raises, and from then on every
+    push and flush raises without taking a frame -- the native push too, called directly, retries the pending submit before it
+    copies anything (it used to write frame `batch` past the slot's planes).  The first batch's results still come out right,
+    and the stream closes cleanly."""
+    from vppstereo_amd import _lib
+    H, W, D, seed, batch = 36, 100, 64, 7, 4
+    frames = _frames(2 * batch + 3, H, W, D, 0.05, 400)
+    kw = dict(batch=batch, depth=3, seed=seed, rsgm_kw=dict(dmax=D))
+    with _fs_env(None, H, W, 3, **kw) as ref:
+        want = list(ref.run(iter(frames[:batch])))
+    fs = _fs_env("fs_fail_from=2", H, W, 3, **kw)
+    try:
+        for fr in frames[:2 * batch - 1]:
+            fs.push(*fr)
+        with pytest.raises(Exception, match="injected submit failure"):
+            fs.push(*frames[2 * batch - 1])
+        assert fs.counts()[:2] == (2 * batch, batch)
+        for fr in frames[2 * batch:]:
+            with pytest.raises(Exception, match="injected submit failure"):
+                fs.push(*fr)
+            assert fs.counts()[:2] == (2 * batch, batch)
+        with pytest.raises(Exception, match="injected submit failure"):
+            fs.flush()
+        l, r, h = (np.ascontiguousarray(a) for a in frames[-1])
+        rc = fs._lib.vppx_fstream_push(fs._h, l.ctypes.data, r.ctypes.data, h.ctypes.data, None)
+        assert rc != 0 and b"injected submit failure" in _lib.load().vppx_last_error(), rc
+        assert fs.counts()[:2] == (2 * batch, batch)
+        got = [fs.pop() for _ in range(batch)]
+        for f in range(batch):
+            assert np.array_equal(got[f], want[f]), f
+        assert fs.pop() is None          # the failed batch was never submitted
+    finally:
+        fs.close()

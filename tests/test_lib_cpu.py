@@ -131,7 +131,7 @@ def test_every_environment_variable_the_library_reads_is_documented_in_the_heade
     import re
     csrc = os.path.join(ROOT, "vppstereo_amd", "csrc")
     header = open(os.path.join(ROOT, "include", "vppx.h")).read()
-    shipped, experiment = set(), set()
+    shipped, experiment, tokens = set(), set(), set()
     for name in sorted(os.listdir(csrc)):
         if not name.endswith((".hip", ".h")):
             continue
@@ -146,6 +146,12 @@ def test_every_environment_variable_the_library_reads_is_documented_in_the_heade
             for m in re.finditer(r'getenv\("(\w+)"\)', code):
                 assert name == "vppx_api.hip", (name, m.group(1))
                 (experiment if depth_exp else shipped).add(m.group(1))
+            if name == "vppx_api.hip" and not depth_exp:   # the VPPX_VARIANT tokens of the shipped build
+                tokens.update(re.findall(r'\bhas\("(\w+)"\)|v\.find\("(\w+=)"\)', code))
     assert shipped and len(shipped) <= 8, shipped
     for v in shipped | experiment:
         assert v in header, v
+    tokens = {a or b for a, b in tokens}
+    assert {"we_stale", "fs_fail_submit=", "fs_fail_from=", "we_layer="} <= tokens, tokens
+    for t in tokens:
+        assert re.search(r"\b" + t + (r"" if t.endswith("=") else r"\b"), header), t

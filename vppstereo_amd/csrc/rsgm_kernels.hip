@@ -965,6 +965,12 @@ struct We12Args {
     // line from there and passes it on.  A piece whose predecessor does not show up within `timeout_ticks` computes the line
     // from its start itself: same values, no dependency, never a hang.
     u32 *hand;        // [tail line][piece boundary][64 lanes][DPL / 2] dwords, then a flag per tail line: serial << 4 | pieces done
+    // Where the flags lie depends on (ntail, pieces, DPL), so after a launch of another geometry they may sit on what an earlier
+    // launch left as records -- packed u16 L values, and a dword of those can read "serial << 4 | k" of this launch.  The launcher
+    // therefore clears this launch's flag words whenever (ntail, pieces, DPL) differs from the last cut launch's (launch_we12).
+    // Chosen over a fixed flag region in front of the records because it leaves the kernel and the steady state alone: a stream of
+    // one geometry never clears, a change of geometry costs one small memset.  (VPPX_VARIANT=we_stale fills each launch's record
+    // area with the dword the next launch's flags accept: tests/test_gpu_fused_fuzz.py, test_we_split_survives_geometry_changes.)
     int n_whole;      // lines run whole: blocks [0, n_whole)
     int lead;         // blocks in front of the grid that do nothing (a multiple of 8)
     int ntail, tail_base, tail_pitch; // tail lines; first block of their pieces (a multiple of 8); blocks per piece index (a multiple of 8)
@@ -1331,13 +1337,18 @@ static int launch_we12(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gr
                 u32 *hand;
                 int rc = ws_get(ctx, WS_WE_HAND, rec_dwords, &hand);
                 if (rc) return rc;
+                const size_t rec_area = (size_t)tail * WE12_WPB * (pieces - 1) * (64 * (dpl / 2)); // dwords in front of the flags
                 if (ctx->we_hand_seen != (void *)hand || ctx->we_hand_cap != ctx->ws[WS_WE_HAND].cap) {
                     // fresh memory may hold anything -- for instance the flags of another context's launch with the same serial
                     // (a wrong frame in a full-size test, once in a few runs): cleared once, then only this context's serials live here
                     VPPX_HIP(hipMemsetAsync(hand, 0, ctx->ws[WS_WE_HAND].cap, ctx->stream));
                     ctx->we_hand_seen = (void *)hand;
                     ctx->we_hand_cap = ctx->ws[WS_WE_HAND].cap;
+                } else if (ctx->we_hand_geom[0] != tail || ctx->we_hand_geom[1] != pieces || ctx->we_hand_geom[2] != dpl) {
+                    // another geometry: this launch's flags may lie on an earlier launch's records (We12Args)
+                    VPPX_HIP(hipMemsetAsync(hand + rec_area, 0, (size_t)tail * WE12_WPB * sizeof(u32), ctx->stream));
                 }
+                ctx->we_hand_geom[0] = tail; ctx->we_hand_geom[1] = pieces; ctx->we_hand_geom[2] = dpl;
                 a.hand = hand; a.n_whole = nunits - tail; a.pieces = pieces; a.piece_groups = ngroups / pieces;
                 a.ntail = tail; a.tail_base = (a.n_whole + 7) & ~7; a.tail_pitch = (tail + 7) & ~7;
                 a.lead = ctx->knobs.we_layer > 0 ? 8 : nsimd_of[dv] / 4; // one per CU
@@ -1376,6 +1387,13 @@ static int launch_we12(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gr
     else WE12_LAUNCH(16);
 #undef WE12_LAUNCH
     VPPX_CHECK_LAUNCH();
+    ctx->we_last_pieces = a.pieces;
+    if (a.pieces > 1 && ctx->knobs.we_stale) {
+        // tests: the worst records a launch can leave -- every dword reads "all pieces done" to the next cut launch's flags
+        const unsigned next = ((a.serial & 0x0FFFFFFFu) + 1) & 0x0FFFFFFFu;
+        const size_t rec_area = (size_t)a.ntail * WE12_WPB * (a.pieces - 1) * (64 * (dpl / 2));
+        VPPX_HIP(hipMemsetD32Async((hipDeviceptr_t)a.hand, (int)((next << 4) | 15u), rec_area, ctx->stream));
+    }
 #ifdef VPPX_EXPERIMENT
     if (a.trace) { // the last launch's trace, every time: (grid, n_whole, pieces, tail_base, tail_pitch, ntail), then 3 words per block
         std::vector<unsigned long long> h((size_t)3 * grid.x + 6);

@@ -172,6 +172,12 @@ extern "C" int vppx_create(vppx_ctx **out, int device)
             if (has("we_after")) ctx->knobs.we_next = 0;
             if (has("we_whole")) ctx->knobs.we_split = 0;
             if (has("we_mute")) ctx->knobs.we_mute = 1;
+            if (has("we_stale")) ctx->knobs.we_stale = 1;
+            {
+                const size_t fk = v.find("fs_fail_submit="), ff = v.find("fs_fail_from=");
+                if (fk != std::string::npos) ctx->knobs.fs_fail_submit = atoi(v.c_str() + fk + 15);
+                if (ff != std::string::npos) ctx->knobs.fs_fail_from = atoi(v.c_str() + ff + 13);
+            }
             {
                 const size_t wl = v.find("we_layer=");
                 if (wl != std::string::npos) ctx->knobs.we_layer = atoi(v.c_str() + wl + 9);
@@ -1529,6 +1535,7 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
 }
 
 extern "C" int vppx_last_call_parts(vppx_ctx *ctx) { return ctx ? ctx->last_parts : 0; }
+extern "C" int vppx_we_last_pieces(vppx_ctx *ctx) { return ctx ? ctx->we_last_pieces : 0; }
 
 static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                           int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,

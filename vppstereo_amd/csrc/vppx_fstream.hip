@@ -72,6 +72,7 @@ struct vppx_fstream {
     uint64_t pop_batch = 0;    // batch the next pop reads
     int pop_idx = 0;           // next frame inside it
     uint64_t reruns = 0;       // batches re-run after a lost lock step
+    uint64_t submits = 0;      // calls of fs_submit (VPPX_VARIANT=fs_fail_submit=K / fs_fail_from=K count them)
     bool lost_pending = false; // a lost lock step was noticed while submitting: what is in flight is re-run at the next pop
 };
 
@@ -251,6 +252,14 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
 {
     vppx_ctx *ctx = fs->ctx;
     const int nb = s.nb;
+    {
+        const uint64_t n = ++fs->submits;
+        const int k = ctx->knobs.fs_fail_submit, from = ctx->knobs.fs_fail_from;
+        if ((k > 0 && n == (uint64_t)k) || (from > 0 && n >= (uint64_t)from)) { // tests: nothing is enqueued
+            vppx_set_error("injected submit failure");
+            return VPPX_E_HIP;
+        }
+    }
     if (upload) {
         // the slot's device buffers are free once its last batch's results have left them (pop has waited for that event on the
         // host already; the stream-side wait costs nothing and keeps the order explicit)
@@ -335,6 +344,12 @@ extern "C" int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const ui
         return VPPX_E_INVALID_ARG;
     }
     DevGuard g(fs->ctx->device);
+    if (fs->fill_count >= fs->batch) {
+        // the push that filled this batch could not submit it (its error was returned): submit it now, or take nothing -- a
+        // frame `batch` of the slot would lie past its planes, the last one past the pinned block
+        const int rc = fs_close_batch(fs);
+        if (rc) return rc;
+    }
     Slot &s = fs->slots[fs->fill_batch % fs->depth];
     if (fs->fill_count == 0 && s.submitted && fs->fill_batch - fs->pop_batch >= (uint64_t)fs->depth) {
         // every slot holds a batch whose results have not been popped: its ring areas (and device inputs, kept for a re-run) are in use

@@ -154,6 +154,9 @@ struct vppx_ctx {
         int we_split = 1;     // W/E kernel: the lines of the last, part-filled layer of waves are cut into pieces; "we_whole": every line whole
         int we_layer = 0;     // "we_layer=N" (tests): the W/E launcher takes a layer of waves to be N instead of the device's SIMD count
         int we_mute = 0;      // "we_mute" (tests): pieces do not publish their state: every later piece takes the give-up path
+        int we_stale = 0;     // "we_stale" (tests): behind every cut W/E launch its record area is filled with the dword the NEXT launch's flags accept
+        int fs_fail_submit = 0; // "fs_fail_submit=K" (tests): the K-th batch submit of a frame stream fails before it enqueues anything
+        int fs_fail_from = 0;   // "fs_fail_from=K" (tests): ... and every submit from the K-th on
         int we_lq = -1;       // "we_lq0" / "we_lq1": the W/E kernel's left-view operand loads (per step / per quad of steps); default by launch
         int sum_blocks = 0;   // (experiment builds) "sum_blocks=N": forced number of blocks of the sum / WTA kernel
     } knobs;
@@ -166,6 +169,8 @@ struct vppx_ctx {
     unsigned we_serial = 0;        // launch serial of the W/E kernel's hand-off flags
     void *we_hand_seen = nullptr;  // the hand-off buffer as it was last cleared (launch_we12)
     size_t we_hand_cap = 0;
+    int we_hand_geom[3] = {0, 0, 0}; // (ntail, pieces, DPL) of the last cut W/E launch: where its flags lie (We12Args)
+    int we_last_pieces = 1;        // pieces per tail line of the last W/E launch (vppx_we_last_pieces)
     bool we_beside_vert = false;   // the W/E launch being queued runs next to a lock-step launch (run_aggregation)
     unsigned long long *draws_dst = nullptr; // device [B]: where the fused call leaves every frame's draw count (set per call by a frame stream)
     int last_sum_nvol = 0;         // volumes the last fused sum / WTA launch added (4: fused layout, 8: eight paths) and its

@@ -340,6 +340,10 @@ class Engine:
         """Parts the last fused call ran as (a batch larger than one round of the lock-step kernel is split; 1 = unsplit)."""
         return int(self.lib.vppx_last_call_parts(self.ctx.handle))
 
+    def we_last_pieces(self):
+        """Pieces per line of the last layer of waves in the last W/E launch of the fused layout (1: no line was cut)."""
+        return int(self.lib.vppx_we_last_pieces(self.ctx.handle))
+
     def fused_pixels_per_wave(self):
         """16 / 8: which fused vertical kernel the last call used (sgm_vert4_kernel / sgm_vert3_kernel); 0: none."""
         return int(self.lib.vppx_fused_pixels_per_wave(self.ctx.handle))

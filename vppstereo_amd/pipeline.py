@@ -167,6 +167,8 @@ class FrameStream:
         return a
 
     def push(self, left, right, hints, g_occ=None):
+        """One frame in (copied before the call returns).  The frame that completes a batch submits it; if that submit fails
+        the push raises but HAS taken the frame, and the next push or `flush()` submits the batch again."""
         left = self._arr(left, np.uint8, self._shape, "left")
         right = self._arr(right, np.uint8, self._shape, "right")
         hints = self._arr(hints, np.float32, (self.h, self.w), "hints")
@@ -179,6 +181,10 @@ class FrameStream:
                 raise ValueError("g_occ: expected shape (H, W)")
         elif g_occ is not None:
             raise ValueError("g_occ given but the stream was created without with_g_occ=True")
+        # a full batch whose submit failed (an earlier push raised, having taken its frame): submit it before anything else --
+        # raises again, and takes nothing, if it still fails
+        if self._fill == self.batch:
+            self.flush()
         # the ring holds `depth` submitted batches: before the frame that would start one more, take the oldest batch's results
         if self._fill == 0:
             while len(self._inflight) >= self.depth:
@@ -187,6 +193,10 @@ class FrameStream:
             _lib.check(self._lib.vppx_fstream_push(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data,
                                                    occ.ctypes.data if occ is not None else None))
         except _lib.VppxError as e:
+            # the native stream may have taken the frame and failed only to submit the batch it completed: stay in step
+            if self.counts()[0] > self._pushed:
+                self._pushed += 1
+                self._fill += 1
             raise Exception(str(e)) from e
         self._pushed += 1
         self._fill += 1
