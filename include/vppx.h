@@ -156,7 +156,8 @@ int vppx_set_stream_legacy(vppx_ctx *ctx);
  * parts.  (No reference counterpart: test.py handles one pair at a time.) */
 int vppx_set_pipeline(vppx_ctx *ctx, int on);
 /* One-shot: `hip_event` (a hipEvent_t the caller recorded on the stream that produced them) completes when ALL inputs of
- * the next vppx_occ_vpp_rsgm_dev / vppx_vpp_rsgm_dev call (left, right, g, g_occ) are ready.  NULL withdraws it.  Without
+ * the next vppx_occ_vpp_rsgm_dev / vppx_vpp_rsgm_dev / vppx_occ_vpp_rsgm_guided_dev call (left, right, g, g_occ,
+ * validhints) are ready.  NULL withdraws it.  Without
  * pipelining the call runs on the launch stream and the event is simply waited for there. */
 int vppx_inputs_ready_event(vppx_ctx *ctx, void *hip_event);
 /* Wait for everything queued on the context's stream.  Returns VPPX_E_HIP (message in vppx_last_error) when a fused
@@ -274,6 +275,19 @@ int vppx_occ_vpp_rsgm_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
 int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                            int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
                            uint8_t *conf_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out, uint64_t *draws_out);
+/* --guided with the rSGM matcher (test.py:207-223): as vppx_occ_vpp_rsgm_dev, and the hints g also re-weight the matching
+ * costs at every pixel whose validhints (float32 [B,H,W], required) is > 0, whatever its hint (_guided_dsi, rsgm.py:116-127).
+ * op != NULL computes the mask on the way; op == NULL: g_occ (may be NULL) is the caller's mask.  With vppx_set_pipeline,
+ * validhints is an input like g (vppx_inputs_ready_event).  Never the fused aggregation layout: the 8-path layout on u16
+ * volumes; a batch whose eight volumes (16 bytes per cell) would exceed 48 GiB runs in parts (frame f keeps srand(seed + f)). */
+int vppx_occ_vpp_rsgm_guided_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B,
+                                 int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
+                                 const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out);
+/* The same for HOST arrays, as vppx_occ_vpp_rsgm_host. */
+int vppx_occ_vpp_rsgm_guided_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B,
+                                  int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
+                                  const float *validhints, uint8_t *conf_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out,
+                                  uint64_t *draws_out);
 
 /* ---- frame stream: the hot path for callers that hold one host frame at a time ---------------------------------------
  * test.py:291-311 iterates a DataLoader with batch size 1 and runs :154-225 per frame on numpy arrays; the kernels want
@@ -293,11 +307,13 @@ int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVpp
  * flight from the device inputs it still holds (vppx_fstream_counts reports how often).  Not thread-safe: one producer /
  * consumer thread (the calls release nothing to other threads but do not hold Python's GIL).
  * flags: VPPX_FS_PATTERNS pop can return the patterned pair; VPPX_FS_MASK (with op) the mask; VPPX_FS_GOCC every push brings
- * a caller's mask (op must be NULL).  copy_threads < 0: chosen from the host's core count.
+ * a caller's mask (op must be NULL); VPPX_FS_GUIDED every frame also brings its validhints and runs through
+ * vppx_occ_vpp_rsgm_guided_dev (push with vppx_fstream_push_guided).  copy_threads < 0: chosen from the host's core count.
  * use_distance_patch: dmin / dmax are each frame's own, computed on the device (per_frame_range is set for the stream). */
 #define VPPX_FS_PATTERNS 1
 #define VPPX_FS_MASK 2
 #define VPPX_FS_GOCC 4
+#define VPPX_FS_GUIDED 8
 typedef struct vppx_fstream vppx_fstream;
 int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int batch,
                         int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out);
@@ -308,6 +324,10 @@ void vppx_fstream_destroy(vppx_fstream *fs);
  * fails, the error is returned but the frame HAS been taken: the next push or vppx_fstream_flush submits that batch again
  * (a push copies nothing until it has), so vppx_fstream_counts never reports more than `batch` frames filling. */
 int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ);
+/* The same for a VPPX_FS_GUIDED stream: validhints (float32 [H,W], required) is copied into the ring with the frame.  Each of
+ * the two push calls fails with VPPX_E_INVALID_ARG on the other kind of stream. */
+int vppx_fstream_push_guided(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ,
+                             const float *validhints);
 /* Submit the frames pushed so far as a (smaller) batch: end of the sequence, or a latency bound. */
 int vppx_fstream_flush(vppx_fstream *fs);
 /* The next frame's results, in input order: *got = 1 and the arrays filled (NULL = not wanted; draws_out = rand() draws the

@@ -30,8 +30,9 @@ EXPORTS = [
     "vppx_vpp_rsgm_dev", "vppx_rsgm_post_dev", "vppx_occ_vpp_rsgm_dev", "vppx_occ_vpp_rsgm_host", "vppx_inputs_ready_event", "vppx_u8_to_nchw_dev", "vppx_psmnet_cost_volume_dev", "vppx_raft_corr_modulate_dev", "vppx_kitti_disp_decode_dev", "vppx_png_decode_dev", "vppx_pfm_decode_dev", "vppx_occlusion_heuristic_host", "vppx_occlusion_heuristic_dev", "vppx_occlusion_heuristic_full_host", "vppx_occlusion_heuristic_full_dev", "vppx_set_graph_mode", "vppx_graph_replays", "vppx_time_aggregate", "vppx_agg_kernel_ms", "vppx_we_kernel_ms", "vppx_time_aggregate_frames", "vppx_time_aggregate_part", "vppx_uses_vert", "vppx_last_call_parts", "vppx_we_last_pieces", "vppx_fused_pixels_per_wave", "vppx_batch_quantum",
     "vppx_enable_stage_timing", "vppx_get_stage_ms", "vppx_stage_name",
     "vppx_fstream_create", "vppx_fstream_destroy", "vppx_fstream_push", "vppx_fstream_flush", "vppx_fstream_pop", "vppx_fstream_counts",
+    "vppx_occ_vpp_rsgm_guided_dev", "vppx_occ_vpp_rsgm_guided_host", "vppx_fstream_push_guided",
 ]
-FS_PATTERNS, FS_MASK, FS_GOCC = 1, 2, 4
+FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 
 
 class VppxVppParams(C.Structure):
@@ -139,6 +140,9 @@ def load():
         lib.vppx_occ_params_default.argtypes = [po]
         lib.vppx_occ_params_default.restype = None
         lib.vppx_occ_vpp_rsgm_dev.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
+        lib.vppx_occ_vpp_rsgm_guided_dev.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.vppx_occ_vpp_rsgm_guided_host.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                      C.POINTER(C.c_uint64)]
         lib.vppx_inputs_ready_event.argtypes = [vp, vp]
         lib.vppx_u8_to_nchw_dev.argtypes = [vp, i, i, i, i, i, vp, vp, i]
         lib.vppx_psmnet_cost_volume_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
@@ -169,6 +173,7 @@ def load():
         lib.vppx_fstream_destroy.argtypes = [vp]
         lib.vppx_fstream_destroy.restype = None
         lib.vppx_fstream_push.argtypes = [vp, vp, vp, vp, vp]
+        lib.vppx_fstream_push_guided.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.vppx_fstream_flush.argtypes = [vp]
         lib.vppx_fstream_pop.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         p64 = C.POINTER(C.c_int64)

@@ -75,10 +75,11 @@ __device__ __forceinline__ u32 row_or_u32(u32 v)
     return v;
 }
 
-// unaligned (4-byte aligned) vector loads/stores of NW dwords
-template <int NW>
-__device__ __forceinline__ void load_words(const u32 *p, u32 (&w)[NW])
+// unaligned (4-byte aligned) vector loads/stores of NW dwords (loads: into the first NW words of w)
+template <int NW, int NA>
+__device__ __forceinline__ void load_words(const u32 *p, u32 (&w)[NA])
 {
+    static_assert(NW <= NA, "load_words: array too small");
     struct __attribute__((packed, aligned(4))) V4 { u32x4 v; };
     struct __attribute__((packed, aligned(4))) V2 { u32x2 v; };
     int i = 0;
@@ -457,29 +458,65 @@ __global__ void __launch_bounds__(256) cost_kernel(const u32 *__restrict__ cl, c
 
 // _guided_dsi (rsgm.py:116-127, numba): at every hint pixel the cost row is multiplied by
 // k*(1 - exp(-(hint-d)^2 / (2 c^2))), k = 10, c = 1, in float64 and truncated back to uint16.
-// hints / validhints are the un-padded [B,H,W] maps; rsgm.py:266-267 pads them with zeros.
-__global__ void __launch_bounds__(256) guided_dsi_kernel(u16 *__restrict__ dsi, const float *__restrict__ hints,
-                                                         const float *__restrict__ valid, int H, int W, int Hp, int Wp, int D,
-                                                         int pad_t, int pad_l)
+// The one place of that arithmetic: every guided cost comes from here.
+__device__ __forceinline__ u16 guided_cost(u32 c, double hv, int d)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y, f = blockIdx.z;
-    if (x >= W) return;
+    const double diff = __dsub_rn(hv, (double)d);
+    const double t = __dmul_rn(10.0, __dsub_rn(1.0, exp(__ddiv_rn(-__dmul_rn(diff, diff), 2.0))));
+    return (u16)(int)__dmul_rn((double)c, t);
+}
+
+// --guided without a cost volume: the hint pixels (validhints > 0, whatever the hint; 3-5 % of a frame) get their
+// re-weighted cost rows written out compactly, u16 [n][D], and a row index map over the padded frames says which pixel
+// owns which row (-1: none).  The aggregation takes every other pixel's costs from the census pair as the unguided
+// kernels do (COST_GUIDED), so the only cost bytes in memory are the hint rows.  hints / validhints are the un-padded
+// [B,H,W] maps; rsgm.py:266-267 pads them with zeros (a padding pixel is never guided).  Rows are handed out per wave
+// through one counter (*count, zero on entry): their order is free, and the row count never leaves the device.
+// One thread per padded pixel for the map; the wave's hint pixels are then walked one at a time by all 64 lanes, one
+// disparity per lane.  Costs as cost_kernel: popc(cl ^ cr[x-d]) for d <= x (padded x), InvalidDispCost beyond.
+__global__ void __launch_bounds__(256) guided_rows_kernel(const u32 *__restrict__ cl, const u32 *__restrict__ cr,
+                                                          const float *__restrict__ hints, const float *__restrict__ valid,
+                                                          int *__restrict__ gmap, u16 *__restrict__ rows, u32 *__restrict__ count,
+                                                          int H, int W, int Hp, int Wp, int D, int pad_t, int pad_l)
+{
+    const int xp = blockIdx.x * blockDim.x + threadIdx.x;
+    const int yp = blockIdx.y, f = blockIdx.z;
+    const int lane = threadIdx.x & 63;
+    const int x = xp - pad_l, y = yp - pad_t;
+    const bool inside = xp < Wp && x >= 0 && x < W && y >= 0 && y < H;
     const size_t o = ((size_t)f * H + y) * W + x;
-    if (!(valid[o] > 0)) return;
-    const double hv = (double)hints[o];
-    u16 *c = dsi + (((size_t)f * Hp + y + pad_t) * Wp + x + pad_l) * D;
-    for (int d = 0; d < D; d++) {
-        const double diff = __dsub_rn(hv, (double)d);
-        const double t = __dmul_rn(10.0, __dsub_rn(1.0, exp(__ddiv_rn(-__dmul_rn(diff, diff), 2.0))));
-        c[d] = (u16)(int)__dmul_rn((double)c[d], t);
+    const bool guided = inside && valid[o] > 0;
+    const u64 mask = __ballot(guided);
+    if (mask == 0) {
+        if (xp < Wp) gmap[((size_t)f * Hp + yp) * Wp + xp] = -1;
+        return;
+    }
+    u32 base = 0;
+    if (lane == 0) base = atomicAdd(count, (u32)__popcll(mask));
+    base = __shfl(base, 0);
+    const int my = (int)(base + (u32)__popcll(mask & ((1ull << lane) - 1ull)));
+    if (xp < Wp) gmap[((size_t)f * Hp + yp) * Wp + xp] = guided ? my : -1;
+    const float h = guided ? hints[o] : 0.f;
+    const size_t fpix = (size_t)f * Hp * Wp + (size_t)yp * Wp;
+    for (u64 m = mask; m != 0; m &= m - 1) {
+        const int l = __ffsll((unsigned long long)m) - 1;
+        const int row = __shfl(my, l), px = __shfl(xp, l);
+        const double hv = (double)__shfl(h, l);
+        const u32 a = cl[fpix + px];
+        for (int d = lane; d < D; d += 64) {
+            const u32 c = d <= px ? __popc(a ^ cr[fpix + px - d]) : INVALID_DISP_COST;
+            rows[(size_t)row * D + d] = guided_cost(c, hv, d);
+        }
     }
 }
 
-int rsgm_launch_guided_dsi(vppx_ctx *ctx, const RsgmGeom &g, u16 *dsi, const float *hints, const float *valid)
+int rsgm_launch_guided_rows(vppx_ctx *ctx, const RsgmGeom &g, const u32 *cl, const u32 *cr, const float *hints,
+                            const float *valid, int *gmap, u16 *rows, u32 *count)
 {
-    dim3 grid((g.W + 255) / 256, g.H, g.B);
-    guided_dsi_kernel<<<grid, 256, 0, ctx->stream>>>(dsi, hints, valid, g.H, g.W, g.Hp, g.Wp, g.D, g.pad_t, g.pad_l);
+    VPPX_HIP(hipMemsetAsync(count, 0, sizeof(u32), ctx->stream));
+    dim3 grid((g.Wp + 255) / 256, g.Hp, g.B);
+    guided_rows_kernel<<<grid, 256, 0, ctx->stream>>>(cl, cr, hints, valid, gmap, rows, count, g.H, g.W, g.Hp, g.Wp, g.D,
+                                                      g.pad_t, g.pad_l);
     VPPX_CHECK_LAUNCH();
     return 0;
 }
@@ -505,7 +542,8 @@ struct PathArgs {
     const u8 *gray;
     const u32 *cl;
     const u32 *cr;
-    const u16 *dsi;
+    const u16 *dsi;   // COST_DSI: the cost volume; COST_GUIDED: the hint pixels' rows (guided_rows_kernel)
+    const int *gmap;  // COST_GUIDED: row index of every padded pixel, -1 = census costs
     const u16 *p2lut;
     void *out;
     int Hp, Wp, D, p1;
@@ -626,29 +664,57 @@ __device__ __forceinline__ void sgm_update(u32 (&L)[NP], const u32 (&C)[NP], con
     minpk = pk_splat(mm);
 }
 
-// operands of one step, fetched one step ahead of their use (software prefetch: a scan line is
-// a serial chain, so without it every step would expose a full L2/HBM round trip)
-template <int DPL, bool FROM_DSI>
-struct StepIn {
-    u32 w[FROM_DSI ? DPL / 2 : DPL]; // census words of the right image, or packed u16 costs
-    u32 clv;
-    int I;
+// Where the line kernels take a step's matching costs from
+enum CostSrc : int {
+    COST_CENSUS = 0, // the census pair
+    COST_DSI = 1,    // a materialised u16 cost volume (stage API)
+    COST_GUIDED = 2, // the census pair, except at hint pixels: their re-weighted u16 rows (guided_rows_kernel)
 };
 
-template <int DPL, bool EXACT, bool FROM_DSI>
-__device__ __forceinline__ void load_step(StepIn<DPL, FROM_DSI> &s, const u8 *gray_f, const u32 *cl_f, const u32 *cr_f,
+// operands of one step, fetched one step ahead of their use (software prefetch: a scan line is
+// a serial chain, so without it every step would expose a full L2/HBM round trip)
+template <int DPL, int SRC>
+struct StepIn {
+    u32 w[SRC == COST_DSI ? DPL / 2 : DPL]; // census words of the right image, or packed u16 costs
+    u32 clv;
+    int I;
+    int g; // COST_GUIDED: the pixel's row (set before load_step), -1 = census costs
+};
+
+// `NP` packed u16 costs of a row into w[0, NP) (lanes past D load nothing: their slots are inactive)
+template <int NP, bool EXACT, int NA>
+__device__ __forceinline__ void load_cost_row(const u32 *cp, u32 (&w)[NA], const u32 (&inact)[NP])
+{
+    if (EXACT) {
+        load_words<NP>(cp, w);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NP; i++) w[i] = inact[i] ? 0u : cp[i];
+    }
+}
+
+template <int DPL, bool EXACT, int SRC>
+__device__ __forceinline__ void load_step(StepIn<DPL, SRC> &s, const u8 *gray_f, const u32 *cl_f, const u32 *cr_f,
                                           const u16 *dsi_f, int pixl, int D, int dbase, const u32 (&inact)[DPL / 2])
 {
     constexpr int NP = DPL / 2;
-    if constexpr (FROM_DSI) {
-        const u32 *cp = (const u32 *)(dsi_f + (size_t)((u32)pixl * (u32)D + (u32)dbase));
-        if (EXACT) {
-            load_words<NP>(cp, s.w);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NP; i++) s.w[i] = inact[i] ? 0u : cp[i];
-        }
+    if constexpr (SRC == COST_DSI) {
+        load_cost_row<NP, EXACT>((const u32 *)(dsi_f + (size_t)((u32)pixl * (u32)D + (u32)dbase)), s.w, inact);
         s.clv = 0;
+    } else if constexpr (SRC == COST_GUIDED) {
+        // every lane loads its census words; a hint pixel's lanes then overwrite w[0, NP) with its row (dsi_f: the rows of
+        // the batch).  (Census or row in an if / else: hipcc merged the two branches' stores into w through a computed index,
+        // and w went to scratch memory.)
+        const u32 pb = (u32)pixl << 2;
+        const char *crb = (const char *)(cr_f - 512);
+        load_words<DPL>((const u32 *)(crb + (size_t)(pb + (u32)((512 - dbase - (DPL - 1)) * 4))), s.w);
+        s.clv = *(const u32 *)((const char *)cl_f + (size_t)pb);
+        if (s.g >= 0) {
+            u32 r[NP];
+            load_cost_row<NP, EXACT>((const u32 *)(dsi_f + ((size_t)(u32)s.g * (u32)D + (u32)dbase)), r, inact);
+#pragma unroll
+            for (int i = 0; i < NP; i++) s.w[i] = r[i];
+        }
     } else {
         // uniform base + 32-bit lane offset (scalar-base addressing, no 64-bit lane arithmetic); the base sits
         // 512 words before the frame so that the offset of the first pixels (x - d < 0) stays non-negative
@@ -661,12 +727,12 @@ __device__ __forceinline__ void load_step(StepIn<DPL, FROM_DSI> &s, const u8 *gr
 }
 
 // packed matching costs of one step.  d > x has no right-image pixel: InvalidDispCost.
-template <int DPL, bool FROM_DSI>
-__device__ __forceinline__ void step_costs(const StepIn<DPL, FROM_DSI> &s, int lim /* k valid iff k <= lim */,
+template <int DPL, int SRC>
+__device__ __forceinline__ void step_costs(const StepIn<DPL, SRC> &s, int lim /* k valid iff k <= lim */,
                                            u32 (&C)[DPL / 2])
 {
     constexpr int NP = DPL / 2;
-    if constexpr (FROM_DSI) {
+    if constexpr (SRC == COST_DSI) {
 #pragma unroll
         for (int i = 0; i < NP; i++) C[i] = s.w[i];
     } else {
@@ -677,6 +743,7 @@ __device__ __forceinline__ void step_costs(const StepIn<DPL, FROM_DSI> &s, int l
             c0 = (2 * i <= lim) ? c0 : INVALID_DISP_COST;
             c1 = (2 * i + 1 <= lim) ? c1 : INVALID_DISP_COST;
             C[i] = (c1 << 16) | c0;
+            if constexpr (SRC == COST_GUIDED) C[i] = s.g >= 0 ? s.w[i] : C[i];
         }
     }
 }
@@ -742,8 +809,8 @@ struct LineState {
     int prevI;
 };
 
-template <int DPL, bool EXACT, bool FROM_DSI, typename OT, bool DIAG, int GW>
-__device__ __forceinline__ void line_step(LineState<DPL> &st, const StepIn<DPL, FROM_DSI> &in, OT *out_f, const u32 *s_lut,
+template <int DPL, bool EXACT, int SRC, typename OT, bool DIAG, int GW>
+__device__ __forceinline__ void line_step(LineState<DPL> &st, const StepIn<DPL, SRC> &in, OT *out_f, const u32 *s_lut,
                                           int x, int pixl, int D, int dbase, int wrap_edge, u32 P1pk,
                                           const u32 (&inact)[DPL / 2], bool first, bool last, bool line_active)
 {
@@ -754,7 +821,7 @@ __device__ __forceinline__ void line_step(LineState<DPL> &st, const StepIn<DPL, 
     if (DIAG) {
         // chain restart at the image border (missing predecessor => L = C)
         const bool restart = (x == wrap_edge);
-        if (FROM_DSI) {
+        if (SRC != COST_CENSUS) {
             // arbitrary u16 costs: with L = 0 and min = 0 the update yields exactly C
             const u32 keep = restart ? 0u : 0xFFFFFFFFu;
 #pragma unroll
@@ -770,19 +837,19 @@ __device__ __forceinline__ void line_step(LineState<DPL> &st, const StepIn<DPL, 
     // byte volumes (no saturation possible) computed from the census pair fuse the cost add into
     // the popcounts; the masked form is only needed where d can exceed x (first D-1 columns).
     // Wave-uniform branch: only those waves pay for the selects.
-    constexpr bool CAN_FUSE = !FROM_DSI && EXACT && sizeof(OT) == 1;
+    constexpr bool CAN_FUSE = SRC == COST_CENSUS && EXACT && sizeof(OT) == 1;
     const int lim = x - dbase;
     if (CAN_FUSE && __builtin_amdgcn_ballot_w64(lim < DPL - 1) == 0) {
         u32 X0[NP], X1[NP];
 #pragma unroll
         for (int i = 0; i < NP; i++) {
-            X0[i] = in.clv ^ in.w[(FROM_DSI ? NP : DPL) - 1 - (FROM_DSI ? 0 : 2 * i)];
-            X1[i] = in.clv ^ in.w[(FROM_DSI ? NP : DPL) - (FROM_DSI ? 1 : 2) - (FROM_DSI ? 0 : 2 * i)];
+            X0[i] = in.clv ^ in.w[DPL - 1 - 2 * i];
+            X1[i] = in.clv ^ in.w[DPL - 2 - 2 * i];
         }
         sgm_update<NP, EXACT, GW, true>(st.L, X0, X0, X1, P1pk, P2pk, st.minpk, inact, first, last);
     } else {
         u32 C[NP];
-        step_costs<DPL, FROM_DSI>(in, FROM_DSI ? DPL : lim, C);
+        step_costs<DPL, SRC>(in, SRC == COST_DSI ? DPL : lim, C);
         sgm_update<NP, EXACT, GW, false>(st.L, C, C, C, P1pk, P2pk, st.minpk, inact, first, last);
     }
     // No branch around the store in the fast variant: a store inside a conditional block makes hipcc's s_waitcnt
@@ -794,13 +861,22 @@ __device__ __forceinline__ void line_step(LineState<DPL> &st, const StepIn<DPL, 
     st.prevI = in.I;
 }
 
+// pixel index one step further along a line than (x, pix) (diagonal lines wrap to the other border of the row)
+template <bool DIAG>
+__device__ __forceinline__ int next_pix(int x, int pix, int dxs, int dpix, int Wp)
+{
+    const int xn = x + dxs;
+    return pix + dpix + (DIAG ? (xn >= Wp ? -Wp : (xn < 0 ? Wp : 0)) : 0);
+}
+
 // one scan line (GW lanes) from start to end; DIAG lines restart where they wrap around the
 // image.  The loop is unrolled by two with ping-pong operand buffers so that the loads of
 // step t+1 are in flight while step t computes, without register copies.
-template <int DPL, bool EXACT, bool FROM_DSI, typename OT, bool DIAG, int GW>
-__device__ __forceinline__ void run_line(const u8 *gray_f, const u32 *cl_f, const u32 *cr_f, const u16 *dsi_f, OT *out_f,
-                                         const u32 *s_lut, int Wp, int D, int x, int y, int dxs, int dys, int nsteps,
-                                         int dbase, u32 P1pk, bool first, bool last, bool line_active)
+template <int DPL, bool EXACT, int SRC, typename OT, bool DIAG, int GW>
+__device__ __forceinline__ void run_line(const u8 *gray_f, const u32 *cl_f, const u32 *cr_f, const u16 *dsi_f,
+                                         const int *gmap_f, OT *out_f, const u32 *s_lut, int Wp, int D, int x, int y,
+                                         int dxs, int dys, int nsteps, int dbase, u32 P1pk, bool first, bool last,
+                                         bool line_active)
 {
     constexpr int NP = DPL / 2;
     u32 inact[NP];
@@ -812,10 +888,18 @@ __device__ __forceinline__ void run_line(const u8 *gray_f, const u32 *cl_f, cons
     for (int i = 0; i < NP; i++) st.L[i] = 0; // first step: L = 0, min = 0 => L = C
     st.minpk = 0;
     int pix0 = y * Wp + x, x0 = x;
-    StepIn<DPL, FROM_DSI> A, Bq;
-    load_step<DPL, EXACT, FROM_DSI>(A, gray_f, cl_f, cr_f, dsi_f, pix0, D, dbase, inact);
-    st.prevI = A.I;
     const int dpix = dys * Wp + dxs; // pixel index advance per step (before the diagonal wrap)
+    StepIn<DPL, SRC> A, Bq;
+    // COST_GUIDED: a step's row index decides which of its operands are loaded, so it comes one step earlier still:
+    // gn is the row index of the pixel after the one whose operands are loaded next
+    int gn = -1;
+    if constexpr (SRC == COST_GUIDED) {
+        const int pn = next_pix<DIAG>(x0, pix0, dxs, dpix, Wp);
+        A.g = gmap_f[pix0];
+        gn = gmap_f[nsteps > 1 ? pn : pix0];
+    }
+    load_step<DPL, EXACT, SRC>(A, gray_f, cl_f, cr_f, dsi_f, pix0, D, dbase, inact);
+    st.prevI = A.I;
     (void)y;
     // Enter the loop with the first operands "used" (no load in flight).  hipcc's s_waitcnt pass merges the counter
     // state of the loop entry with that of the back edge; with loads pending on entry, the merged state keeps waits in
@@ -823,7 +907,7 @@ __device__ __forceinline__ void run_line(const u8 *gray_f, const u32 *cl_f, cons
     // round trip exposed every iteration.  (Worth 0 on the 8-direction launch, whose waves hide it; the W/E launch of
     // the fused layout is a latency chain per line.)
 #pragma unroll
-    for (int i = 0; i < (FROM_DSI ? DPL / 2 : DPL); i++) asm volatile("" ::"v"(A.w[i]));
+    for (int i = 0; i < (SRC == COST_DSI ? DPL / 2 : DPL); i++) asm volatile("" ::"v"(A.w[i]));
     asm volatile("" ::"v"(A.clv), "v"(A.I));
     for (int t = 0; t < nsteps; t += 2) {
         // position of step t+1 (clamped at the end of the line: a harmless reload).  Only diagonal lines can
@@ -835,12 +919,17 @@ __device__ __forceinline__ void run_line(const u8 *gray_f, const u32 *cl_f, cons
             p1 += wr;
         }
         // the fast variant only sees padded frames (Hp, Wp multiples of 16): an even number of steps, no tail branch
-        constexpr bool EVEN = !FROM_DSI && EXACT && sizeof(OT) == 1;
+        constexpr bool EVEN = SRC == COST_CENSUS && EXACT && sizeof(OT) == 1;
         const bool have1 = EVEN || (t + 1 < nsteps);
         const int pix1 = have1 ? p1 : pix0;
-        load_step<DPL, EXACT, FROM_DSI>(Bq, gray_f, cl_f, cr_f, dsi_f, pix1, D, dbase, inact);
-        line_step<DPL, EXACT, FROM_DSI, OT, DIAG, GW>(st, A, out_f, s_lut, x0, pix0, D, dbase, wrap_edge, P1pk, inact,
-                                                      first, last, line_active);
+        if constexpr (SRC == COST_GUIDED) { // (the row index load goes out first: waiting for it leaves the others in flight)
+            const int pn = next_pix<DIAG>(x1, pix1, dxs, dpix, Wp);
+            Bq.g = gn;
+            gn = gmap_f[(t + 2 < nsteps) ? pn : pix1];
+        }
+        load_step<DPL, EXACT, SRC>(Bq, gray_f, cl_f, cr_f, dsi_f, pix1, D, dbase, inact);
+        line_step<DPL, EXACT, SRC, OT, DIAG, GW>(st, A, out_f, s_lut, x0, pix0, D, dbase, wrap_edge, P1pk, inact,
+                                                 first, last, line_active);
         // position of step t+2
         int x2 = x1 + dxs, p2 = pix1 + dpix;
         if (DIAG) {
@@ -849,21 +938,26 @@ __device__ __forceinline__ void run_line(const u8 *gray_f, const u32 *cl_f, cons
             p2 += wr;
         }
         const int pix2 = (t + 2 < nsteps) ? p2 : pix1;
-        load_step<DPL, EXACT, FROM_DSI>(A, gray_f, cl_f, cr_f, dsi_f, pix2, D, dbase, inact);
+        if constexpr (SRC == COST_GUIDED) {
+            const int pn = next_pix<DIAG>(x2, pix2, dxs, dpix, Wp);
+            A.g = gn;
+            gn = gmap_f[(t + 3 < nsteps) ? pn : pix2];
+        }
+        load_step<DPL, EXACT, SRC>(A, gray_f, cl_f, cr_f, dsi_f, pix2, D, dbase, inact);
         if (have1)
-            line_step<DPL, EXACT, FROM_DSI, OT, DIAG, GW>(st, Bq, out_f, s_lut, x1, pix1, D, dbase, wrap_edge, P1pk, inact,
-                                                          first, last, line_active);
+            line_step<DPL, EXACT, SRC, OT, DIAG, GW>(st, Bq, out_f, s_lut, x1, pix1, D, dbase, wrap_edge, P1pk, inact,
+                                                     first, last, line_active);
         x0 = x2;
         pix0 = pix2;
     }
 }
 
-template <int GW, int DPL, bool EXACT, bool FROM_DSI, typename OT>
+template <int GW, int DPL, bool EXACT, int SRC, typename OT>
 __global__ void __launch_bounds__(256) sgm_paths_kernel(PathArgs a)
 {
     constexpr int LPB = 256 / GW; // scan lines per block
     // P2 table + (byte variant of the 8 x 24 layout) the waves' store transposition buffers
-    constexpr bool TR = !FROM_DSI && EXACT && sizeof(OT) == 1 && DPL == 24 && GW == 8;
+    constexpr bool TR = SRC == COST_CENSUS && EXACT && sizeof(OT) == 1 && DPL == 24 && GW == 8;
     __shared__ __attribute__((aligned(16))) u32 s_lut[256 + (TR ? 4 * TR_WORDS : 0)];
     s_lut[threadIdx.x] = pk_splat(a.p2lut[threadIdx.x]);
     __syncthreads();
@@ -923,17 +1017,18 @@ __global__ void __launch_bounds__(256) sgm_paths_kernel(PathArgs a)
     const u32 P1pk = pk_splat(a.p1 > 65535 ? 65535u : (u32)(a.p1 < 0 ? 0 : a.p1));
     const size_t fpix = (size_t)f * Hp * Wp;
     const u8 *gray_f = a.gray + fpix;
-    const u32 *cl_f = FROM_DSI ? nullptr : a.cl + fpix;
-    const u32 *cr_f = FROM_DSI ? nullptr : a.cr + fpix;
-    const u16 *dsi_f = FROM_DSI ? a.dsi + fpix * D : nullptr;
+    const u32 *cl_f = SRC == COST_DSI ? nullptr : a.cl + fpix;
+    const u32 *cr_f = SRC == COST_DSI ? nullptr : a.cr + fpix;
+    const u16 *dsi_f = SRC == COST_DSI ? a.dsi + fpix * D : (SRC == COST_GUIDED ? a.dsi : nullptr); // (rows: of the batch)
+    const int *gmap_f = SRC == COST_GUIDED ? a.gmap + fpix : nullptr;
     OT *out_f = (OT *)a.out + (size_t)a.vol_of_dir[dir] * a.vol_elems + fpix * D;
     const bool first = lg == 0, last = lg == GW - 1;
     if (diag)
-        run_line<DPL, EXACT, FROM_DSI, OT, true, GW>(gray_f, cl_f, cr_f, dsi_f, out_f, s_lut, Wp, D, x, y, dxs, dys,
-                                                     nsteps, dbase, P1pk, first, last, line_active);
+        run_line<DPL, EXACT, SRC, OT, true, GW>(gray_f, cl_f, cr_f, dsi_f, gmap_f, out_f, s_lut, Wp, D, x, y, dxs, dys,
+                                                nsteps, dbase, P1pk, first, last, line_active);
     else
-        run_line<DPL, EXACT, FROM_DSI, OT, false, GW>(gray_f, cl_f, cr_f, dsi_f, out_f, s_lut, Wp, D, x, y, dxs, dys,
-                                                      nsteps, dbase, P1pk, first, last, line_active);
+        run_line<DPL, EXACT, SRC, OT, false, GW>(gray_f, cl_f, cr_f, dsi_f, gmap_f, out_f, s_lut, Wp, D, x, y, dxs, dys,
+                                                 nsteps, dbase, P1pk, first, last, line_active);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1411,21 +1506,24 @@ static int launch_we12(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gr
 }
 
 template <int GW, int DPL>
-static int launch_paths_t(vppx_ctx *ctx, PathArgs a, int B, bool from_dsi, int elem_bytes)
+static int launch_paths_t(vppx_ctx *ctx, PathArgs a, int B, int src, int elem_bytes)
 {
     constexpr int LPB = 256 / GW;
     a.nlb = ((a.Hp > a.Wp ? a.Hp : a.Wp) + LPB - 1) / LPB;
     dim3 grid((unsigned)(a.nlb * a.ndirs * B), 1, 1);
     const bool exact = (a.D == GW * DPL);
-    if (from_dsi) {
-        if (exact) sgm_paths_kernel<GW, DPL, true, true, u16><<<grid, 256, 0, ctx->stream>>>(a);
-        else sgm_paths_kernel<GW, DPL, false, true, u16><<<grid, 256, 0, ctx->stream>>>(a);
+    if (src == COST_DSI) {
+        if (exact) sgm_paths_kernel<GW, DPL, true, COST_DSI, u16><<<grid, 256, 0, ctx->stream>>>(a);
+        else sgm_paths_kernel<GW, DPL, false, COST_DSI, u16><<<grid, 256, 0, ctx->stream>>>(a);
+    } else if (src == COST_GUIDED) {
+        if (exact) sgm_paths_kernel<GW, DPL, true, COST_GUIDED, u16><<<grid, 256, 0, ctx->stream>>>(a);
+        else sgm_paths_kernel<GW, DPL, false, COST_GUIDED, u16><<<grid, 256, 0, ctx->stream>>>(a);
     } else if (!exact) {
-        sgm_paths_kernel<GW, DPL, false, false, u16><<<grid, 256, 0, ctx->stream>>>(a);
+        sgm_paths_kernel<GW, DPL, false, COST_CENSUS, u16><<<grid, 256, 0, ctx->stream>>>(a);
     } else if (elem_bytes == 2) {
-        sgm_paths_kernel<GW, DPL, true, false, u16><<<grid, 256, 0, ctx->stream>>>(a);
+        sgm_paths_kernel<GW, DPL, true, COST_CENSUS, u16><<<grid, 256, 0, ctx->stream>>>(a);
     } else {
-        sgm_paths_kernel<GW, DPL, true, false, u8><<<grid, 256, 0, ctx->stream>>>(a);
+        sgm_paths_kernel<GW, DPL, true, COST_CENSUS, u8><<<grid, 256, 0, ctx->stream>>>(a);
     }
     VPPX_CHECK_LAUNCH();
     return 0;
@@ -1442,7 +1540,7 @@ int rsgm_paths_elem_bytes(int D, int maxp2)
 }
 
 int rsgm_launch_paths(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gray, const u32 *cl, const u32 *cr,
-                      const u16 *dsi, const u16 *p2lut, int p1, void *paths, int elem_bytes, int dir_mask)
+                      const u16 *dsi, const u16 *p2lut, int p1, void *paths, int elem_bytes, int dir_mask, const int *gmap)
 {
     PathArgs a;
     a.dir_mask = dir_mask & 0xFF;
@@ -1453,14 +1551,14 @@ int rsgm_launch_paths(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gra
         int nv = 0;
         for (int k = 0; k < 8; k++) a.vol_of_dir[k] = (a.dir_mask == 0xFF) ? k : (((a.dir_mask >> k) & 1) ? nv++ : 0);
     }
-    a.gray = gray; a.cl = cl; a.cr = cr; a.dsi = dsi; a.p2lut = p2lut; a.out = paths;
+    a.gray = gray; a.cl = cl; a.cr = cr; a.dsi = dsi; a.gmap = gmap; a.p2lut = p2lut; a.out = paths;
     a.Hp = Hp; a.Wp = Wp; a.D = D; a.p1 = p1;
     a.B = B;
     a.nlb = 0;
     a.vol_elems = (size_t)B * Hp * Wp * D;
     if ((size_t)Hp * Wp * D >= ((size_t)1 << 32)) { vppx_set_error("frame volume too large"); return VPPX_E_UNSUPPORTED; }
-    const bool from_dsi = dsi != nullptr;
-    if (from_dsi || D % 64 != 0) elem_bytes = 2; // those variants always write u16 volumes
+    const int src = gmap ? COST_GUIDED : (dsi ? COST_DSI : COST_CENSUS);
+    if (src != COST_CENSUS || D % 64 != 0) elem_bytes = 2; // those variants always write u16 volumes
     // Byte volumes run the small-value update (plain 32-bit adds on packed pairs, f16-pattern three-way minimum): its
     // operands must stay far below 0x7C00, which an unclamped P1 would break (0x3FFF + P1).  Clamping P1 to any value
     // >= P2max is exact: L(d+-1) + P1 >= min_k L(k) + P1 >= min_k L(k) + P2, so the P1 terms can never win the minimum
@@ -1472,31 +1570,31 @@ int rsgm_launch_paths(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gra
     {
         // W + E of the fused layout at D = 128 / 192 / 256: the register-window kernel (VPPX_VARIANT we_line: the line kernel)
         const int we12 = !ctx->knobs.we_line;
-        if (we12 && (D == 128 || D == 192 || D == 256) && a.dir_mask == 0x11 && !from_dsi && elem_bytes == 1 && Hp % 16 == 0 && Wp % 16 == 0 &&
+        if (we12 && (D == 128 || D == 192 || D == 256) && a.dir_mask == 0x11 && src == COST_CENSUS && elem_bytes == 1 && Hp % 16 == 0 && Wp % 16 == 0 &&
             Wp >= 16 && gw_override <= 0)
             return launch_we12(ctx, B, Hp, Wp, D, gray, cl, cr, p2lut, p1, paths);
     }
     if (D <= 64) {
-        if (gw_override == 8) return launch_paths_t<8, 8>(ctx, a, B, from_dsi, elem_bytes);
-        return launch_paths_t<4, 16>(ctx, a, B, from_dsi, elem_bytes);
+        if (gw_override == 8) return launch_paths_t<8, 8>(ctx, a, B, src, elem_bytes);
+        return launch_paths_t<4, 16>(ctx, a, B, src, elem_bytes);
     }
     // 32 disparities per lane need ~150 VGPRs (3 waves/SIMD) and run 1.7-1.8x slower than 16 per lane
     if (D <= 128) {
-        if (gw_override == 4) return launch_paths_t<4, 32>(ctx, a, B, from_dsi, elem_bytes);
-        return launch_paths_t<8, 16>(ctx, a, B, from_dsi, elem_bytes);
+        if (gw_override == 4) return launch_paths_t<4, 32>(ctx, a, B, src, elem_bytes);
+        return launch_paths_t<8, 16>(ctx, a, B, src, elem_bytes);
     }
     if (D <= 192) {
-        if (gw_override == 4) return launch_paths_t<4, 48>(ctx, a, B, from_dsi, elem_bytes);
+        if (gw_override == 4) return launch_paths_t<4, 48>(ctx, a, B, src, elem_bytes);
         // fewer than 8 frames do not fill the chip with 8 lanes per pixel (1920 waves per frame): twice the
         // waves at 7 waves/SIMD win below that (B=1: 0.45 vs 0.60 ms), 8 x 24 wins from B=16 on (-5 %)
         // the W/E-only launch of the fused layout has 4352 8-lane waves for 4096 slots: its second round is a tail as long
         // as the first; twice the waves at 7 per SIMD pack better (B=32: 2.34 -> 2.06 ms)
         if (gw_override == 16 || (gw_override != 8 && (B < 8 || a.dir_mask == 0x11)))
-            return launch_paths_t<16, 12>(ctx, a, B, from_dsi, elem_bytes);
-        return launch_paths_t<8, 24>(ctx, a, B, from_dsi, elem_bytes);
+            return launch_paths_t<16, 12>(ctx, a, B, src, elem_bytes);
+        return launch_paths_t<8, 24>(ctx, a, B, src, elem_bytes);
     }
-    if (gw_override == 8) return launch_paths_t<8, 32>(ctx, a, B, from_dsi, elem_bytes);
-    return launch_paths_t<16, 16>(ctx, a, B, from_dsi, elem_bytes);
+    if (gw_override == 8) return launch_paths_t<8, 32>(ctx, a, B, src, elem_bytes);
+    return launch_paths_t<16, 16>(ctx, a, B, src, elem_bytes);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1960,8 +2058,8 @@ __global__ void __launch_bounds__(256) sgm_vert3_kernel(Vert3Args a)
     const int dy = pass == 0 ? 1 : -1;
     int y = pass == 0 ? 0 : Hp - 1;
     const int xl = x > 0 ? x - 1 : 0, xr = x < Wp - 1 ? x + 1 : Wp - 1;
-    StepIn<DPL, false> A;
-    load_step<DPL, true, false>(A, gray_f, cl_f, cr_f, nullptr, y * Wp + x, D, dbase, inact);
+    StepIn<DPL, COST_CENSUS> A;
+    load_step<DPL, true, COST_CENSUS>(A, gray_f, cl_f, cr_f, nullptr, y * Wp + x, D, dbase, inact);
     int Ipl = 0, Ipr = 0;
     // the row's bytes leave one row late (right after the next row's poll), so that no wait of this wave ever has a
     // young volume store in front of it
@@ -2073,7 +2171,7 @@ __global__ void __launch_bounds__(256) sgm_vert3_kernel(Vert3Args a)
         // by the fourth wave
         {
             const int yn = (t + 1 < Hp) ? y + dy : y;
-            load_step<DPL, true, false>(A, gray_f, cl_f, cr_f, nullptr, yn * Wp + x, D, dbase, inact);
+            load_step<DPL, true, COST_CENSUS>(A, gray_f, cl_f, cr_f, nullptr, yn * Wp + x, D, dbase, inact);
             Ipl = gray_f[y * Wp + xl];
             Ipr = gray_f[y * Wp + xr];
         }
@@ -2236,8 +2334,8 @@ __global__ void __launch_bounds__(256, 2) sgm_vert4_kernel(Vert3Args a)
     const int dy = pass == 0 ? 1 : -1;
     int y = pass == 0 ? 0 : Hp - 1;
     const int xl = x > 0 ? x - 1 : 0, xr = x < Wp - 1 ? x + 1 : Wp - 1;
-    StepIn<DPL, false> A;
-    load_step<DPL, true, false>(A, gray_f, cl_f, cr_f, nullptr, y * Wp + x, D, dbase, inact);
+    StepIn<DPL, COST_CENSUS> A;
+    load_step<DPL, true, COST_CENSUS>(A, gray_f, cl_f, cr_f, nullptr, y * Wp + x, D, dbase, inact);
     int Ipl = 0, Ipr = 0;
     u32x4 pend[NQ];
 #pragma unroll
@@ -2350,7 +2448,7 @@ __global__ void __launch_bounds__(256, 2) sgm_vert4_kernel(Vert3Args a)
         // ---- operands of the next row
         {
             const int yn = (t + 1 < Hp) ? y + dy : y;
-            load_step<DPL, true, false>(A, gray_f, cl_f, cr_f, nullptr, yn * Wp + x, D, dbase, inact);
+            load_step<DPL, true, COST_CENSUS>(A, gray_f, cl_f, cr_f, nullptr, yn * Wp + x, D, dbase, inact);
             Ipl = gray_f[y * Wp + xl];
             Ipr = gray_f[y * Wp + xr];
         }

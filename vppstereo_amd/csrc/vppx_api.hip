@@ -4,6 +4,7 @@
 // no CPU fallback: without a HIP device every entry point fails with VPPX_E_NO_DEVICE.
 #include "vppx_internal.h"
 
+#include <limits.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -672,15 +673,16 @@ static int run_aggregation(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeo
     int nvol;
     if ((rc = lockstep_check(ctx))) return rc; // an earlier fused launch lost its lock step: say so before queueing more
     if (hints && validhints) {
-        // --guided (rsgm.py:265-268): like the reference, materialise the cost volume, re-weight the
-        // hint pixels' rows, aggregate from it (costs reach 240: u16 path volumes)
-        u16 *dsi;
+        // --guided (rsgm.py:265-268): the hint pixels' re-weighted cost rows are written out compactly, every other
+        // pixel's costs come from the census pair inside the aggregation (guided costs reach 240: u16 path volumes)
+        u16 *rows;
+        int *gmap;
         void *gp;
-        if ((rc = ws_get(ctx, WS_DSI, ncell, &dsi))) return rc;
+        if ((rc = ws_get(ctx, WS_DSI, (size_t)g.B * g.H * g.W * g.D, &rows))) return rc; // (at most every pixel has one)
+        if ((rc = ws_get(ctx, WS_GUIDED_MAP, npp + 1, &gmap))) return rc;
         if ((rc = ws_reserve(ctx, WS_PATHS, ncell * 8 * 2, &gp))) return rc;
-        if ((rc = rsgm_launch_cost(ctx, g.B, g.Hp, g.Wp, g.D, cl, cr, dsi))) return rc;
-        if ((rc = rsgm_launch_guided_dsi(ctx, g, dsi, hints, validhints))) return rc;
-        if ((rc = rsgm_launch_paths(ctx, g.B, g.Hp, g.Wp, g.D, gl, nullptr, nullptr, dsi, lut_d, p.p1, gp, 2, 0xFF))) return rc;
+        if ((rc = rsgm_launch_guided_rows(ctx, g, cl, cr, hints, validhints, gmap, rows, (u32 *)(gmap + npp)))) return rc;
+        if ((rc = rsgm_launch_paths(ctx, g.B, g.Hp, g.Wp, g.D, gl, cl, cr, rows, lut_d, p.p1, gp, 2, 0xFF, gmap))) return rc;
         for (int k = 0; k < 8; k++) vols[k] = (const u8 *)gp + (size_t)k * ncell * 2;
         *nvol_out = 8;
         *elem_bytes_out = 2;
@@ -1062,6 +1064,18 @@ static int check_frames(int B, int H, int W, int C)
     return 0;
 }
 
+// A guided batch keeps 8 u16 path volumes (16 bytes per cell): one whose volumes would exceed this runs in parts of as many
+// frames as fit (at least one).  (8 frames of 1536x2048x256 would need 103 GB.)
+#define VPPX_GUIDED_PART_BYTES (48ull << 30)
+static int guided_frames_per_part(int H, int W, int C, int dmax)
+{
+    RsgmGeom g1;
+    make_geom(1, H, W, C, dmax, g1);
+    const unsigned long long per = (unsigned long long)g1.Hp * g1.Wp * g1.D * 16ull;
+    const unsigned long long n = VPPX_GUIDED_PART_BYTES / per;
+    return n < 1 ? 1 : (n > (unsigned long long)INT_MAX ? INT_MAX : (int)n);
+}
+
 extern "C" int vppx_rsgm_dev(vppx_ctx *ctx, const VppxRsgmParams *p, int B, int H, int W, int C, const uint8_t *left,
                              const uint8_t *left_vpp, const uint8_t *right_vpp, const float *hints,
                              const float *validhints, float *disp_out)
@@ -1074,9 +1088,23 @@ extern "C" int vppx_rsgm_dev(vppx_ctx *ctx, const VppxRsgmParams *p, int B, int 
     if ((rc = check_rsgm_params(*p))) return rc;
     if ((hints == nullptr) != (validhints == nullptr)) { hints = nullptr; validhints = nullptr; } // rsgm.py:265 needs both
     RsgmGeom g;
-    make_geom(B, H, W, C, p->dmax, g);
     stage_begin(ctx);
-    return rsgm_core(ctx, *p, g, left, left_vpp, right_vpp, disp_out, hints, validhints);
+    const int q = hints ? guided_frames_per_part(H, W, C, p->dmax) : B;
+    if (q >= B) {
+        make_geom(B, H, W, C, p->dmax, g);
+        return rsgm_core(ctx, *p, g, left, left_vpp, right_vpp, disp_out, hints, validhints);
+    }
+    const size_t fpx = (size_t)H * W;
+    for (int lo = 0; lo < B; lo += q) {
+        const int nb = B - lo < q ? B - lo : q;
+        make_geom(nb, H, W, C, p->dmax, g);
+        ctx->stage_append = lo > 0;
+        rc = rsgm_core(ctx, *p, g, left + (size_t)lo * fpx * C, left_vpp + (size_t)lo * fpx * C, right_vpp + (size_t)lo * fpx * C,
+                       disp_out + (size_t)lo * fpx, hints + (size_t)lo * fpx, validhints + (size_t)lo * fpx);
+        ctx->stage_append = false;
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 extern "C" int vppx_rsgm_post_dev(vppx_ctx *ctx, int B, int H, int W, const float *disp_l_pad, const float *disp_r_pad,
@@ -1287,7 +1315,7 @@ extern "C" int vppx_rand_stream(vppx_ctx *ctx, uint32_t seed, uint64_t offset, i
 // ---------------------------------------------------------------------------------------
 static int vpp_rsgm_one(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                         int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                        uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+                        const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
 {
     int rc;
     const size_t nb = (size_t)B * H * W * C, np = (size_t)B * H * W;
@@ -1351,12 +1379,13 @@ static int vpp_rsgm_one(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPar
         VPPX_HIP(hipMemcpy2DAsync(ctx->draws_dst, 8, ctx->ws[WS_FRAME_TOT].p, 16, 8, (size_t)B, hipMemcpyDeviceToDevice, ctx->stream));
     RsgmGeom rg;
     make_geom(B, H, W, C, rp->dmax, rg);
-    return rsgm_core(ctx, *rp, rg, left, l_vpp, r_vpp, disp_out);
+    // --guided: the VPP hints re-weight the costs too (test.py:207 passes data['hints'] to both)
+    return rsgm_core(ctx, *rp, rg, left, l_vpp, r_vpp, disp_out, validhints ? g : nullptr, validhints);
 }
 
 static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                           int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                          uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out);
+                          const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out);
 
 extern "C" int vppx_inputs_ready_event(vppx_ctx *ctx, void *hip_event)
 {
@@ -1372,7 +1401,7 @@ extern "C" int vppx_vpp_rsgm_dev(vppx_ctx *ctx, const VppxVppParams *vp, const V
 {
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
-    const int rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, left, right, g, g_occ, nullptr, l_vpp, r_vpp, disp_out);
+    const int rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, left, right, g, g_occ, nullptr, nullptr, l_vpp, r_vpp, disp_out);
     ctx->inputs_ev = nullptr; // one-shot, whatever happened
     return rc;
 }
@@ -1384,7 +1413,23 @@ extern "C" int vppx_occ_vpp_rsgm_dev(vppx_ctx *ctx, const VppxOccParams *op, con
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
     if (!op) { vppx_set_error("vppx_occ_vpp_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
-    const int rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, nullptr, conf_out, l_vpp, r_vpp, disp_out);
+    const int rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, nullptr, nullptr, conf_out, l_vpp, r_vpp, disp_out);
+    ctx->inputs_ev = nullptr;
+    return rc;
+}
+
+// test.py:207-223 (--guided --stereomodel rsgm): the VPP hints g re-weight the matching costs as well (_guided_dsi).
+// op != NULL computes the mask on the way, else g_occ (may be NULL) is the caller's.
+extern "C" int vppx_occ_vpp_rsgm_guided_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                            int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g,
+                                            const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp,
+                                            uint8_t *r_vpp, float *disp_out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx);
+    int rc;
+    if (!validhints) { vppx_set_error("vppx_occ_vpp_rsgm_guided: validhints is NULL"); rc = VPPX_E_INVALID_ARG; }
+    else rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, op ? nullptr : g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
     ctx->inputs_ev = nullptr;
     return rc;
 }
@@ -1394,16 +1439,16 @@ extern "C" int vppx_occ_vpp_rsgm_dev(vppx_ctx *ctx, const VppxOccParams *op, con
 // + vpp_standalone.vpp + rsgm.compute_rsgm called one after the other.  op != NULL computes the mask on the way (--maskocc),
 // else g_occ (may be NULL) is the caller's.  draws_out (may be NULL, [B]): rand() draws each frame consumed, so that a
 // single-frame caller can advance the libc-like stream exactly like vpp() does.
-extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
-                                      int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                                      uint8_t *conf_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out, uint64_t *draws_out)
+static int occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
+                             int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
+                             const float *validhints, uint8_t *conf_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out,
+                             uint64_t *draws_out)
 {
     int rc;
-    VPPX_ENTER(ctx);
     if (!vp || !rp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_host: NULL argument"); return VPPX_E_INVALID_ARG; }
     if ((rc = check_frames(B, H, W, C))) return rc;
     const size_t nb = (size_t)B * H * W * C, np = (size_t)B * H * W;
-    void *dl, *dr, *dg, *docc = nullptr, *dconf = nullptr, *dlv = nullptr, *drv = nullptr, *dout;
+    void *dl, *dr, *dg, *docc = nullptr, *dconf = nullptr, *dlv = nullptr, *drv = nullptr, *dout, *dvh = nullptr;
     // the hints go up first and the occlusion heuristic is queued at once: its kernels run while the host is busy with the
     // (pageable, i.e. host-blocking) uploads of the pair
     if ((rc = upload(ctx, WS_STAGE_C, g, np * sizeof(float), &dg))) return rc;
@@ -1416,6 +1461,7 @@ extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, co
         docc = dconf; // from here on a given mask
         if (!conf_out) dconf = nullptr;
     } else if (g_occ && (rc = upload(ctx, WS_STAGE_D, g_occ, np, &docc))) return rc;
+    if (validhints && (rc = upload(ctx, WS_HANDOFF_V, validhints, np * sizeof(float), &dvh))) return rc;
     if ((rc = upload(ctx, WS_STAGE_A, left, nb, &dl))) return rc;
     if ((rc = upload(ctx, WS_STAGE_B, right, nb, &dr))) return rc;
     if (l_vpp_out && (rc = ws_reserve(ctx, WS_STAGE_E, nb, &dlv))) return rc;
@@ -1423,8 +1469,8 @@ extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, co
     if ((rc = ws_reserve(ctx, WS_HANDOFF_H, np * sizeof(float), &dout))) return rc;
     for (int attempt = 0;; attempt++) {
         const unsigned serial_before = ctx->v3.serial;
-        rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, (const u8 *)dl, (const u8 *)dr, (const float *)dg, (const u8 *)docc, nullptr,
-                            (u8 *)dlv, (u8 *)drv, (float *)dout);
+        rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, (const u8 *)dl, (const u8 *)dr, (const float *)dg, (const u8 *)docc,
+                            (const float *)dvh, nullptr, (u8 *)dlv, (u8 *)drv, (float *)dout);
         ctx->inputs_ev = nullptr;
         if (rc) return rc;
         if ((rc = download(ctx, disp_out, dout, np * sizeof(float)))) return rc;
@@ -1450,6 +1496,25 @@ extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, co
     return 0;
 }
 
+extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
+                                      int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
+                                      uint8_t *conf_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out, uint64_t *draws_out)
+{
+    VPPX_ENTER(ctx);
+    return occ_vpp_rsgm_host(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, nullptr, conf_out, l_vpp_out, r_vpp_out, disp_out, draws_out);
+}
+
+extern "C" int vppx_occ_vpp_rsgm_guided_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                             int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g,
+                                             const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp_out,
+                                             uint8_t *r_vpp_out, float *disp_out, uint64_t *draws_out)
+{
+    VPPX_ENTER(ctx);
+    if (!validhints) { vppx_set_error("vppx_occ_vpp_rsgm_guided_host: validhints is NULL"); return VPPX_E_INVALID_ARG; }
+    return occ_vpp_rsgm_host(ctx, op, vp, rp, B, H, W, C, left, right, g, op ? nullptr : g_occ, validhints, conf_out, l_vpp_out, r_vpp_out,
+                             disp_out, draws_out);
+}
+
 // Batches larger than one round of the lock-step kernel are run as consecutive parts of one round each ("batch quantum":
 // 16 frames at 540x960x192, 12 at 375x1242x192).  Frames are independent and frame f draws from srand(seed + f) whatever
 // the split, so results do not change; what changes is the length of the bursts: 32 frames per launch keep the chip's
@@ -1462,14 +1527,14 @@ extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, co
 // VPPX_CHUNK=0 keeps whole batches, VPPX_CHUNK=n forces parts of n frames.
 static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                           int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                          uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+                          const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
 {
     int rc;
     const int chunk_env = ctx->knobs.chunk;
     int q = 0;
     if (chunk_env > 0) {
         q = chunk_env;
-    } else if (chunk_env < 0 && !ctx->is_child && B >= 16) {
+    } else if (chunk_env < 0 && !ctx->is_child && B >= 16 && !validhints) { // (guided calls never take the lock-step kernel)
         RsgmGeom g1;
         make_geom(1, H, W, C, rp->dmax, g1);
         u16 lut[256];
@@ -1485,8 +1550,17 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             if (fused) q = fpr;
         }
     }
+    bool budget = false; // guided: parts of the memory budget (a remainder is a part of its own, never merged into a full one)
+    if (validhints) {
+        const int fb = guided_frames_per_part(H, W, C, rp->dmax);
+        if (fb < B && (q <= 0 || q > fb)) {
+            q = fb;
+            budget = true;
+        }
+    }
     ctx->last_parts = 1;
-    if (q <= 0 || q >= B) return vpp_rsgm_one(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, conf_out, l_vpp, r_vpp, disp_out);
+    if (q <= 0 || q >= B)
+        return vpp_rsgm_one(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
     ctx->last_parts = 0;
     const size_t fpx = (size_t)H * W;
     void *const inputs_ev = ctx->inputs_ev; // one-shot per CALL: every part's front stage may start on it
@@ -1498,14 +1572,14 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
     std::vector<int> plan;
     {
         const int k = B / q, r = B % q;
-        if (chunk_env < 0 && r > 0 && k >= 1 && 3 * ((r + k - 1) / k) <= q) {
+        if (chunk_env < 0 && !budget && r > 0 && k >= 1 && 3 * ((r + k - 1) / k) <= q) {
             for (int i = 0; i < k; i++) plan.push_back(q + r / k + (i < r % k ? 1 : 0));
         } else {
             int left_over = B;
             while (left_over > 0) {
                 int nb = left_over % q;
                 if (nb == 0) nb = q;
-                else if (nb < 8 && left_over > q) nb += q; // a few frames do not make a launch of their own
+                else if (nb < 8 && left_over > q && !budget) nb += q; // a few frames do not make a launch of their own
                 plan.push_back(nb);
                 left_over -= nb;
             }
@@ -1523,7 +1597,7 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         ctx->draws_dst = draws_base ? draws_base + lo : nullptr;
         rc = vpp_rsgm_one(ctx, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C,
                           g + (size_t)lo * fpx, g_occ ? g_occ + (size_t)lo * fpx : nullptr,
-                          conf_out ? conf_out + (size_t)lo * fpx : nullptr,
+                          validhints ? validhints + (size_t)lo * fpx : nullptr, conf_out ? conf_out + (size_t)lo * fpx : nullptr,
                           l_vpp ? l_vpp + (size_t)lo * fpx * C : nullptr, r_vpp ? r_vpp + (size_t)lo * fpx * C : nullptr,
                           disp_out + (size_t)lo * fpx);
         ctx->stage_append = false;
@@ -1539,7 +1613,7 @@ extern "C" int vppx_we_last_pieces(vppx_ctx *ctx) { return ctx ? ctx->we_last_pi
 
 static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                           int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                          uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+                          const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
 {
     int rc;
     if ((rc = lockstep_check(ctx))) return rc;
@@ -1558,7 +1632,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         memset(&key, 0, sizeof(key));
         key.B = B; key.H = H; key.W = W; key.C = C; key.vp = *vp; key.rp = *rp;
         key.ptr[0] = left; key.ptr[1] = right; key.ptr[2] = g; key.ptr[3] = g_occ; key.ptr[4] = l_vpp; key.ptr[5] = r_vpp;
-        key.ptr[6] = disp_out; key.ptr[7] = conf_out;
+        key.ptr[6] = disp_out; key.ptr[7] = conf_out; key.ptr[8] = validhints;
         key.has_op = op ? 1 : 0;
         if (op) key.op = *op;
         key.stream = (void *)ctx->stream;
@@ -1576,7 +1650,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
                 ctx->capturing = true;
-                rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, conf_out, l_vpp, r_vpp, disp_out);
+                rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
                 ctx->capturing = false;
                 hipGraph_t graph = nullptr;
                 e = hipStreamEndCapture(ctx->stream, &graph);
@@ -1605,15 +1679,15 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             // capture is not possible here (e.g. the legacy default stream): stay on the eager path
             (void)hipGetLastError();
             ctx->graph_mode = false;
-            return vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, conf_out, l_vpp, r_vpp, disp_out);
+            return vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
         }
-        rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, conf_out, l_vpp, r_vpp, disp_out);
+        rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
         key.ws_gen = ctx->ws_gen; // the workspace as this call left it
         ctx->lastkey = key;
         ctx->have_lastkey = (rc == 0);
         return rc;
     }
-    if (nsub <= 1) return vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, conf_out, l_vpp, r_vpp, disp_out);
+    if (nsub <= 1) return vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
     // Frames are independent: split the batch over child contexts (own stream + arena).  The
     // latency-bound stages of one part (VPP replay, post-processing) then overlap the
     // bandwidth-bound stages of another (aggregation stores, sum/WTA loads).
@@ -1637,11 +1711,16 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         VPPX_HIP(hipStreamWaitEvent(c->stream, ctx->ev_fork, 0));
         VppxVppParams v2 = *vp;
         v2.seed = vp->seed + (uint32_t)lo; // frame f keeps srand(seed + f) whatever the split
-        rc = vpp_rsgm_one(c, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C,
-                          g + (size_t)lo * fpx, g_occ ? g_occ + (size_t)lo * fpx : nullptr,
-                          conf_out ? conf_out + (size_t)lo * fpx : nullptr,
-                          l_vpp ? l_vpp + (size_t)lo * fpx * C : nullptr, r_vpp ? r_vpp + (size_t)lo * fpx * C : nullptr,
-                          disp_out + (size_t)lo * fpx);
+        // (a guided part goes through the parts of its own context: the memory budget holds for it as well)
+        const uint8_t *const occ_i = g_occ ? g_occ + (size_t)lo * fpx : nullptr;
+        uint8_t *const conf_i = conf_out ? conf_out + (size_t)lo * fpx : nullptr;
+        uint8_t *const lv_i = l_vpp ? l_vpp + (size_t)lo * fpx * C : nullptr, *const rv_i = r_vpp ? r_vpp + (size_t)lo * fpx * C : nullptr;
+        if (validhints)
+            rc = vpp_rsgm_parts(c, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C, g + (size_t)lo * fpx,
+                                occ_i, validhints + (size_t)lo * fpx, conf_i, lv_i, rv_i, disp_out + (size_t)lo * fpx);
+        else
+            rc = vpp_rsgm_one(c, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C,
+                              g + (size_t)lo * fpx, occ_i, nullptr, conf_i, lv_i, rv_i, disp_out + (size_t)lo * fpx);
         if (rc) return rc;
         VPPX_HIP(hipEventRecord(ctx->sub_done[i], c->stream));
         VPPX_HIP(hipStreamWaitEvent(ctx->stream, ctx->sub_done[i], 0));

@@ -58,7 +58,7 @@ struct vppx_fstream {
     int batch = 0, depth = 0, H = 0, W = 0, C = 0, flags = 0;
     size_t img = 0, px = 0;                 // bytes of one image, pixels of one frame
     size_t in_frame = 0, out_frame = 0;     // ring bytes per frame
-    size_t o_left = 0, o_right = 0, o_hint = 0, o_gocc = 0;          // offsets inside a slot's input area (planes of `batch` frames)
+    size_t o_left = 0, o_right = 0, o_hint = 0, o_gocc = 0, o_valid = 0;          // offsets inside a slot's input area (planes of `batch` frames)
     size_t o_disp = 0, o_lv = 0, o_rv = 0, o_conf = 0, o_draws = 0;  // offsets inside a slot's output area
     size_t in_bytes = 0, out_bytes = 0;
     std::vector<Slot> slots;
@@ -143,6 +143,7 @@ extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const
     fs->o_right = o; o += up256(fs->img * batch);
     fs->o_hint = o;  o += up256(fs->px * 4 * batch);
     fs->o_gocc = o;  if (flags & VPPX_FS_GOCC) o += up256(fs->px * batch);
+    fs->o_valid = o; if (flags & VPPX_FS_GUIDED) o += up256(fs->px * 4 * batch);
     fs->in_bytes = o;
     o = 0;
     fs->o_disp = o;  o += up256(fs->px * 4 * batch);
@@ -269,6 +270,8 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_hint, s.h_in + fs->o_hint, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
         if (fs->flags & VPPX_FS_GOCC)
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gocc, s.h_in + fs->o_gocc, fs->px * nb, hipMemcpyHostToDevice, fs->s_in));
+        if (fs->flags & VPPX_FS_GUIDED)
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_valid, s.h_in + fs->o_valid, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
         VPPX_HIP(hipEventRecord(s.ev_in, fs->s_in));
     }
     VppxVppParams vp = fs->vp;
@@ -284,7 +287,12 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         rc = vppx_inputs_ready_event(ctx, (void *)s.ev_in);
         if (rc) return rc;
         ctx->draws_dst = (vp.method == VPPX_METHOD_RND) ? (unsigned long long *)(s.d_out + fs->o_draws) : nullptr;
-        if (fs->have_op)
+        if (fs->flags & VPPX_FS_GUIDED) // (never the lock-step kernel: no re-run)
+            rc = vppx_occ_vpp_rsgm_guided_dev(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left,
+                                              s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
+                                              (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr, (const float *)(s.d_in + fs->o_valid),
+                                              (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp));
+        else if (fs->have_op)
             rc = vppx_occ_vpp_rsgm_dev(ctx, &fs->op, &vp, &fs->rp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right,
                                        (const float *)(s.d_in + fs->o_hint), (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv,
                                        (float *)(s.d_out + fs->o_disp));
@@ -336,13 +344,14 @@ static int fs_close_batch(vppx_fstream *fs)
     return 0;
 }
 
-extern "C" int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ)
+static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ,
+                   const float *validhints, const char *name)
 {
-    if (!fs) { vppx_set_error("vppx_fstream_push: stream is NULL"); return VPPX_E_INVALID_ARG; }
     if (!left || !right || !hints || (((fs->flags & VPPX_FS_GOCC) != 0) != (g_occ != nullptr))) {
-        vppx_set_error("vppx_fstream_push: left, right, hints%s", (fs->flags & VPPX_FS_GOCC) ? " and g_occ (VPPX_FS_GOCC)" : "; g_occ only with VPPX_FS_GOCC");
+        vppx_set_error("%s: left, right, hints%s", name, (fs->flags & VPPX_FS_GOCC) ? " and g_occ (VPPX_FS_GOCC)" : "; g_occ only with VPPX_FS_GOCC");
         return VPPX_E_INVALID_ARG;
     }
+    if ((fs->flags & VPPX_FS_GUIDED) && !validhints) { vppx_set_error("%s: validhints is NULL", name); return VPPX_E_INVALID_ARG; }
     DevGuard g(fs->ctx->device);
     if (fs->fill_count >= fs->batch) {
         // the push that filled this batch could not submit it (its error was returned): submit it now, or take nothing -- a
@@ -353,19 +362,41 @@ extern "C" int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const ui
     Slot &s = fs->slots[fs->fill_batch % fs->depth];
     if (fs->fill_count == 0 && s.submitted && fs->fill_batch - fs->pop_batch >= (uint64_t)fs->depth) {
         // every slot holds a batch whose results have not been popped: its ring areas (and device inputs, kept for a re-run) are in use
-        vppx_set_error("vppx_fstream_push: %d batches are waiting to be popped (depth %d); pop results first", fs->depth, fs->depth);
+        vppx_set_error("%s: %d batches are waiting to be popped (depth %d); pop results first", name, fs->depth, fs->depth);
         return VPPX_E_INVALID_ARG;
     }
     const int i = fs->fill_count;
-    CopyJob jobs[4] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
+    CopyJob jobs[5] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
                        {s.h_in + fs->o_right + fs->img * i, right, fs->img},
                        {s.h_in + fs->o_hint + fs->px * 4 * i, hints, fs->px * 4},
-                       {g_occ ? s.h_in + fs->o_gocc + fs->px * i : nullptr, g_occ, fs->px}};
-    fs->pool->copy(jobs, 4);
+                       {g_occ ? s.h_in + fs->o_gocc + fs->px * i : nullptr, g_occ, fs->px},
+                       {validhints ? s.h_in + fs->o_valid + fs->px * 4 * i : nullptr, validhints, fs->px * 4}};
+    fs->pool->copy(jobs, 5);
     fs->fill_count++;
     fs->pushed++;
     if (fs->fill_count == fs->batch) return fs_close_batch(fs);
     return 0;
+}
+
+extern "C" int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ)
+{
+    if (!fs) { vppx_set_error("vppx_fstream_push: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_GUIDED) {
+        vppx_set_error("vppx_fstream_push: the stream was created with VPPX_FS_GUIDED; push frames with vppx_fstream_push_guided");
+        return VPPX_E_INVALID_ARG;
+    }
+    return fs_push(fs, left, right, hints, g_occ, nullptr, "vppx_fstream_push");
+}
+
+extern "C" int vppx_fstream_push_guided(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints,
+                                        const uint8_t *g_occ, const float *validhints)
+{
+    if (!fs) { vppx_set_error("vppx_fstream_push_guided: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (!(fs->flags & VPPX_FS_GUIDED)) {
+        vppx_set_error("vppx_fstream_push_guided: the stream was created without VPPX_FS_GUIDED; push frames with vppx_fstream_push");
+        return VPPX_E_INVALID_ARG;
+    }
+    return fs_push(fs, left, right, hints, g_occ, validhints, "vppx_fstream_push_guided");
 }
 
 extern "C" int vppx_fstream_flush(vppx_fstream *fs)

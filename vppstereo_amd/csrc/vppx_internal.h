@@ -93,7 +93,8 @@ enum WsSlot {
     WS_V3ERR,        // device-side copy of the fused kernel's error word (void_if_lost_kernel)
     WS_WE_TRACE,     // experiment builds: per-block wall-clock trace of the W/E kernel
     WS_WE_HAND,      // W/E kernel: path states handed from piece to piece of the split tail lines + a flag per line (We12Args)
-    WS_DSI,          // materialised cost volume (stage API only)
+    WS_DSI,          // materialised cost volume (stage API), or the hint pixels' cost rows of a guided call
+    WS_GUIDED_MAP,   // guided call: row index of every padded pixel (+ the row counter behind it)
     WS_DISP_L0,
     WS_DISP_L1,
     WS_DISP_R0,
@@ -253,7 +254,7 @@ struct vppx_ctx {
         int B, H, W, C;
         VppxVppParams vp;
         VppxRsgmParams rp;
-        const void *ptr[8];
+        const void *ptr[9];
         VppxOccParams op;
         int has_op;
         void *stream;
@@ -323,11 +324,16 @@ int rsgm_launch_pad_gray_census(vppx_ctx *ctx, const RsgmGeom &g, const u8 *left
                                 u32 *census_l, u32 *census_r); // the three of the fused pipeline in one launch
 int rsgm_launch_census_n(vppx_ctx *ctx, int B, int Hp, int Wp, int n, const u8 *const *gray, u32 *const *census); // n <= 2
 int rsgm_launch_cost(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u32 *cl, const u32 *cr, u16 *dsi);
-int rsgm_launch_guided_dsi(vppx_ctx *ctx, const RsgmGeom &g, u16 *dsi, const float *hints, const float *valid);
-// 8-path aggregation.  Cost source: census pair (dsi == nullptr) or a materialised u16 DSI.
+// --guided: the hint pixels' re-weighted cost rows (u16 [n][D], n <= B*H*W, never read back by the host) and the row index
+// of every padded pixel (int [B][Hp][Wp], -1 = not a hint pixel); *count is the row counter (cleared by the launch)
+int rsgm_launch_guided_rows(vppx_ctx *ctx, const RsgmGeom &g, const u32 *cl, const u32 *cr, const float *hints,
+                            const float *valid, int *gmap, u16 *rows, u32 *count);
+// 8-path aggregation.  Cost source: census pair (dsi == nullptr), a materialised u16 DSI, or (gmap != nullptr) the census
+// pair with the guided rows `dsi` of rsgm_launch_guided_rows at the pixels gmap names.
 // Writes the 8 per-path volumes into `paths` (element size elem_bytes = 1 or 2).
 int rsgm_launch_paths(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gray, const u32 *cl, const u32 *cr,
-                      const u16 *dsi, const u16 *p2lut, int p1, void *paths, int elem_bytes, int dir_mask);
+                      const u16 *dsi, const u16 *p2lut, int p1, void *paths, int elem_bytes, int dir_mask,
+                      const int *gmap = nullptr);
 // band-marching vertical/diagonal paths (3 summed paths per pass, one byte per cell)
 int rsgm_vert3_probe(vppx_ctx *ctx, u32 *scratch_dev, bool *ok);
 bool rsgm_vert3_supported(int B, int Hp, int Wp, int D, int maxp2);

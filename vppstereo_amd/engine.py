@@ -62,19 +62,25 @@ class Engine:
                                          _ptr(g_occ), None, None))
         return l, r
 
-    def rsgm(self, left, left_vpp, right_vpp, out=None, **kw):
+    def rsgm(self, left, left_vpp, right_vpp, out=None, hints=None, validhints=None, **kw):
+        """compute_rsgm for a batch; hints / validhints (float32 [B,H,W], both or neither): --guided (rsgm.py:265-268)."""
         torch = self.torch
         self._chk(left, torch.uint8, 4, "left")
         B, H, W, Cc = left.shape
         self._chk(left_vpp, torch.uint8, 4, "left_vpp", left.shape)
         self._chk(right_vpp, torch.uint8, 4, "right_vpp", left.shape)
+        if (hints is None) != (validhints is None):
+            raise ValueError("hints and validhints go together (--guided needs both)")
+        if hints is not None:
+            self._chk(hints, torch.float32, 3, "hints", (B, H, W))
+            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
         if out is None:
             out = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
         self._chk(out, torch.float32, 3, "out", (B, H, W))
         self._bind_stream()
         p = _lib.rsgm_params(**kw)
         _lib.check(self.lib.vppx_rsgm_dev(self.ctx.handle, C.byref(p), B, H, W, Cc, _ptr(left), _ptr(left_vpp),
-                                          _ptr(right_vpp), None, None, _ptr(out)))
+                                          _ptr(right_vpp), _ptr(hints), _ptr(validhints), _ptr(out)))
         return out
 
     def rsgm_post(self, disp_l_pad, disp_r_pad, h, w, subpixel=True, out=None):
@@ -96,7 +102,7 @@ class Engine:
         return out
 
     def vpp_rsgm(self, left, right, hints, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
-                 rsgm_kw=None, occ_out=None, inputs_ready=None):
+                 rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None):
         """The whole hot path for a batch: one call, no host round trips, no synchronisation.
 
         g_occ: None, a uint8 [B,H,W] mask tensor, or -- test.py:154 with --maskocc in the same call --
@@ -104,7 +110,9 @@ class Engine:
         computed on the way (vppx_occ_vpp_rsgm_dev) and also written to `occ_out` when given.
         inputs_ready: a ``torch.cuda.Event`` recorded after the work that produced this call's input tensors.  Only
         matters with `set_pipeline(True)`: the front stage then waits for that event instead of for everything queued on
-        the current stream, and can overlap the previous call's tail."""
+        the current stream, and can overlap the previous call's tail (it then covers `validhints` too).
+        validhints: float32 [B,H,W] or None.  Given, the call is --guided (test.py:207-223): `hints` also re-weight the
+        matching costs wherever validhints > 0 (vppx_occ_vpp_rsgm_guided_dev), with either form of g_occ."""
         torch = self.torch
         heuristic = isinstance(g_occ, (str, dict))
         if isinstance(g_occ, str) and g_occ != "occlusion_heuristic":
@@ -113,6 +121,8 @@ class Engine:
         if out is None:
             out = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
         self._chk(out, torch.float32, 3, "out", (B, H, W))
+        if validhints is not None:
+            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
         for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
             if t is not None:
                 self._chk(t, torch.uint8, 4, n, left.shape)
@@ -125,7 +135,14 @@ class Engine:
         rp = _lib.rsgm_params(**(rsgm_kw or {}))
         if inputs_ready is not None:
             _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
-        if heuristic:
+        if validhints is not None:
+            op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
+            _lib.check(self.lib.vppx_occ_vpp_rsgm_guided_dev(self.ctx.handle, C.byref(op) if heuristic else None,
+                                                             C.byref(vp), C.byref(rp), B, H, W, Cc, _ptr(left), _ptr(right),
+                                                             _ptr(hints), None if heuristic else _ptr(g_occ),
+                                                             _ptr(validhints), _ptr(occ_out), _ptr(l_vpp), _ptr(r_vpp),
+                                                             _ptr(out)))
+        elif heuristic:
             op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {}))
             _lib.check(self.lib.vppx_occ_vpp_rsgm_dev(self.ctx.handle, C.byref(op), C.byref(vp), C.byref(rp), B, H, W, Cc,
                                                       _ptr(left), _ptr(right), _ptr(hints), _ptr(occ_out), _ptr(l_vpp),

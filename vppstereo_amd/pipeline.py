@@ -2,6 +2,7 @@
 `vpp_standalone.vpp` and `rsgm.compute_rsgm` remain the drop-ins for its three call sites).
 
     disp = run_frame(left, right, hints, maskocc=True)                      # test.py --vpp --maskocc --stereomodel rsgm
+    disp = run_frame(left, right, hints, validhints=valid)                  # test.py --vpp --guided --stereomodel rsgm
     disp, lc, rc, conf = run_frame(..., return_patterns=True)
 
 The pair, the hints and the mask cross PCIe once, the mask never leaves the device
@@ -30,11 +31,14 @@ def _vpp_params(vk, method, dmin, dmax):
     return p
 
 
-def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw=None, rsgm_kw=None, return_patterns=False):
+def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw=None, rsgm_kw=None, return_patterns=False,
+              validhints=None):
     """left, right: uint8 [H,W,3] or [H,W]; hints: float [H,W] (0 = none).  maskocc: compute g_occ with the occlusion heuristic
     (test.py:154) -- else `g_occ` (uint8 [H,W] or None) is used as given.  vpp_kw: keywords of `vpp_standalone.vpp`
-    (wsize, blending, c_occ, ...); rsgm_kw: keywords of `rsgm.compute_rsgm` (dmax, p1, ...).  Returns the float32 disparity
-    map, or (disparity, left_vpp, right_vpp, conf_map or None) with return_patterns."""
+    (wsize, blending, c_occ, ...); rsgm_kw: keywords of `rsgm.compute_rsgm` (dmax, p1, ...).  validhints: float [H,W] or None;
+    given, the call is --guided (test.py:207-223): `hints` also re-weight the matching costs of compute_rsgm wherever
+    validhints > 0.  Returns the float32 disparity map, or (disparity, left_vpp, right_vpp, conf_map or None) with
+    return_patterns."""
     vk = dict(vpp_kw or {})
     method = vk.pop("method", "rnd")
     assert method in ["rnd", "maxDistance"]
@@ -43,6 +47,11 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
     gt = np.ascontiguousarray(np.asarray(hints, dtype=np.float32))
     if left.shape != right.shape or left.shape[:2] != gt.shape:
         raise ValueError("left, right and hints must agree in height and width")
+    vh = None
+    if validhints is not None:
+        vh = np.ascontiguousarray(np.asarray(validhints, dtype=np.float32))
+        if vh.shape != gt.shape:
+            raise ValueError("validhints must have the shape of hints")
     h, w = gt.shape
     ch = 1 if left.ndim == 2 else left.shape[2]
     dmin, dmax = hint_range(gt)
@@ -73,9 +82,15 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
         conf = np.empty((h, w), np.uint8) if maskocc else None
     draws = (C.c_uint64 * 1)()
     try:
-        _lib.check(lib.vppx_occ_vpp_rsgm_host(ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp), 1, h, w, ch,
-                                              _lib.np_ptr(left), _lib.np_ptr(right), _lib.np_ptr(gt), _lib.np_ptr(occ), _lib.np_ptr(conf),
-                                              _lib.np_ptr(lc), _lib.np_ptr(rc), _lib.np_ptr(disp), draws))
+        if vh is not None:
+            _lib.check(lib.vppx_occ_vpp_rsgm_guided_host(ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp), 1,
+                                                         h, w, ch, _lib.np_ptr(left), _lib.np_ptr(right), _lib.np_ptr(gt), _lib.np_ptr(occ),
+                                                         _lib.np_ptr(vh), _lib.np_ptr(conf), _lib.np_ptr(lc), _lib.np_ptr(rc),
+                                                         _lib.np_ptr(disp), draws))
+        else:
+            _lib.check(lib.vppx_occ_vpp_rsgm_host(ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp), 1, h, w,
+                                                  ch, _lib.np_ptr(left), _lib.np_ptr(right), _lib.np_ptr(gt), _lib.np_ptr(occ),
+                                                  _lib.np_ptr(conf), _lib.np_ptr(lc), _lib.np_ptr(rc), _lib.np_ptr(disp), draws))
     except _lib.VppxError as e:
         raise Exception(str(e)) from e   # the reference raises bare Exception(msg) (rsgm.py:31-40,166)
     if method == "rnd":
@@ -101,10 +116,12 @@ class FrameStream:
     batched and sharded)  `use_distance_patch`: dmin / dmax are each frame's own, computed on the device
     (a frame whose hints all have ONE value, where the reference divides by zero, gets the full patch size).  batch=None: one round of the lock-step kernel for this shape (vppx_batch_quantum), else 16.
     Results: the float32 disparity map, or with return_patterns (disparity, left_vpp, right_vpp, conf_map or None); each a fresh
-    array.  `draws` of the last popped frame (rand() calls it consumed) is in `last_draws`."""
+    array.  `draws` of the last popped frame (rand() calls it consumed) is in `last_draws`.
+    guided=True: --guided (test.py:207-223); every push brings the frame's validhints, and the frame equals
+    `run_frame(..., validhints=...)` with seed + f."""
 
     def __init__(self, height, width, channels=3, batch=None, depth=3, seed=1, maskocc=False, with_g_occ=False, occ_kw=None,
-                 vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1):
+                 vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1, guided=False):
         vk = dict(vpp_kw or {})
         method = vk.pop("method", "rnd")
         assert method in ["rnd", "maxDistance"]
@@ -125,7 +142,9 @@ class FrameStream:
             batch = int(self._lib.vppx_batch_quantum(self._ctx.handle, self.h, self.w, int(rp.dmax))) or 16
         self.batch, self.depth = int(batch), int(depth)
         self._patterns, self._mask, self._gocc = bool(return_patterns), bool(maskocc and return_patterns), bool(with_g_occ)
+        self._guided = bool(guided)
         flags = (_lib.FS_PATTERNS if self._patterns else 0) | (_lib.FS_MASK if self._mask else 0) | (_lib.FS_GOCC if self._gocc else 0)
+        flags |= _lib.FS_GUIDED if self._guided else 0
         self._h = C.c_void_p()
         try:
             _lib.check(self._lib.vppx_fstream_create(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp),
@@ -166,9 +185,10 @@ class FrameStream:
             raise ValueError(f"{name}: expected shape {shape}, got {a.shape}")
         return a
 
-    def push(self, left, right, hints, g_occ=None):
+    def push(self, left, right, hints, g_occ=None, validhints=None):
         """One frame in (copied before the call returns).  The frame that completes a batch submits it; if that submit fails
-        the push raises but HAS taken the frame, and the next push or `flush()` submits the batch again."""
+        the push raises but HAS taken the frame, and the next push or `flush()` submits the batch again.  validhints: float
+        [H,W], required on a guided stream and refused on any other."""
         left = self._arr(left, np.uint8, self._shape, "left")
         right = self._arr(right, np.uint8, self._shape, "right")
         hints = self._arr(hints, np.float32, (self.h, self.w), "hints")
@@ -181,6 +201,13 @@ class FrameStream:
                 raise ValueError("g_occ: expected shape (H, W)")
         elif g_occ is not None:
             raise ValueError("g_occ given but the stream was created without with_g_occ=True")
+        vh = None
+        if self._guided:
+            if validhints is None:
+                raise ValueError("the stream was created with guided=True: every push brings validhints")
+            vh = self._arr(validhints, np.float32, (self.h, self.w), "validhints")
+        elif validhints is not None:
+            raise ValueError("validhints given but the stream was created without guided=True")
         # a full batch whose submit failed (an earlier push raised, having taken its frame): submit it before anything else --
         # raises again, and takes nothing, if it still fails
         if self._fill == self.batch:
@@ -190,8 +217,12 @@ class FrameStream:
             while len(self._inflight) >= self.depth:
                 self._early.append(self._pop_native())
         try:
-            _lib.check(self._lib.vppx_fstream_push(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data,
-                                                   occ.ctypes.data if occ is not None else None))
+            occ_p = occ.ctypes.data if occ is not None else None
+            if vh is not None:
+                _lib.check(self._lib.vppx_fstream_push_guided(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data, occ_p,
+                                                              vh.ctypes.data))
+            else:
+                _lib.check(self._lib.vppx_fstream_push(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data, occ_p))
         except _lib.VppxError as e:
             # the native stream may have taken the frame and failed only to submit the batch it completed: stay in step
             if self.counts()[0] > self._pushed:
@@ -257,7 +288,8 @@ class FrameStream:
         return tuple(int(x.value) for x in v)
 
     def run(self, frames):
-        """Generator: results for an iterable of (left, right, hints[, g_occ]) in input order; keeps about `depth` batches in flight."""
+        """Generator: results for an iterable of (left, right, hints[, g_occ]) in input order -- on a guided stream
+        (left, right, hints, g_occ or None, validhints) -- keeps about `depth` batches in flight."""
         for fr in frames:
             self.push(*fr)
             # whole batches that must be complete by now: everything but the last depth - 1 submitted ones
@@ -286,5 +318,5 @@ def run_stream(frames, **kw):
     def chain():
         yield first
         yield from it
-    with FrameStream(l.shape[0], l.shape[1], ch, with_g_occ=kw.pop("with_g_occ", len(first) > 3), **kw) as fs:
+    with FrameStream(l.shape[0], l.shape[1], ch, with_g_occ=kw.pop("with_g_occ", len(first) > 3 and first[3] is not None), **kw) as fs:
         yield from fs.run(chain())
