@@ -437,6 +437,19 @@ int vppx_last_call_parts(vppx_ctx *ctx);
 /* Pieces per line of the last, part-filled layer of waves in the last launch of the W / E register-window kernel (its lines are
  * cut into 2..8 pieces that hand the path state on through memory when that evens out the SIMDs' load); 1 = nothing was cut. */
 int vppx_we_last_pieces(vppx_ctx *ctx);
+/* The kernel instantiations the last rSGM-bearing call launched, as a comma-separated list in launch order, each one once
+ * (a call that ran in parts lists the union over its parts), e.g. "paths<8,24,exact,guided,u16,dirs=ff>,
+ * sum_lr<12,u16,8,64,spare,nosw4,general,16,partw>".  Names: paths<lanes per pixel,disparities per lane,exact|partial,
+ * census|dsi|guided,u8|u16,dirs=ff|11> (line-parallel kernel, 8 paths or W + E), we12<DPL> (W / E register-window
+ * kernel), vert3<DPL> / vert4<DPL> (fused vertical kernel, 8 / 16 pixels per wave), vert_band<DPL>, sum_lr<DPL,u8|u16,
+ * volumes,T,spare|nospare,sw4|nosw4,fast|general,lanes per pixel,fullw|partw> and sum_trap<DPL,T,spare|nospare> (fused
+ * sum / WTA), sum_wta<DPL,exact|partial,u8|u16> + wta_right_t (materialised sum, then the right view).  Commas inside
+ * <> belong to a name.  The list is cleared at the entry of vppx_rsgm_dev / _host, vppx_vpp_rsgm_dev, vppx_occ_vpp_rsgm_*
+ * (guided or not) and vppx_aggregate / _img; the timing helpers re-launch the last call's aggregation and add to it.  A
+ * graph replay (vppx_set_graph_mode) launches nothing from the host and reports the routes of the call it captured.  The
+ * children of VPPX_SUBSTREAMS keep lists of their own, which are not merged: a call split over them lists nothing.
+ * Writes at most n - 1 characters and a NUL to buf (buf may be NULL when n == 0); returns the length of the whole list. */
+int vppx_last_routes(vppx_ctx *ctx, char *buf, int n);
 /* Per-stage hipEvent timing of the last vppx_vpp_rsgm_dev/vppx_rsgm_dev call when stage
  * timing is enabled: fills ms[0..n) and returns the number of stages; names via
  * vppx_stage_name(i). */
@@ -454,6 +467,8 @@ const char *vppx_stage_name(int i);
  *   VPPX_V3_PPW         8 / 16: pixels per wave of the fused vertical kernel (default: by batch size)
  *   VPPX_V3_TIMEOUT_MS  bound of one neighbour wait of the lock-step kernel (default 250)
  *   VPPX_V3_SPIN_LIMIT  the same bound in polls (tests force the give-up path with 1; default unbounded)
+ *   VPPX_GUIDED_PART_MB budget in MiB of the eight u16 path volumes of one part of a guided batch (default 49152, i.e. 48 GiB;
+ *                       tests set a few MiB to run small batches in parts)
  *   VPPX_VARIANT        comma-separated tokens that select alternative kernels with identical results, each run by
  *                       tests/test_gpu_variants.py: sum_general, sum_gl8, sum_trap0, sum_trap1 (fused sum / WTA kernel), gw4, gw8,
  *                       gw16 (lanes per pixel of the line-parallel kernel), we_line (W / E on the line-parallel kernel), we_after (W / E never next to

@@ -155,3 +155,22 @@ def test_every_environment_variable_the_library_reads_is_documented_in_the_heade
     assert {"we_stale", "fs_fail_submit=", "fs_fail_from=", "we_layer="} <= tokens, tokens
     for t in tokens:
         assert re.search(r"\b" + t + (r"" if t.endswith("=") else r"\b"), header), t
+
+
+def test_route_query_is_exported_declared_and_bound():
+    """vppx_last_routes: declared with its signature, exported, bound in Python (Engine.last_routes); a NULL context fails
+    with a message; the list splits at the commas outside <>; VPPX_GUIDED_PART_MB is documented."""
+    import inspect
+    from vppstereo_amd import engine
+    lib = _lib.load()
+    hdr = open(os.path.join(ROOT, "include", "vppx.h")).read()
+    assert "int vppx_last_routes(vppx_ctx *ctx, char *buf, int n);" in hdr
+    assert "vppx_last_routes" in _lib.EXPORTS and hasattr(lib, "vppx_last_routes")
+    assert lib.vppx_last_routes.argtypes == [C.c_void_p, C.c_char_p, C.c_int]
+    assert list(inspect.signature(engine.Engine.last_routes).parameters) == ["self"]
+    buf = C.create_string_buffer(8)
+    assert lib.vppx_last_routes(C.c_void_p(), buf, 8) == -7 and b"context is NULL" in lib.vppx_last_error()
+    assert _lib.split_routes("paths<8,24,exact,guided,u16,dirs=ff>,sum_lr<12,u16,8,64,spare,nosw4,general,16,partw>,wta_right_t") == [
+        "paths<8,24,exact,guided,u16,dirs=ff>", "sum_lr<12,u16,8,64,spare,nosw4,general,16,partw>", "wta_right_t"]
+    assert _lib.split_routes("") == []
+    assert re.search(r"VPPX_GUIDED_PART_MB\s", hdr)

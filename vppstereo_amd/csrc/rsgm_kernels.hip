@@ -1482,6 +1482,7 @@ static int launch_we12(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gr
     else WE12_LAUNCH(16);
 #undef WE12_LAUNCH
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, "we12<%d>", D == 128 ? 8 : (D == 192 ? 12 : 16));
     ctx->we_last_pieces = a.pieces;
     if (a.pieces > 1 && ctx->knobs.we_stale) {
         // tests: the worst records a launch can leave -- every dword reads "all pieces done" to the next cut launch's flags
@@ -1526,6 +1527,9 @@ static int launch_paths_t(vppx_ctx *ctx, PathArgs a, int B, int src, int elem_by
         sgm_paths_kernel<GW, DPL, true, COST_CENSUS, u8><<<grid, 256, 0, ctx->stream>>>(a);
     }
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, "paths<%d,%d,%s,%s,%s,dirs=%02x>", GW, DPL, exact ? "exact" : "partial",
+               src == COST_DSI ? "dsi" : (src == COST_GUIDED ? "guided" : "census"),
+               (src == COST_CENSUS && exact && elem_bytes == 1) ? "u8" : "u16", a.dir_mask);
     return 0;
 }
 
@@ -1832,7 +1836,7 @@ int rsgm_launch_vert(vppx_ctx *ctx, hipStream_t stream, int B, int Hp, int Wp, i
     if (D == 64) LAUNCH_V(4); else if (D == 128) LAUNCH_V(8); else if (D == 192) LAUNCH_V(12); else LAUNCH_V(16);
 #undef LAUNCH_V
     VPPX_CHECK_LAUNCH();
-    (void)ctx;
+    route_note(ctx, "vert_band<%d>", D / 16);
     return 0;
 }
 
@@ -2710,6 +2714,7 @@ int rsgm_launch_vert3_range(vppx_ctx *ctx, hipStream_t stream, int B_total, int 
     else if (D == 192) sgm_vert3_kernel<24><<<grid, 256, 0, stream>>>(a);
     else sgm_vert3_kernel<32><<<grid, 256, 0, stream>>>(a);
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, wide ? "vert4<%d>" : "vert3<%d>", (wide ? D / 4 : D / 8));
     return 0;
 }
 
@@ -3014,6 +3019,7 @@ static int launch_sum_wta_t(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const v
         sum_wta_kernel<DPL, false, u16><<<grid, 256, lds, ctx->stream>>>((const u16 *)paths, vol, S, ST, disp, Hp, Wp, D, fu, sub);
     }
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, "sum_wta<%d,%s,%s>", DPL, (elem_bytes == 1 || exact) ? "exact" : "partial", elem_bytes == 1 ? "u8" : "u16");
     return 0;
 }
 
@@ -3521,6 +3527,7 @@ static int launch_trap(vppx_ctx *ctx, const VolPtrs &vp, int B, int Hp, int Wp, 
     chunks = (Hp + rpb - 1) / rpb;
     sum_wta_trap_kernel<DPL, T, SPARE><<<dim3(chunks, B), 16 * T, lds, ctx->stream>>>(vp, disp_l, disp_r, Hp, Wp, fu, sub, rpb);
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, "sum_trap<%d,%d,%s>", DPL, T, SPARE ? "spare" : "nospare");
     return 0;
 }
 
@@ -3569,6 +3576,8 @@ static int launch_lr_t2(vppx_ctx *ctx, const VolPtrs &vp, int B, int Hp, int Wp,
     chunks = (Hp + rpb - 1) / rpb;
     sum_wta_lr_kernel<DPL, IT, NV, T, SPARE, SW4, FAST, GL, FULLW><<<dim3(chunks, B), GL * T, lds, ctx->stream>>>(vp, disp_l, disp_r, Hp, Wp, fu, sub, rpb);
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, "sum_lr<%d,%s,%d,%d,%s,%s,%s,%d,%s>", DPL, sizeof(IT) == 1 ? "u8" : "u16", NV, T, SPARE ? "spare" : "nospare",
+               SW4 ? "sw4" : "nosw4", FAST ? "fast" : "general", GL, FULLW ? "fullw" : "partw");
     return 0;
 }
 
@@ -3765,6 +3774,7 @@ int rsgm_launch_wta_right_t(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u
     dim3 grid((Wp + 255) / 256, Hp, B);
     wta_right_t_kernel<<<grid, 256, 0, ctx->stream>>>(ST, disp, Hp, Wp, D, fu);
     VPPX_CHECK_LAUNCH();
+    route_note(ctx, "wta_right_t");
     return 0;
 }
 

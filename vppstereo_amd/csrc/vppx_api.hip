@@ -23,6 +23,39 @@ void vppx_set_error(const char *fmt, ...)
 }
 
 extern "C" const char *vppx_last_error(void) { return g_err; }
+
+// ---------------------------------------------------------------------------------------
+// routes: the kernel instantiations the last rSGM-bearing call launched (vppx_last_routes)
+// ---------------------------------------------------------------------------------------
+void route_note(vppx_ctx *ctx, const char *fmt, ...)
+{
+    char buf[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    for (const std::string &r : ctx->routes)
+        if (r == buf) return;
+    ctx->routes.emplace_back(buf);
+}
+
+extern "C" int vppx_last_routes(vppx_ctx *ctx, char *buf, int n)
+{
+    if (!ctx) { vppx_set_error("context is NULL (vppx_create failed? there is no CPU fallback)"); return VPPX_E_NO_DEVICE; }
+    if (n < 0 || (n > 0 && !buf)) { vppx_set_error("vppx_last_routes: bad buffer"); return VPPX_E_INVALID_ARG; }
+    std::string all;
+    for (const std::string &r : ctx->routes) {
+        if (!all.empty()) all += ',';
+        all += r;
+    }
+    if (n > 0) {
+        const size_t k = all.size() < (size_t)n - 1 ? all.size() : (size_t)n - 1;
+        memcpy(buf, all.data(), k);
+        buf[k] = '\0';
+    }
+    return (int)all.size();
+}
+
 extern "C" int vppx_version(void) { return VPPX_VERSION; }
 
 #define VPPX_ENTER(ctx)                                                                                              \
@@ -207,6 +240,8 @@ extern "C" int vppx_create(vppx_ctx **out, int device)
 #endif
         e = getenv("VPPX_V3_SPIN_LIMIT");
         if (e && atoi(e) > 0) ctx->v3.spin_limit = (unsigned)atoi(e);
+        e = getenv("VPPX_GUIDED_PART_MB");
+        if (e && atoll(e) > 0) ctx->knobs.guided_part_bytes = (unsigned long long)atoll(e) << 20;
     }
     *out = ctx;
     return 0;
@@ -1064,15 +1099,15 @@ static int check_frames(int B, int H, int W, int C)
     return 0;
 }
 
-// A guided batch keeps 8 u16 path volumes (16 bytes per cell): one whose volumes would exceed this runs in parts of as many
-// frames as fit (at least one).  (8 frames of 1536x2048x256 would need 103 GB.)
-#define VPPX_GUIDED_PART_BYTES (48ull << 30)
-static int guided_frames_per_part(int H, int W, int C, int dmax)
+// A guided batch keeps 8 u16 path volumes (16 bytes per cell): one whose volumes would exceed the budget (48 GiB;
+// VPPX_GUIDED_PART_MB sets another) runs in parts of as many frames as fit (at least one).  (8 frames of 1536x2048x256
+// would need 103 GB.)
+static int guided_frames_per_part(const vppx_ctx *ctx, int H, int W, int C, int dmax)
 {
     RsgmGeom g1;
     make_geom(1, H, W, C, dmax, g1);
     const unsigned long long per = (unsigned long long)g1.Hp * g1.Wp * g1.D * 16ull;
-    const unsigned long long n = VPPX_GUIDED_PART_BYTES / per;
+    const unsigned long long n = ctx->knobs.guided_part_bytes / per;
     return n < 1 ? 1 : (n > (unsigned long long)INT_MAX ? INT_MAX : (int)n);
 }
 
@@ -1082,6 +1117,7 @@ extern "C" int vppx_rsgm_dev(vppx_ctx *ctx, const VppxRsgmParams *p, int B, int 
 {
     int rc;
     VPPX_ENTER(ctx);
+    routes_reset(ctx);
     if ((rc = lockstep_check(ctx))) return rc;
     if (!p || !left || !left_vpp || !right_vpp || !disp_out) { vppx_set_error("vppx_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
     if ((rc = check_frames(B, H, W, C))) return rc;
@@ -1089,7 +1125,7 @@ extern "C" int vppx_rsgm_dev(vppx_ctx *ctx, const VppxRsgmParams *p, int B, int 
     if ((hints == nullptr) != (validhints == nullptr)) { hints = nullptr; validhints = nullptr; } // rsgm.py:265 needs both
     RsgmGeom g;
     stage_begin(ctx);
-    const int q = hints ? guided_frames_per_part(H, W, C, p->dmax) : B;
+    const int q = hints ? guided_frames_per_part(ctx, H, W, C, p->dmax) : B;
     if (q >= B) {
         make_geom(B, H, W, C, p->dmax, g);
         return rsgm_core(ctx, *p, g, left, left_vpp, right_vpp, disp_out, hints, validhints);
@@ -1552,7 +1588,7 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
     }
     bool budget = false; // guided: parts of the memory budget (a remainder is a part of its own, never merged into a full one)
     if (validhints) {
-        const int fb = guided_frames_per_part(H, W, C, rp->dmax);
+        const int fb = guided_frames_per_part(ctx, H, W, C, rp->dmax);
         if (fb < B && (q <= 0 || q > fb)) {
             q = fb;
             budget = true;
@@ -1616,6 +1652,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
                           const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
 {
     int rc;
+    routes_reset(ctx); // (sub-stream children record into their own lists: not merged here)
     if ((rc = lockstep_check(ctx))) return rc;
     if (!vp || !rp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_vpp_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
     if ((rc = check_frames(B, H, W, C))) return rc;
@@ -1642,6 +1679,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         if (lut_ok && ctx->gexec && ctx->have_gkey && memcmp(&key, &ctx->gkey, sizeof(key)) == 0) {
             VPPX_HIP(hipGraphLaunch(ctx->gexec, ctx->stream));
             ctx->graph_replays++;
+            ctx->routes = ctx->graph_routes; // what the captured call launched
             return 0;
         }
         if (lut_ok && ctx->have_lastkey && memcmp(&key, &ctx->lastkey, sizeof(key)) == 0) {
@@ -1666,6 +1704,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
                     if (e == hipSuccess) {
                         ctx->gkey = key;
                         ctx->have_gkey = true;
+                        ctx->graph_routes = ctx->routes;
                         ctx->graph_captures++;
                         VPPX_HIP(hipGraphLaunch(ctx->gexec, ctx->stream));
                         ctx->graph_replays++;
@@ -1948,6 +1987,7 @@ extern "C" int vppx_aggregate_img(vppx_ctx *ctx, const uint8_t *img, int channel
 {
     int rc;
     VPPX_ENTER(ctx);
+    routes_reset(ctx);
     if (!img || !dsi || !dsi_agg || w <= 0 || h <= 0) { vppx_set_error("vppx_aggregate: bad arguments"); return VPPX_E_INVALID_ARG; }
     if (channels != 1 && channels != 3) { vppx_set_error("vppx_aggregate: image must have 1 or 3 channels (got %d)", channels); return VPPX_E_INVALID_ARG; }
     if ((rc = check_w16(w))) return rc; // rsgm.py:51-58 order

@@ -160,7 +160,12 @@ struct vppx_ctx {
         int fs_fail_from = 0;   // "fs_fail_from=K" (tests): ... and every submit from the K-th on
         int we_lq = -1;       // "we_lq0" / "we_lq1": the W/E kernel's left-view operand loads (per step / per quad of steps); default by launch
         int sum_blocks = 0;   // (experiment builds) "sum_blocks=N": forced number of blocks of the sum / WTA kernel
+        unsigned long long guided_part_bytes = 48ull << 30; // VPPX_GUIDED_PART_MB: volume budget of one part of a guided batch
     } knobs;
+    // kernel instantiations the last rSGM-bearing call launched, distinct, in launch order (vppx_last_routes): cleared at the
+    // entry of every such call, appended to by the launchers where the template arguments are known
+    std::vector<std::string> routes;
+    std::vector<std::string> graph_routes; // those of the captured call: a replay launches nothing from the host and restores them
     int use_vert = -1;             // VPPX_VERT: -1 pick by shape (default), 0 eight line-parallel paths, 1 band marching, 3 fused vertical kernel
     int last_vert = 0;             // what the last aggregation used (vppx_uses_vert)
     int last_parts = 1;            // parts the last fused call ran as (vppx_last_call_parts)
@@ -286,6 +291,10 @@ static inline int ws_get(vppx_ctx *ctx, WsSlot s, size_t count, T **out)
     *out = (T *)p;
     return rc;
 }
+
+// vppx_last_routes: the launcher of a kernel instantiation records it (printf-style name, e.g. "we12<12>"); duplicates are dropped
+void route_note(vppx_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static inline void routes_reset(vppx_ctx *ctx) { ctx->routes.clear(); }
 
 // stage ids (vppx_stage_name)
 enum {

@@ -361,6 +361,11 @@ class Engine:
         """Pieces per line of the last layer of waves in the last W/E launch of the fused layout (1: no line was cut)."""
         return int(self.lib.vppx_we_last_pieces(self.ctx.handle))
 
+    def last_routes(self):
+        """The kernel instantiations the last rSGM-bearing call launched, in launch order, each once (vppx_last_routes),
+        e.g. ["paths<4,16,exact,census,u8,dirs=ff>", "sum_lr<4,u8,8,64,spare,sw4,fast,16,fullw>"]."""
+        return _lib.last_routes(self.lib, self.ctx.handle)
+
     def fused_pixels_per_wave(self):
         """16 / 8: which fused vertical kernel the last call used (sgm_vert4_kernel / sgm_vert3_kernel); 0: none."""
         return int(self.lib.vppx_fused_pixels_per_wave(self.ctx.handle))
