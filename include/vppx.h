@@ -289,6 +289,37 @@ int vppx_occ_vpp_rsgm_guided_host(vppx_ctx *ctx, const VppxOccParams *op, const 
                                   const float *validhints, uint8_t *conf_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out,
                                   uint64_t *draws_out);
 
+/* ---- --iscale / --oscale (test.py:136-148, :247-248): the batched call on frames resized on the device ------------------
+ * With s = iscale and (h, w) = (H / s, W / s): the pair is resized as cv2.resize(INTER_LINEAR) does for 8U (DESIGN section 5,
+ * rule 1), the hints and validhints are decimated to every s-th row and column (F.interpolate nearest) and the hints divided
+ * by s (float32 true division).  Occlusion heuristic, VPP and rSGM then run at (h, w), unchanged.  When iscale != 1 and
+ * iscale / oscale != 1 the map is restored to (Ho, Wo) = floor((h, w) * iscale / oscale) (double) by F.interpolate nearest
+ * and multiplied by iscale, divided by oscale (two float32 operations); otherwise (Ho, Wo) = (h, w) and the map is returned
+ * as computed.  (Ho, Wo) need not be (H, W): H = 375, s = 2 gives 374 rows. */
+typedef struct VppxScaleParams {
+    int32_t iscale; /* >= 1, default 1: --iscale */
+    int32_t oscale; /* >= 1, default 1: --oscale */
+} VppxScaleParams;
+void vppx_scale_params_default(VppxScaleParams *p);
+/* (h, w): the shape the matcher runs at; (Ho, Wo): the shape of the returned map.  VPPX_E_INVALID_ARG for iscale < 1,
+ * oscale < 1 or an empty scaled shape. */
+int vppx_scaled_shape(int H, int W, const VppxScaleParams *sp, int *h, int *w, int *Ho, int *Wo);
+/* As vppx_occ_vpp_rsgm_guided_dev on full-size inputs left / right (uint8 [B,H,W,C]), g and validhints (float32 [B,H,W]):
+ * validhints == NULL runs unguided; op != NULL computes the mask on the way, op == NULL takes g_occ (may be NULL) as the
+ * caller's mask at (h, w).  conf_out [B,h,w], l_vpp / r_vpp [B,h,w,C] are at the scaled shape (may be NULL), disp_out is
+ * float32 [B,Ho,Wo], disp_small (may be NULL) receives the map at [B,h,w] before the restore.  Rejects sp out of range and
+ * a scaled shape that fails the frame checks with VPPX_E_INVALID_ARG before anything is launched.  With vppx_set_pipeline
+ * the resize runs in the front stage (the scaled buffers alternate between two sets). */
+int vppx_occ_vpp_rsgm_scaled_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                 const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
+                                 const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp,
+                                 uint8_t *r_vpp, float *disp_out, float *disp_small);
+/* The same for HOST arrays, as vppx_occ_vpp_rsgm_host (draws_out: draws of each frame at the scaled shape). */
+int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                  const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
+                                  const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out,
+                                  uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out, float *disp_small, uint64_t *draws_out);
+
 /* ---- frame stream: the hot path for callers that hold one host frame at a time ---------------------------------------
  * test.py:291-311 iterates a DataLoader with batch size 1 and runs :154-225 per frame on numpy arrays; the kernels want
  * batches of one lock-step round, resident.  A frame stream takes (left, right, hints[, g_occ]) host arrays one frame at a
@@ -318,6 +349,13 @@ typedef struct vppx_fstream vppx_fstream;
 int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int batch,
                         int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out);
 void vppx_fstream_destroy(vppx_fstream *fs);
+/* vppx_fstream_create with --iscale / --oscale: pushes take frames of H x W x C (and a VPPX_FS_GOCC mask at the scaled
+ * shape), each batch runs through vppx_occ_vpp_rsgm_scaled_dev; pop returns disparities of (Ho, Wo) and patterns / mask of
+ * (h, w) (vppx_scaled_shape).  sp == NULL or {1, 1} is vppx_fstream_create. */
+int vppx_fstream_create_scaled(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                               const VppxScaleParams *sp, int batch, int depth, int H, int W, int C, int flags, int copy_threads,
+                               vppx_fstream **out);
+
 /* One frame in (host arrays of the stream's H x W x C).  Returns when the frame has been copied: the arrays may be
  * reused at once.  The frame that completes a batch also queues the batch's upload, kernels and download (no waiting).
  * Fails with VPPX_E_INVALID_ARG when `depth` whole batches are waiting to be popped.  When submitting the completed batch

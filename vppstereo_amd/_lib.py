@@ -31,6 +31,8 @@ EXPORTS = [
     "vppx_enable_stage_timing", "vppx_get_stage_ms", "vppx_stage_name",
     "vppx_fstream_create", "vppx_fstream_destroy", "vppx_fstream_push", "vppx_fstream_flush", "vppx_fstream_pop", "vppx_fstream_counts",
     "vppx_occ_vpp_rsgm_guided_dev", "vppx_occ_vpp_rsgm_guided_host", "vppx_fstream_push_guided",
+    "vppx_scale_params_default", "vppx_scaled_shape", "vppx_occ_vpp_rsgm_scaled_dev", "vppx_occ_vpp_rsgm_scaled_host",
+    "vppx_fstream_create_scaled",
 ]
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 
@@ -56,6 +58,10 @@ class VppxRsgmParams(C.Structure):
 class VppxOccParams(C.Structure):
     _fields_ = [("rx", C.c_int32), ("ry", C.c_int32), ("l", C.c_double), ("g", C.c_double), ("th_conf", C.c_double),
                 ("th_filter", C.c_double)]
+
+
+class VppxScaleParams(C.Structure):
+    _fields_ = [("iscale", C.c_int32), ("oscale", C.c_int32)]
 
 
 class VppxError(Exception):
@@ -177,6 +183,15 @@ def load():
         lib.vppx_fstream_push_guided.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.vppx_fstream_flush.argtypes = [vp]
         lib.vppx_fstream_pop.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        ps = C.POINTER(VppxScaleParams)
+        lib.vppx_scale_params_default.argtypes = [ps]
+        lib.vppx_scale_params_default.restype = None
+        pi = C.POINTER(C.c_int)
+        lib.vppx_scaled_shape.argtypes = [i, i, ps, pi, pi, pi, pi]
+        lib.vppx_occ_vpp_rsgm_scaled_dev.argtypes = [vp, po, pv, pr, ps, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.vppx_occ_vpp_rsgm_scaled_host.argtypes = [vp, po, pv, pr, ps, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                      C.POINTER(C.c_uint64)]
+        lib.vppx_fstream_create_scaled.argtypes = [vp, po, pv, pr, ps, i, i, i, i, i, i, i, C.POINTER(vp)]
         p64 = C.POINTER(C.c_int64)
         lib.vppx_fstream_counts.argtypes = [vp, p64, p64, p64, p64]
         _lib = lib
@@ -320,6 +335,21 @@ def rsgm_params(**kw):
     p = VppxRsgmParams()
     load().vppx_rsgm_params_default(C.byref(p))
     return _fill(p, kw)
+
+
+def scale_params(**kw):
+    """VppxScaleParams: iscale / oscale of test.py:36-37 (defaults 1, 1)."""
+    p = VppxScaleParams()
+    load().vppx_scale_params_default(C.byref(p))
+    return _fill(p, kw)
+
+
+def scaled_shape(H, W, iscale=1, oscale=1):
+    """(h, w, Ho, Wo): the shape the matcher runs at and the shape of the returned map (vppx_scaled_shape)."""
+    sp = scale_params(iscale=int(iscale), oscale=int(oscale))
+    v = [C.c_int(0) for _ in range(4)]
+    check(load().vppx_scaled_shape(int(H), int(W), C.byref(sp), *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
 
 
 def c_contig(a, dtype):

@@ -5,6 +5,7 @@
 #include "vppx_internal.h"
 
 #include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -274,6 +275,7 @@ extern "C" void vppx_destroy(vppx_ctx *ctx)
     if (ctx->ev_front_done) (void)hipEventDestroy(ctx->ev_front_done);
     if (ctx->ev_occ_done) (void)hipEventDestroy(ctx->ev_occ_done);
     if (ctx->ev_inputs_auto) (void)hipEventDestroy(ctx->ev_inputs_auto);
+    if (ctx->ev_scaled) (void)hipEventDestroy(ctx->ev_scaled);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -1549,6 +1551,264 @@ extern "C" int vppx_occ_vpp_rsgm_guided_host(vppx_ctx *ctx, const VppxOccParams 
     if (!validhints) { vppx_set_error("vppx_occ_vpp_rsgm_guided_host: validhints is NULL"); return VPPX_E_INVALID_ARG; }
     return occ_vpp_rsgm_host(ctx, op, vp, rp, B, H, W, C, left, right, g, op ? nullptr : g_occ, validhints, conf_out, l_vpp_out, r_vpp_out,
                              disp_out, draws_out);
+}
+
+// ---------------------------------------------------------------------------------------
+// --iscale / --oscale (test.py:136-148, :247-248): resize on the way in, restore on the way out
+// ---------------------------------------------------------------------------------------
+extern "C" void vppx_scale_params_default(VppxScaleParams *p)
+{
+    if (!p) return;
+    p->iscale = 1;
+    p->oscale = 1;
+}
+
+// test.py:247: `if args.iscale != 1 and args.iscale/args.oscale != 1`
+static bool scale_restores(const VppxScaleParams &sp) { return sp.iscale != 1 && sp.iscale != sp.oscale; }
+
+extern "C" int vppx_scaled_shape(int H, int W, const VppxScaleParams *sp, int *h, int *w, int *Ho, int *Wo)
+{
+    if (!sp) { vppx_set_error("vppx_scaled_shape: sp is NULL"); return VPPX_E_INVALID_ARG; }
+    if (sp->iscale < 1 || sp->oscale < 1) {
+        vppx_set_error("iscale and oscale must be positive integers (got iscale %d, oscale %d)", sp->iscale, sp->oscale);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (H < 1 || W < 1) { vppx_set_error("vppx_scaled_shape: bad shape %dx%d", H, W); return VPPX_E_INVALID_ARG; }
+    const int hs = H / sp->iscale, ws = W / sp->iscale; // cv2.resize(img, (w // iscale, h // iscale))
+    if (hs < 1 || ws < 1) {
+        vppx_set_error("iscale %d leaves nothing of %dx%d frames", sp->iscale, H, W);
+        return VPPX_E_INVALID_ARG;
+    }
+    int ho = hs, wo = ws;
+    if (scale_restores(*sp)) { // F.interpolate(scale_factor=iscale/oscale): floor(size * factor) in double
+        const double f = (double)sp->iscale / (double)sp->oscale;
+        ho = (int)floor((double)hs * f);
+        wo = (int)floor((double)ws * f);
+        if (ho < 1 || wo < 1) {
+            vppx_set_error("iscale %d / oscale %d restores %dx%d to an empty map", sp->iscale, sp->oscale, hs, ws);
+            return VPPX_E_INVALID_ARG;
+        }
+    }
+    if (h) *h = hs;
+    if (w) *w = ws;
+    if (Ho) *Ho = ho;
+    if (Wo) *Wo = wo;
+    return 0;
+}
+
+// DESIGN section 5, rule 1: the tables OpenCV's resize (INTER_LINEAR, 8U) builds for one axis, n_in -> n_out; per output
+// {first source index, second (clamped), weight of the first, weight of the second} (weights: cvRound(x * 2048), half-even)
+static void resize_axis_table(int n_in, int n_out, int *tab)
+{
+    const double inv = (double)n_out / n_in, scale = 1.0 / inv;
+    for (int d = 0; d < n_out; d++) {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int s0 = (int)floorf(f);
+        f -= (float)s0;
+        if (s0 < 0) { s0 = 0; f = 0.f; }
+        if (s0 >= n_in - 1) { s0 = n_in - 1; f = 0.f; }
+        tab[4 * d] = s0;
+        tab[4 * d + 1] = s0 + 1 < n_in ? s0 + 1 : n_in - 1;
+        tab[4 * d + 2] = (int)(short)lrintf((1.f - f) * 2048.f);
+        tab[4 * d + 3] = (int)(short)lrintf(f * 2048.f);
+    }
+}
+
+// torch's nearest_idx (ATen UpSample.h) for scale_factor = factor, n_in -> n_out
+static void restore_axis_table(int n_in, int n_out, double factor, int *idx)
+{
+    const float sc = (float)(1.0 / factor);
+    for (int i = 0; i < n_out; i++) {
+        long long v;
+        if (n_out == n_in) v = i;
+        else if (n_out == 2 * n_in) v = i >> 1;
+        else v = (long long)floorf((float)i * sc);
+        idx[i] = (int)(v < n_in - 1 ? v : n_in - 1);
+    }
+}
+
+// Tables of one shape in WS_SCALE_TAB: ytab [h] int4, xtab [w] int4, ry [Ho], rx [Wo].  Kept per context and rebuilt when the
+// shape changes -- after both streams are idle, since a call in flight may still read the old ones.
+static int scale_tables(vppx_ctx *ctx, int H, int W, const VppxScaleParams &sp, int h, int w, int Ho, int Wo, const int **tab)
+{
+    const int key[6] = {H, W, sp.iscale, sp.oscale, Ho, Wo};
+    if (ctx->scale_tab_at && ctx->scale_tab_at == ctx->ws[WS_SCALE_TAB].p && memcmp(key, ctx->scale_key, sizeof(key)) == 0) {
+        *tab = (const int *)ctx->scale_tab_at;
+        return 0;
+    }
+    std::vector<int> host((size_t)4 * h + (size_t)4 * w + Ho + Wo);
+    resize_axis_table(H, h, host.data());
+    resize_axis_table(W, w, host.data() + 4 * h);
+    const double f = (double)sp.iscale / (double)sp.oscale;
+    restore_axis_table(h, Ho, f, host.data() + 4 * h + 4 * w);
+    restore_axis_table(w, Wo, f, host.data() + 4 * h + 4 * w + Ho);
+    VPPX_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream_front) VPPX_HIP(hipStreamSynchronize(ctx->stream_front));
+    void *d = nullptr;
+    int rc;
+    if ((rc = ws_reserve(ctx, WS_SCALE_TAB, host.size() * sizeof(int), &d))) return rc;
+    VPPX_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+    memcpy(ctx->scale_key, key, sizeof(key));
+    ctx->scale_tab_at = d;
+    *tab = (const int *)d;
+    return 0;
+}
+
+// The scaled call on device pointers: resize + decimation (scale_front_kernel), the unchanged hot path at (h, w) on the
+// library-owned scaled buffers, then the restore (scale_restore_kernel) on the launch stream.
+static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
+                       int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
+                       const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small)
+{
+    int rc;
+    if (!vp || !rp || !sp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_scaled: NULL argument"); return VPPX_E_INVALID_ARG; }
+    int h, w, Ho, Wo;
+    if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
+    if ((rc = check_frames(B, H, W, C))) return rc;
+    if ((rc = check_frames(B, h, w, C))) {
+        char msg[512];
+        snprintf(msg, sizeof(msg), "%s", vppx_last_error());
+        vppx_set_error("vppx_occ_vpp_rsgm_scaled: iscale %d turns %dx%d frames into %dx%d: %s", sp->iscale, H, W, h, w, msg);
+        return rc;
+    }
+    if ((rc = check_vpp_params(*vp))) return rc;
+    if ((rc = check_rsgm_params(*rp))) return rc;
+    if (sp->iscale == 1) { // nothing to resize, nothing to restore: the unscaled call
+        rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, op ? nullptr : g_occ, validhints, op ? conf_out : nullptr, l_vpp,
+                            r_vpp, disp_out);
+        if (rc == 0 && disp_small)
+            VPPX_HIP(hipMemcpyAsync(disp_small, disp_out, (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        return rc;
+    }
+    if ((rc = lockstep_check(ctx))) return rc; // (before anything is queued, as the hot path itself does)
+    const int *tab = nullptr;
+    if ((rc = scale_tables(ctx, H, W, *sp, h, w, Ho, Wo, &tab))) return rc;
+    const bool piped = pipeline_applies(ctx);
+    const int set = piped ? ctx->scale_parity : 0;
+    const size_t np = (size_t)B * h * w, nb = np * C;
+    u8 *ls, *rs;
+    float *gs, *vhs = nullptr;
+    if ((rc = ws_get(ctx, set ? WS_SCALE_L1 : WS_SCALE_L0, nb, &ls))) return rc;
+    if ((rc = ws_get(ctx, set ? WS_SCALE_R1 : WS_SCALE_R0, nb, &rs))) return rc;
+    if ((rc = ws_get(ctx, set ? WS_SCALE_G1 : WS_SCALE_G0, np, &gs))) return rc;
+    if (validhints && (rc = ws_get(ctx, set ? WS_SCALE_V1 : WS_SCALE_V0, np, &vhs))) return rc;
+    const bool restore = scale_restores(*sp);
+    float *dsmall = restore ? disp_small : disp_out;
+    if (restore && !dsmall && (rc = ws_get(ctx, WS_SCALE_DSMALL, np, &dsmall))) return rc;
+    ScaleFrontArgs a;
+    a.l = left; a.r = right; a.g = g; a.vh = validhints;
+    a.ls = ls; a.rs = rs; a.gs = gs; a.vhs = vhs;
+    a.ytab = (const int4 *)tab;
+    a.xtab = (const int4 *)(tab + 4 * h);
+    a.B = B; a.H = H; a.W = W; a.C = C; a.h = h; a.w = w; a.s = sp->iscale;
+    a.fs = (float)sp->iscale;
+    a.n_img_threads = 0;
+    if (piped) {
+        // the resize is the first kernel of the front stage.  It waits for what every front stage waits for (the
+        // previous call's aggregation event and this call's inputs) and writes the set of scaled buffers the previous call did NOT
+        // use; the front stage proper then starts on the resize's event.
+        if (!ctx->ev_scaled) VPPX_HIP(hipEventCreateWithFlags(&ctx->ev_scaled, hipEventDisableTiming));
+        if ((rc = front_begin(ctx))) return rc;
+        rc = scale_launch_front(ctx, a);
+        const hipError_t e = rc ? hipSuccess : hipEventRecord(ctx->ev_scaled, ctx->stream);
+        ctx->stream = ctx->main_saved;
+        ctx->front_active = false;
+        if (rc) return rc;
+        if (e != hipSuccess) { vppx_set_error("hipEventRecord failed: %s", hipGetErrorString(e)); return VPPX_E_HIP; }
+        ctx->scale_parity ^= 1;
+        ctx->inputs_ev = (void *)ctx->ev_scaled;
+    } else {
+        if (ctx->inputs_ev) {
+            VPPX_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->inputs_ev, 0));
+            ctx->inputs_ev = nullptr;
+        }
+        if ((rc = scale_launch_front(ctx, a))) return rc;
+    }
+    rc = vpp_rsgm_entry(ctx, op, vp, rp, B, h, w, C, ls, rs, gs, op ? nullptr : g_occ, vhs, op ? conf_out : nullptr, l_vpp, r_vpp, dsmall);
+    if (rc) return rc;
+    {   // vppx_last_routes: the resize first, the restore last
+        char buf[32];
+        snprintf(buf, sizeof(buf), "scale_front<%d>", C);
+        ctx->routes.insert(ctx->routes.begin(), std::string(buf));
+    }
+    if (restore) {
+        const int *ry = tab + 4 * h + 4 * w, *rx = ry + Ho;
+        if ((rc = scale_launch_restore(ctx, B, h, w, Ho, Wo, dsmall, disp_out, ry, rx, sp->iscale, sp->oscale))) return rc;
+        route_note(ctx, "scale_restore");
+    } else if (disp_small) {
+        VPPX_HIP(hipMemcpyAsync(disp_small, disp_out, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return 0;
+}
+
+extern "C" int vppx_occ_vpp_rsgm_scaled_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                            const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
+                                            const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp,
+                                            uint8_t *r_vpp, float *disp_out, float *disp_small)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx);
+    const int rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out, disp_small);
+    ctx->inputs_ev = nullptr; // one-shot, whatever happened
+    return rc;
+}
+
+extern "C" int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                             const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
+                                             const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out,
+                                             uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out, float *disp_small, uint64_t *draws_out)
+{
+    VPPX_ENTER(ctx);
+    int rc;
+    if (!vp || !rp || !sp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_scaled_host: NULL argument"); return VPPX_E_INVALID_ARG; }
+    int h, w, Ho, Wo;
+    if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
+    if ((rc = check_frames(B, H, W, C))) return rc;
+    if ((rc = check_frames(B, h, w, C))) {
+        char msg[512];
+        snprintf(msg, sizeof(msg), "%s", vppx_last_error());
+        vppx_set_error("vppx_occ_vpp_rsgm_scaled_host: iscale %d turns %dx%d frames into %dx%d: %s", sp->iscale, H, W, h, w, msg);
+        return rc;
+    }
+    const size_t nb = (size_t)B * H * W * C, np = (size_t)B * H * W;
+    const size_t nbs = (size_t)B * h * w * C, nps = (size_t)B * h * w, npo = (size_t)B * Ho * Wo;
+    void *dl, *dr, *dg, *docc = nullptr, *dconf = nullptr, *dlv = nullptr, *drv = nullptr, *dout, *dvh = nullptr, *dsm = nullptr;
+    if ((rc = upload(ctx, WS_STAGE_C, g, np * sizeof(float), &dg))) return rc;
+    if (validhints && (rc = upload(ctx, WS_HANDOFF_V, validhints, np * sizeof(float), &dvh))) return rc;
+    if (!op && g_occ && (rc = upload(ctx, WS_STAGE_D, g_occ, nps, &docc))) return rc;
+    if (op && conf_out && (rc = ws_reserve(ctx, WS_STAGE_D, nps, &dconf))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_A, left, nb, &dl))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_B, right, nb, &dr))) return rc;
+    if (l_vpp_out && (rc = ws_reserve(ctx, WS_STAGE_E, nbs, &dlv))) return rc;
+    if (r_vpp_out && (rc = ws_reserve(ctx, WS_STAGE_F, nbs, &drv))) return rc;
+    if ((rc = ws_reserve(ctx, WS_HANDOFF_H, npo * sizeof(float), &dout))) return rc;
+    if (disp_small && (rc = ws_reserve(ctx, WS_SCALE_HOST_D, nps * sizeof(float), &dsm))) return rc;
+    for (int attempt = 0;; attempt++) {
+        const unsigned serial_before = ctx->v3.serial;
+        rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, (const u8 *)dl, (const u8 *)dr, (const float *)dg, (const u8 *)docc,
+                         (const float *)dvh, (u8 *)dconf, (u8 *)dlv, (u8 *)drv, (float *)dout, (float *)dsm);
+        ctx->inputs_ev = nullptr;
+        if (rc) return rc;
+        if ((rc = download(ctx, disp_out, dout, npo * sizeof(float)))) return rc;
+        if (dsm && (rc = download(ctx, disp_small, dsm, nps * sizeof(float)))) return rc;
+        if (dconf && (rc = download(ctx, conf_out, dconf, nps))) return rc;
+        if (dlv && (rc = download(ctx, l_vpp_out, dlv, nbs))) return rc;
+        if (drv && (rc = download(ctx, r_vpp_out, drv, nbs))) return rc;
+        std::vector<unsigned long long> tot;
+        if (draws_out && vp->method == VPPX_METHOD_RND && ctx->ws[WS_FRAME_TOT].p && ctx->last_parts == 1 &&
+            ctx->ws[WS_FRAME_TOT].cap >= (size_t)B * 16) {
+            tot.resize((size_t)B * 2);
+            VPPX_HIP(hipMemcpyAsync(tot.data(), ctx->ws[WS_FRAME_TOT].p, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VPPX_HIP(hipStreamSynchronize(ctx->stream));
+        if (draws_out)
+            for (int f = 0; f < B; f++) draws_out[f] = tot.empty() ? 0 : tot[2 * f];
+        if ((rc = lockstep_check(ctx)) == 0) break;
+        const unsigned s = ctx->lockstep_last_serial;
+        const bool mine = (unsigned)(s - serial_before - 1u) < (unsigned)(ctx->v3.serial - serial_before);
+        if (!mine || attempt > 0) return rc;
+    }
+    return 0;
 }
 
 // Batches larger than one round of the lock-step kernel are run as consecutive parts of one round each ("batch quantum":

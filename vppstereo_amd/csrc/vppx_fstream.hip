@@ -27,6 +27,10 @@
 
 int vppx_lockstep_check_internal(vppx_ctx *ctx); // vppx_api.hip
 int vppx_check_hot_path_args_internal(const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H, int W, int C);
+extern "C" int vppx_occ_vpp_rsgm_scaled_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                            const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
+                                            const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp,
+                                            uint8_t *r_vpp, float *disp_out, float *disp_small);
 
 namespace {
 
@@ -57,6 +61,11 @@ struct vppx_fstream {
     VppxRsgmParams rp;
     int batch = 0, depth = 0, H = 0, W = 0, C = 0, flags = 0;
     size_t img = 0, px = 0;                 // bytes of one image, pixels of one frame
+    // --iscale / --oscale (vppx_fstream_create_scaled): the results are those of the scaled shape (h, w) -- patterns, mask, a
+    // pushed mask -- and of the restored one (Ho, Wo) -- disparities; without scaling both are the frame's own
+    bool scaled = false;
+    VppxScaleParams sp = {1, 1};
+    size_t img_s = 0, px_s = 0, px_o = 0;
     size_t in_frame = 0, out_frame = 0;     // ring bytes per frame
     size_t o_left = 0, o_right = 0, o_hint = 0, o_gocc = 0, o_valid = 0;          // offsets inside a slot's input area (planes of `batch` frames)
     size_t o_disp = 0, o_lv = 0, o_rv = 0, o_conf = 0, o_draws = 0;  // offsets inside a slot's output area
@@ -104,8 +113,8 @@ static int fs_free(vppx_fstream *fs)
 
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
-                                   int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
+static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
+                     int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
 {
     if (!ctx) { vppx_set_error("context is NULL (vppx_create failed? there is no CPU fallback)"); return VPPX_E_NO_DEVICE; }
     if (!out || !vp || !rp) { vppx_set_error("vppx_fstream_create: NULL argument"); return VPPX_E_INVALID_ARG; }
@@ -120,8 +129,17 @@ extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const
         vppx_set_error("vppx_fstream_create: the context must launch on a stream of its own, without sub-streams, graph mode or stage timing");
         return VPPX_E_INVALID_ARG;
     }
+    int hs = H, ws = W, Ho = H, Wo = W;
+    if (sp) {
+        const int rc = vppx_scaled_shape(H, W, sp, &hs, &ws, &Ho, &Wo);
+        if (rc) return rc;
+    }
     {
         const int rc = vppx_check_hot_path_args_internal(vp, rp, batch, H, W, C); // (same codes and messages as the hot path itself)
+        if (rc) return rc;
+    }
+    if (sp) {
+        const int rc = vppx_check_hot_path_args_internal(vp, rp, batch, hs, ws, C);
         if (rc) return rc;
     }
     DevGuard g(ctx->device);
@@ -137,19 +155,24 @@ extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const
     fs->batch = batch; fs->depth = depth; fs->H = H; fs->W = W; fs->C = C; fs->flags = flags;
     fs->px = (size_t)H * W;
     fs->img = fs->px * C;
+    fs->scaled = sp != nullptr;
+    if (sp) fs->sp = *sp;
+    fs->px_s = (size_t)hs * ws;
+    fs->img_s = fs->px_s * C;
+    fs->px_o = (size_t)Ho * Wo;
     // planes of `batch` frames each, so that a batch goes up / comes down in one copy per plane and the hot path sees [B,H,W,C]
     size_t o = 0;
     fs->o_left = o;  o += up256(fs->img * batch);
     fs->o_right = o; o += up256(fs->img * batch);
     fs->o_hint = o;  o += up256(fs->px * 4 * batch);
-    fs->o_gocc = o;  if (flags & VPPX_FS_GOCC) o += up256(fs->px * batch);
+    fs->o_gocc = o;  if (flags & VPPX_FS_GOCC) o += up256(fs->px_s * batch);
     fs->o_valid = o; if (flags & VPPX_FS_GUIDED) o += up256(fs->px * 4 * batch);
     fs->in_bytes = o;
     o = 0;
-    fs->o_disp = o;  o += up256(fs->px * 4 * batch);
-    fs->o_lv = o;    if (flags & VPPX_FS_PATTERNS) o += up256(fs->img * batch);
-    fs->o_rv = o;    if (flags & VPPX_FS_PATTERNS) o += up256(fs->img * batch);
-    fs->o_conf = o;  if (flags & VPPX_FS_MASK) o += up256(fs->px * batch);
+    fs->o_disp = o;  o += up256(fs->px_o * 4 * batch);
+    fs->o_lv = o;    if (flags & VPPX_FS_PATTERNS) o += up256(fs->img_s * batch);
+    fs->o_rv = o;    if (flags & VPPX_FS_PATTERNS) o += up256(fs->img_s * batch);
+    fs->o_conf = o;  if (flags & VPPX_FS_MASK) o += up256(fs->px_s * batch);
     fs->o_draws = o; o += up256((size_t)8 * batch);
     fs->out_bytes = o;
     fs->slots.resize(depth);
@@ -188,6 +211,20 @@ extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const
     ctx->have_agg_done = false;
     *out = fs;
     return 0;
+}
+
+extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                   int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
+{
+    return fs_create(ctx, op, vp, rp, nullptr, batch, depth, H, W, C, flags, copy_threads, out);
+}
+
+extern "C" int vppx_fstream_create_scaled(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                          const VppxScaleParams *sp, int batch, int depth, int H, int W, int C, int flags, int copy_threads,
+                                          vppx_fstream **out)
+{
+    const bool unscaled = !sp || (sp->iscale == 1 && sp->oscale == 1);
+    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, batch, depth, H, W, C, flags, copy_threads, out);
 }
 
 extern "C" void vppx_fstream_destroy(vppx_fstream *fs) { fs_free(fs); }
@@ -234,12 +271,12 @@ static int fs_copy_out(vppx_fstream *fs, Slot &s, bool behind_last_aggregation)
         a.n16[a.n] = (bytes + 15) / 16;
         a.n++;
     };
-    seg(fs->o_disp, fs->px * 4 * nb);
+    seg(fs->o_disp, fs->px_o * 4 * nb);
     if (fs->flags & VPPX_FS_PATTERNS) {
-        seg(fs->o_lv, fs->img * nb);
-        seg(fs->o_rv, fs->img * nb);
+        seg(fs->o_lv, fs->img_s * nb);
+        seg(fs->o_rv, fs->img_s * nb);
     }
-    if (fs->flags & VPPX_FS_MASK) seg(fs->o_conf, fs->px * nb);
+    if (fs->flags & VPPX_FS_MASK) seg(fs->o_conf, fs->px_s * nb);
     if (s.out_method_rnd) seg(fs->o_draws, (size_t)8 * nb);
     fs_copy_out_kernel<<<FS_COPY_WGS, 256, 0, fs->s_out>>>(a);
     VPPX_HIP(hipGetLastError());
@@ -269,7 +306,7 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_right, s.h_in + fs->o_right, fs->img * nb, hipMemcpyHostToDevice, fs->s_in));
         VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_hint, s.h_in + fs->o_hint, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
         if (fs->flags & VPPX_FS_GOCC)
-            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gocc, s.h_in + fs->o_gocc, fs->px * nb, hipMemcpyHostToDevice, fs->s_in));
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gocc, s.h_in + fs->o_gocc, fs->px_s * nb, hipMemcpyHostToDevice, fs->s_in));
         if (fs->flags & VPPX_FS_GUIDED)
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_valid, s.h_in + fs->o_valid, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
         VPPX_HIP(hipEventRecord(s.ev_in, fs->s_in));
@@ -287,7 +324,14 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         rc = vppx_inputs_ready_event(ctx, (void *)s.ev_in);
         if (rc) return rc;
         ctx->draws_dst = (vp.method == VPPX_METHOD_RND) ? (unsigned long long *)(s.d_out + fs->o_draws) : nullptr;
-        if (fs->flags & VPPX_FS_GUIDED) // (never the lock-step kernel: no re-run)
+        if (fs->scaled)
+            rc = vppx_occ_vpp_rsgm_scaled_dev(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, &fs->sp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left,
+                                              s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
+                                              (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
+                                              (fs->flags & VPPX_FS_GUIDED) ? (const float *)(s.d_in + fs->o_valid) : nullptr,
+                                              (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp),
+                                              nullptr);
+        else if (fs->flags & VPPX_FS_GUIDED) // (never the lock-step kernel: no re-run)
             rc = vppx_occ_vpp_rsgm_guided_dev(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left,
                                               s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
                                               (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr, (const float *)(s.d_in + fs->o_valid),
@@ -369,7 +413,7 @@ static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, 
     CopyJob jobs[5] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
                        {s.h_in + fs->o_right + fs->img * i, right, fs->img},
                        {s.h_in + fs->o_hint + fs->px * 4 * i, hints, fs->px * 4},
-                       {g_occ ? s.h_in + fs->o_gocc + fs->px * i : nullptr, g_occ, fs->px},
+                       {g_occ ? s.h_in + fs->o_gocc + fs->px_s * i : nullptr, g_occ, fs->px_s},
                        {validhints ? s.h_in + fs->o_valid + fs->px * 4 * i : nullptr, validhints, fs->px * 4}};
     fs->pool->copy(jobs, 5);
     fs->fill_count++;
@@ -477,10 +521,10 @@ extern "C" int vppx_fstream_pop(vppx_fstream *fs, float *disp_out, uint8_t *l_vp
         if (rc) return rc;
     }
     const int i = fs->pop_idx;
-    CopyJob jobs[4] = {{disp_out, s.h_out + fs->o_disp + fs->px * 4 * i, fs->px * 4},
-                       {l_vpp_out, s.h_out + fs->o_lv + fs->img * i, fs->img},
-                       {r_vpp_out, s.h_out + fs->o_rv + fs->img * i, fs->img},
-                       {conf_out, s.h_out + fs->o_conf + fs->px * i, fs->px}};
+    CopyJob jobs[4] = {{disp_out, s.h_out + fs->o_disp + fs->px_o * 4 * i, fs->px_o * 4},
+                       {l_vpp_out, s.h_out + fs->o_lv + fs->img_s * i, fs->img_s},
+                       {r_vpp_out, s.h_out + fs->o_rv + fs->img_s * i, fs->img_s},
+                       {conf_out, s.h_out + fs->o_conf + fs->px_s * i, fs->px_s}};
     fs->pool->copy(jobs, 4);
     if (draws_out) *draws_out = fs->vp.method == VPPX_METHOD_RND ? ((const uint64_t *)(s.h_out + fs->o_draws))[i] : 0;
     *got = 1;

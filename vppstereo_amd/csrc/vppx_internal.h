@@ -121,6 +121,17 @@ enum WsSlot {
     WS_PNG_RAW,      // concatenated IDAT payloads of a batch of PNG files (the zlib streams)
     WS_PNG_OFFS,
     WS_PNG_STATUS,
+    WS_SCALE_L0,     // --iscale: the scaled pair, hints and validhints of a scaled call (two sets: pipelined calls alternate)
+    WS_SCALE_R0,
+    WS_SCALE_G0,
+    WS_SCALE_V0,
+    WS_SCALE_L1,
+    WS_SCALE_R1,
+    WS_SCALE_G1,
+    WS_SCALE_V1,
+    WS_SCALE_DSMALL, // the disparities at the scaled shape, when the caller does not want them (the restore kernel reads them)
+    WS_SCALE_TAB,    // index / weight tables of the resize and the restore (scale_tables)
+    WS_SCALE_HOST_D, // vppx_occ_vpp_rsgm_scaled_host: device copy of disp_small
     WS_NUM
 };
 
@@ -280,6 +291,12 @@ struct vppx_ctx {
     int stage_id[VPPX_MAX_STAGES];
     size_t total_bytes = 0;
     std::vector<long long> png_offs_host; // kept alive for the asynchronous upload
+    // --iscale / --oscale (vppx_occ_vpp_rsgm_scaled_*): shape the tables in WS_SCALE_TAB were computed for, and which set of
+    // scaled buffers the next pipelined scaled call writes
+    int scale_key[6] = {0, 0, 0, 0, 0, 0};
+    const void *scale_tab_at = nullptr;
+    int scale_parity = 0;
+    hipEvent_t ev_scaled = nullptr;
 };
 
 int ws_reserve(vppx_ctx *ctx, WsSlot s, size_t bytes, void **out);
@@ -405,6 +422,22 @@ int handoff_pfm_decode(vppx_ctx *ctx, const u8 *raw, int H, int W, int channels,
 // png_kernels.hip
 int handoff_png_decode(vppx_ctx *ctx, int n_files, const u8 *blob_dev, const long long *offs_dev, int H, int W, int C, u8 *zcat,
                        const long long *zoffs_dev, float scale, float *disp, u8 *valid, u8 *out_u8, int *status_dev);
+
+// scale_kernels.hip (--iscale / --oscale, DESIGN section 5 rule 1)
+struct ScaleFrontArgs {
+    const u8 *l, *r;        // [B, H, W, C]
+    const float *g, *vh;    // [B, H, W]; vh may be null
+    u8 *ls, *rs;            // [B, h, w, C]
+    float *gs, *vhs;        // [B, h, w]
+    const int4 *ytab;       // [h]: {first row, second row (clamped), b0, b1}
+    const int4 *xtab;       // [w]: {first column, second column (clamped), a0, a1}
+    int B, H, W, C, h, w, s;
+    float fs;               // (float)s
+    long long n_img_threads; // (set by the launcher)
+};
+int scale_launch_front(vppx_ctx *ctx, const ScaleFrontArgs &a);
+int scale_launch_restore(vppx_ctx *ctx, int B, int h, int w, int Ho, int Wo, const float *src, float *out, const int *ry,
+                         const int *rx, int iscale, int oscale);
 
 // occ_kernels (in vpp_kernels.hip)
 int occ_launch(vppx_ctx *ctx, int B, int H, int W, const float *hints, int rx, int ry, double l, double g,

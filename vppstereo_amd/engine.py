@@ -102,7 +102,7 @@ class Engine:
         return out
 
     def vpp_rsgm(self, left, right, hints, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
-                 rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None):
+                 rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None, iscale=1, oscale=1, disp_small=None):
         """The whole hot path for a batch: one call, no host round trips, no synchronisation.
 
         g_occ: None, a uint8 [B,H,W] mask tensor, or -- test.py:154 with --maskocc in the same call --
@@ -112,11 +112,18 @@ class Engine:
         matters with `set_pipeline(True)`: the front stage then waits for that event instead of for everything queued on
         the current stream, and can overlap the previous call's tail (it then covers `validhints` too).
         validhints: float32 [B,H,W] or None.  Given, the call is --guided (test.py:207-223): `hints` also re-weight the
-        matching costs wherever validhints > 0 (vppx_occ_vpp_rsgm_guided_dev), with either form of g_occ."""
+        matching costs wherever validhints > 0 (vppx_occ_vpp_rsgm_guided_dev), with either form of g_occ.
+        iscale / oscale: --iscale / --oscale (test.py:136-148, :247-248, vppx_occ_vpp_rsgm_scaled_dev).  The inputs keep their
+        full shape [B,H,W(,C)]; the call runs at (h, w) = (H // iscale, W // iscale), so g_occ, occ_out, l_vpp and r_vpp are of
+        that shape, and `out` is [B,Ho,Wo] (pipeline.scaled_shape).  disp_small: float32 [B,h,w] or None, the map before the
+        restore.  With the defaults the call is exactly the unscaled one."""
         torch = self.torch
         heuristic = isinstance(g_occ, (str, dict))
         if isinstance(g_occ, str) and g_occ != "occlusion_heuristic":
             raise ValueError("g_occ: expected a mask tensor, None, 'occlusion_heuristic' or a dict of its parameters")
+        if int(iscale) != 1 or int(oscale) != 1 or disp_small is not None:
+            return self._vpp_rsgm_scaled(left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out,
+                                         inputs_ready, validhints, int(iscale), int(oscale), disp_small)
         B, H, W, Cc = self._chk_pair(left, right, hints, None if heuristic else g_occ)
         if out is None:
             out = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
@@ -151,6 +158,45 @@ class Engine:
             _lib.check(self.lib.vppx_vpp_rsgm_dev(self.ctx.handle, C.byref(vp), C.byref(rp), B, H, W, Cc, _ptr(left),
                                                   _ptr(right), _ptr(hints), _ptr(g_occ), _ptr(l_vpp), _ptr(r_vpp),
                                                   _ptr(out)))
+        return out
+
+    def _vpp_rsgm_scaled(self, left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
+                         validhints, iscale, oscale, disp_small):
+        torch = self.torch
+        self._chk(left, torch.uint8, 4, "left")
+        B, H, W, Cc = left.shape
+        if Cc not in (1, 3):
+            raise ValueError("left: channels must be 1 or 3")
+        self._chk(right, torch.uint8, 4, "right", left.shape)
+        self._chk(hints, torch.float32, 3, "hints", (B, H, W))
+        sp = _lib.scale_params(iscale=iscale, oscale=oscale)
+        h, w, Ho, Wo = _lib.scaled_shape(H, W, iscale, oscale)
+        if g_occ is not None and not heuristic:
+            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
+        if validhints is not None:
+            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
+        if out is None:
+            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
+        if disp_small is not None:
+            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
+        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
+            if t is not None:
+                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
+        if occ_out is not None:
+            if not heuristic:
+                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
+            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
+        self._bind_stream()
+        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
+        rp = _lib.rsgm_params(**(rsgm_kw or {}))
+        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
+        if inputs_ready is not None:
+            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        _lib.check(self.lib.vppx_occ_vpp_rsgm_scaled_dev(self.ctx.handle, C.byref(op) if heuristic else None, C.byref(vp), C.byref(rp),
+                                                         C.byref(sp), B, H, W, Cc, _ptr(left), _ptr(right), _ptr(hints),
+                                                         None if heuristic else _ptr(g_occ), _ptr(validhints), _ptr(occ_out),
+                                                         _ptr(l_vpp), _ptr(r_vpp), _ptr(out), _ptr(disp_small)))
         return out
 
     def occlusion_heuristic(self, hints, rx=9, ry=7, l=2, g=0.4375, th_conf=1, th_filter=0.1, out=None):

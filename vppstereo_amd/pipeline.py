@@ -4,6 +4,7 @@
     disp = run_frame(left, right, hints, maskocc=True)                      # test.py --vpp --maskocc --stereomodel rsgm
     disp = run_frame(left, right, hints, validhints=valid)                  # test.py --vpp --guided --stereomodel rsgm
     disp, lc, rc, conf = run_frame(..., return_patterns=True)
+    disp = run_frame(left, right, hints, maskocc=True, iscale=2)            # test.py --iscale 2 (resize + restore on the device)
 
 The pair, the hints and the mask cross PCIe once, the mask never leaves the device
 between the occlusion heuristic and the scan, and only the disparity map comes back unless the patterned pair is asked for.
@@ -31,14 +32,28 @@ def _vpp_params(vk, method, dmin, dmax):
     return p
 
 
+def scaled_shape(H, W, iscale=1, oscale=1):
+    """--iscale / --oscale (test.py:142-148, :247-248): (h, w, Ho, Wo), the shape the matcher runs at, (H // iscale, W // iscale),
+    and the shape of the returned map -- floor((h, w) * iscale / oscale) when iscale != 1 and iscale / oscale != 1, else (h, w)."""
+    return _lib.scaled_shape(H, W, iscale, oscale)
+
+
+def _scaled_hints(gt, iscale):
+    """The hints vpp() sees at iscale (test.py:147): every iscale-th row and column, divided by iscale (float32)."""
+    h, w = gt.shape[0] // iscale, gt.shape[1] // iscale
+    return gt[::iscale, ::iscale][:h, :w] / np.float32(iscale)
+
+
 def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw=None, rsgm_kw=None, return_patterns=False,
-              validhints=None):
+              validhints=None, iscale=1, oscale=1):
     """left, right: uint8 [H,W,3] or [H,W]; hints: float [H,W] (0 = none).  maskocc: compute g_occ with the occlusion heuristic
     (test.py:154) -- else `g_occ` (uint8 [H,W] or None) is used as given.  vpp_kw: keywords of `vpp_standalone.vpp`
     (wsize, blending, c_occ, ...); rsgm_kw: keywords of `rsgm.compute_rsgm` (dmax, p1, ...).  validhints: float [H,W] or None;
     given, the call is --guided (test.py:207-223): `hints` also re-weight the matching costs of compute_rsgm wherever
     validhints > 0.  Returns the float32 disparity map, or (disparity, left_vpp, right_vpp, conf_map or None) with
-    return_patterns."""
+    return_patterns.  iscale / oscale: --iscale / --oscale (test.py:136-148, :247-248): the full-size frame is resized on the
+    device, the call runs at (h, w) = (H // iscale, W // iscale) -- g_occ and the returned patterns and mask have that shape --
+    and the map comes back at (Ho, Wo) (`scaled_shape`)."""
     vk = dict(vpp_kw or {})
     method = vk.pop("method", "rnd")
     assert method in ["rnd", "maxDistance"]
@@ -52,9 +67,12 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
         vh = np.ascontiguousarray(np.asarray(validhints, dtype=np.float32))
         if vh.shape != gt.shape:
             raise ValueError("validhints must have the shape of hints")
-    h, w = gt.shape
+    iscale, oscale = int(iscale), int(oscale)
+    scaled = (iscale, oscale) != (1, 1)
+    H, W = gt.shape
+    h, w, Ho, Wo = scaled_shape(H, W, iscale, oscale) if scaled else (H, W, H, W)
     ch = 1 if left.ndim == 2 else left.shape[2]
-    dmin, dmax = hint_range(gt)
+    dmin, dmax = hint_range(_scaled_hints(gt, iscale) if iscale != 1 else gt)
     no_hints = dmin is None
     if no_hints:
         dmin, dmax = 0.0, 0.0     # no hints: the scan leaves the pair as it is (vpp_standalone.py:407)
@@ -71,18 +89,26 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
     occ = None
     if not maskocc and g_occ is not None:
         occ = np.ascontiguousarray(np.asarray(g_occ) != 0, np.uint8)
+        if occ.shape != (h, w):
+            raise ValueError(f"g_occ: expected shape {(h, w)}, got {occ.shape}")
     lib, ctx = _lib.load(), _lib.default_context()
     seed, consumed = C.c_uint32(), C.c_uint64()
     _lib.check(lib.vppx_rand_state(ctx.handle, C.byref(seed), C.byref(consumed)))   # the stream vpp() and the scans share
     p.seed, p.rand_offset = seed.value, consumed.value
-    disp = np.empty((h, w), np.float32)
+    disp = np.empty((Ho, Wo), np.float32)
     lc = rc = conf = None
     if return_patterns:
         lc, rc = np.empty((h, w, ch), np.uint8), np.empty((h, w, ch), np.uint8)
         conf = np.empty((h, w), np.uint8) if maskocc else None
     draws = (C.c_uint64 * 1)()
     try:
-        if vh is not None:
+        if scaled:
+            sp = _lib.scale_params(iscale=iscale, oscale=oscale)
+            _lib.check(lib.vppx_occ_vpp_rsgm_scaled_host(ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp),
+                                                         C.byref(sp), 1, H, W, ch, _lib.np_ptr(left), _lib.np_ptr(right), _lib.np_ptr(gt),
+                                                         _lib.np_ptr(occ), _lib.np_ptr(vh), _lib.np_ptr(conf), _lib.np_ptr(lc),
+                                                         _lib.np_ptr(rc), _lib.np_ptr(disp), None, draws))
+        elif vh is not None:
             _lib.check(lib.vppx_occ_vpp_rsgm_guided_host(ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp), 1,
                                                          h, w, ch, _lib.np_ptr(left), _lib.np_ptr(right), _lib.np_ptr(gt), _lib.np_ptr(occ),
                                                          _lib.np_ptr(vh), _lib.np_ptr(conf), _lib.np_ptr(lc), _lib.np_ptr(rc),
@@ -118,10 +144,13 @@ class FrameStream:
     Results: the float32 disparity map, or with return_patterns (disparity, left_vpp, right_vpp, conf_map or None); each a fresh
     array.  `draws` of the last popped frame (rand() calls it consumed) is in `last_draws`.
     guided=True: --guided (test.py:207-223); every push brings the frame's validhints, and the frame equals
-    `run_frame(..., validhints=...)` with seed + f."""
+    `run_frame(..., validhints=...)` with seed + f.
+    iscale / oscale: --iscale / --oscale (test.py:136-148, :247-248): pushes take full-size frames (and, with_g_occ, masks of the
+    scaled shape); disparities come back at (Ho, Wo), patterns and mask at (h, w) (`scaled_shape`), and frame f equals
+    `run_frame(..., iscale=, oscale=)` with seed + f.  batch=None then takes the batch quantum of the scaled shape."""
 
     def __init__(self, height, width, channels=3, batch=None, depth=3, seed=1, maskocc=False, with_g_occ=False, occ_kw=None,
-                 vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1, guided=False):
+                 vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1, guided=False, iscale=1, oscale=1):
         vk = dict(vpp_kw or {})
         method = vk.pop("method", "rnd")
         assert method in ["rnd", "maxDistance"]
@@ -136,10 +165,21 @@ class FrameStream:
         op = _lib.occ_params(**(occ_kw or {})) if maskocc else None
         self.h, self.w, self.ch = int(height), int(width), int(channels)
         self._shape = (self.h, self.w) if self.ch == 1 else (self.h, self.w, self.ch)
+        self.iscale, self.oscale = int(iscale), int(oscale)
+        self._scaled = (self.iscale, self.oscale) != (1, 1)
         self._lib = _lib.load()
+        if self._scaled:
+            sp = _lib.scale_params(iscale=self.iscale, oscale=self.oscale)
+            try:
+                self.hs, self.ws, self.ho, self.wo = scaled_shape(self.h, self.w, self.iscale, self.oscale)
+            except _lib.VppxError as e:
+                raise Exception(str(e)) from e
+        else:
+            self.hs, self.ws, self.ho, self.wo = self.h, self.w, self.h, self.w
+        self._shape_s = (self.hs, self.ws) if self.ch == 1 else (self.hs, self.ws, self.ch)
         self._ctx = _lib.Context(device)
         if batch is None:
-            batch = int(self._lib.vppx_batch_quantum(self._ctx.handle, self.h, self.w, int(rp.dmax))) or 16
+            batch = int(self._lib.vppx_batch_quantum(self._ctx.handle, self.hs, self.ws, int(rp.dmax))) or 16
         self.batch, self.depth = int(batch), int(depth)
         self._patterns, self._mask, self._gocc = bool(return_patterns), bool(maskocc and return_patterns), bool(with_g_occ)
         self._guided = bool(guided)
@@ -147,8 +187,13 @@ class FrameStream:
         flags |= _lib.FS_GUIDED if self._guided else 0
         self._h = C.c_void_p()
         try:
-            _lib.check(self._lib.vppx_fstream_create(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp),
-                                                     self.batch, self.depth, self.h, self.w, self.ch, flags, int(copy_threads), C.byref(self._h)))
+            if self._scaled:
+                _lib.check(self._lib.vppx_fstream_create_scaled(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p),
+                                                                C.byref(rp), C.byref(sp), self.batch, self.depth, self.h, self.w, self.ch,
+                                                                flags, int(copy_threads), C.byref(self._h)))
+            else:
+                _lib.check(self._lib.vppx_fstream_create(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p), C.byref(rp),
+                                                         self.batch, self.depth, self.h, self.w, self.ch, flags, int(copy_threads), C.byref(self._h)))
         except _lib.VppxError as e:
             self._ctx.close()
             raise Exception(str(e)) from e
@@ -197,8 +242,8 @@ class FrameStream:
             if g_occ is None:
                 raise ValueError("the stream was created with with_g_occ=True: every push brings a mask")
             occ = np.ascontiguousarray(np.asarray(g_occ) != 0, np.uint8)
-            if occ.shape != (self.h, self.w):
-                raise ValueError("g_occ: expected shape (H, W)")
+            if occ.shape != (self.hs, self.ws):
+                raise ValueError(f"g_occ: expected shape {(self.hs, self.ws)}")
         elif g_occ is not None:
             raise ValueError("g_occ given but the stream was created without with_g_occ=True")
         vh = None
@@ -247,12 +292,12 @@ class FrameStream:
 
     # ---- one frame out ----
     def _pop_native(self):
-        disp = np.empty((self.h, self.w), np.float32)
+        disp = np.empty((self.ho, self.wo), np.float32)
         lc = rc = conf = None
         if self._patterns:
-            lc, rc = np.empty(self._shape, np.uint8), np.empty(self._shape, np.uint8)
+            lc, rc = np.empty(self._shape_s, np.uint8), np.empty(self._shape_s, np.uint8)
         if self._mask:
-            conf = np.empty((self.h, self.w), np.uint8)
+            conf = np.empty((self.hs, self.ws), np.uint8)
         draws, got = C.c_uint64(0), C.c_int(0)
         try:
             _lib.check(self._lib.vppx_fstream_pop(self._h, disp.ctypes.data, lc.ctypes.data if lc is not None else None,
