@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the VPP + rSGM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Metric (BASELINE.json): Mdisparities/s = frames * H * W * D / wall-seconds / 1e6 for
@@ -14,7 +14,10 @@ per GPU); the only exchange is the final gather of the disparity maps to rank 0,
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts N rank processes itself, before
 this process has made any GPU call, and exits with the first non-zero rank status.
 
-One JSON line is printed by rank 0.  Extra objects:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+headline (metric, value, unit, ms_per_step, ...) with its configuration and per-rank step times.  Everything else takes runs of
+its own and comes with `--full` only: the sustained and unpipelined loops, the run without the mask, stage times and the
+objects below, the other BASELINE configurations, the batch sweep and the frame stream.  Extra objects (`--full`):
   roofline     -- dominant kernel (the fused vertical aggregation kernel, 6 of the 8 paths; the 8-path kernel
                   when that layout runs): algorithmic bytes per launch (SURVEY 8d's 10 B/cell for the 8-path
                   aggregation, pro rata for the paths the launch carries) / average launch
@@ -60,9 +63,15 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU per step")
-    ap.add_argument("--cpu-frames", type=int, default=4, help="frames timed for the 1-thread CPU baseline (0 = skip both CPU legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline line: sustained and unpipelined loops, the dominant kernel's roofline "
+                         "and stage times, the run without the mask, B=1 latency, the CPU baselines, the other BASELINE "
+                         "configurations, the batch sweep and the frame stream.  Without it a run sets up, warms up, times the "
+                         "steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--cpu-frames", type=int, default=4,
+                    help="--full: frames timed for the 1-thread CPU baseline (0 = skip both CPU legs)")
     ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-cpu-parallel", action="store_true", help="skip the all-cores CPU leg")
+    ap.add_argument("--no-cpu-parallel", action="store_true", help="--full: skip the all-cores CPU leg")
     ap.add_argument("--no-occ", action="store_true", help="headline run without the occlusion mask (g_occ = None)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend for N > 1 (default nccl = RCCL; gloo when the "
                                                     "ranks have to share a GPU: dry runs)")
@@ -77,10 +86,10 @@ def parse(argv=None):
                     help="uniform-random u8 images and hint values (the variant SURVEY section 6 timed on the CPU) "
                          "instead of the textured scenes; GPU timing only")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the bounded runs of the other BASELINE configurations (cfg 3 KITTI B=32, cfg 5 1536x2048x256 B=8)")
+                    help="--full: skip the bounded runs of the other BASELINE configurations (cfg 3 KITTI B=32, cfg 5 1536x2048x256 B=8)")
     ap.add_argument("--sustained-steps", type=int, default=500,
-                    help="further steps timed AFTER the K timed ones (power steady state of the chip; 0 = skip); reported as "
-                         "ms_per_step_sustained, never as value")
+                    help="--full: further steps timed AFTER the K timed ones (power steady state of the chip; 0 = skip); "
+                         "reported as ms_per_step_sustained, never as value")
     ap.add_argument("--spawn-check", action="store_true",
                     help="rank processes only form the process group (gloo, CPU) and report the frame plan: launcher self-test")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -104,6 +113,21 @@ def frame_plan(batch, rank, world, base_seed=1):
     n_total = batch * world
     lo, hi = vdist.shard_range(n_total, rank, world)
     return dict(n_total=n_total, lo=lo, hi=hi, seed0=vdist.frame_seed(base_seed, lo))
+
+
+def make_inputs(n, frame0, procs):
+    """The step's synthetic scenes: the left, right and hints arrays of synth.make_batch(n, H, W, D, P_HINTS, seed=1234,
+    frame0=frame0), bit for bit.  A frame is ~0.4 s of host numpy at 540x960, so the frames are made on up to `procs` fresh
+    processes (spawned, not forked: the caller has opened the GPU; a frame depends on its seed and index only)."""
+    import numpy as np
+    import synth
+    if procs <= 1 or n <= 1:
+        return synth.make_batch(n, H, W, D, P_HINTS, seed=1234, frame0=frame0)
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(min(procs, n), mp_context=mp.get_context("spawn")) as ex:
+        frames = list(ex.map(synth.make_frame, [H] * n, [W] * n, [D] * n, [P_HINTS] * n, [1234] * n, range(frame0, frame0 + n)))
+    return {k: np.stack([f[k] for f in frames]) for k in ("left", "right", "hints")}
 
 
 def _free_port():
@@ -428,12 +452,14 @@ def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
     os.makedirs(dirname, exist_ok=True)
     header = 128   # an .npy header of a 1-D or 3-D array
     keep = (budget // len(arrays) - header) // 4
+    picks = {}   # the positions depend on the number of elements only: drawn once per size
     for name, a in arrays.items():
         a = np.ascontiguousarray(a, dtype=np.float32)
         what = "x".join(map(str, a.shape))
         if a.size > keep:
-            pos = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))
-            a = a.reshape(-1)[pos]
+            if a.size not in picks:
+                picks[a.size] = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[picks[a.size]]
             what = f"{keep} sampled elements of {what}"
         np.save(os.path.join(dirname, name + ".npy"), a)
         print(f"[bench] wrote {os.path.join(dirname, name + '.npy')}: {what}", file=sys.stderr)
@@ -566,7 +592,8 @@ def run_rank(args):
     B = args.batch
     plan = frame_plan(B, rank, world)
     n_total, lo, seed0 = plan["n_total"], plan["lo"], plan["seed0"]
-    # synthetic frames: every frame of the batch is its own scene (generation is host-side numpy, ~0.4 s per frame)
+    # synthetic frames: every frame of the batch is its own scene (generation is host-side numpy, ~0.4 s per frame: the
+    # processes this rank may use share it; ranks of one node split the cores)
     n_unique = B
     if args.uniform_random:
         trip = [synth.uniform_random_pair(H, W, D, P_HINTS, seed=lo + i) for i in range(n_unique)]
@@ -574,7 +601,8 @@ def run_rank(args):
                 "hints": np.stack([t[2] for t in trip])}
         args.cpu_frames = 0  # the CPU leg regenerates the textured frames: not comparable
     else:
-        base = synth.make_batch(n_unique, H, W, D, P_HINTS, seed=1234, frame0=lo)
+        local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
+        base = make_inputs(n_unique, lo, _usable_cores()[0] // max(1, local_world))
     idx = [i % n_unique for i in range(B)]
     left = torch.from_numpy(np.ascontiguousarray(base["left"][idx])).to(dev)
     right = torch.from_numpy(np.ascontiguousarray(base["right"][idx])).to(dev)
@@ -696,19 +724,19 @@ def run_rank(args):
         dt = max(float(x[0].item()) for x in allt)
     if args.graph:
         assert eng.graph_replays() > 0, "--graph was given but no call was served by a graph replay"
-    # power steady state: the timed region is a fraction of a second on a chip that clocks by its power budget; the same loop
-    # for `--sustained-steps` further steps (every rank: `timed` has barriers), reported next to the K-step figure
+    # --full: power steady state: the timed region is a fraction of a second on a chip that clocks by its power budget; the
+    # same loop for `--sustained-steps` further steps (every rank: `timed` has barriers), reported next to the K-step figure
     ms_sustained = None
-    if args.sustained_steps > 0:
+    if args.full and args.sustained_steps > 0:
         ms_sustained = timed(args.sustained_steps, step) / args.sustained_steps * 1e3
         if world > 1:
             t = torch.tensor([ms_sustained], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             ms_sustained = float(t.item())
         eng.status()
-    # the same steps with the cross-step overlap off (every rank: `timed` has barriers)
+    # --full: the same steps with the cross-step overlap off (every rank: `timed` has barriers)
     ms_unpipelined = None
-    if not (args.no_pipeline or args.graph):
+    if args.full and not (args.no_pipeline or args.graph):
         eng.set_pipeline(False)
         n_unp = max(2, min(5, args.steps))
         step()
@@ -724,8 +752,8 @@ def run_rank(args):
     ms_per_step = dt / args.steps * 1e3
     value = n_total * H * W * D * args.steps / dt / 1e6
 
-    result = None
-    if rank == 0:
+    def full_legs(result):
+        """--full, rank 0 (no collectives from here on): the figures that take runs of their own, added to `result`."""
         # ---- dominant kernel, measured live with hipEvents on its own launch stream ----------
         # average over the launches made INSIDE the timed region (event pairs on the launch stream, ring of 64)
         agg_ms, agg_n = eng.agg_kernel_ms(args.steps)
@@ -830,35 +858,9 @@ def run_rank(args):
                        we_name: kernel_row(we_name, we_ms_in_step if we_n else we_ms, AGG_BYTES_PER_CELL * 2.0 / 8.0, "W, E (in-step hipEvent pairs)"),
                        ("sum_wta_trap_kernel" if D == 256 else "sum_wta_lr_kernel"):
                            kernel_row("sum_wta_trap_kernel" if D == 256 else "sum_wta_lr_kernel", sum_ms, 4.0, "sum + left / right WTA + sub-pixel (stage-timed pass, overlap off)")}
-        occ_txt = "occlusion heuristic + " if use_occ else ""
-        result = {
-            "metric": f"Mdisparities/s (HxWxD / s) VPP+rSGM at {H}x{W}xD={D}",
-            "value": round(value, 1), "unit": "Mdisparities/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        result.update({
             "ms_per_step_unpipelined": round(ms_unpipelined, 3) if ms_unpipelined else None,
             "ms_per_step_sustained": round(ms_sustained, 3) if ms_sustained else None, "sustained_steps": args.sustained_steps if ms_sustained else None,
-            "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u16",
-            "data": "synthetic (uniform random u8)" if args.uniform_random else "synthetic",
-            "config": {"workload": f"{H}x{W} RGB pair, {100 * P_HINTS:g}% hints, {occ_txt}VPP(rnd, wsize 3)+rSGM D={D} subpixel, "
-                                   f"{B} frames/GPU/step resident in HBM", "frames_per_step": n_total,
-                       "H": H, "W": W, "D": D, "hint_density": P_HINTS, "g_occ": "occlusion_heuristic" if use_occ else None,
-                       "parts": (f"the library runs a call of {B} frames as {-(-B // agg_frames)} consecutive parts of {agg_frames} frames (one round of "
-                                 "the lock-step aggregation kernel each; results do not depend on the split; VPPX_CHUNK=0 keeps whole batches)"
-                                 if 0 < agg_frames < B else None),
-                       "cross_step_overlap": (None if (args.no_pipeline or args.graph) else
-                                              "front stage of step k+1 (occlusion heuristic, VPP, pad+gray, census) on a second "
-                                              "stream under the sum/WTA and post kernels of step k; inputs are resident and declared "
-                                              "ready (vppx_inputs_ready_event), outputs are delivered in launch-stream order; "
-                                              "ms_per_step_unpipelined is the same loop with the overlap off")},
-            "ranks": {"launched": args.gpus, "seen": dist.get_world_size() if world > 1 else 1,
-                      "backend": (backend if backend != "nccl" else "nccl (RCCL)") if world > 1 else None,
-                      "ms_per_step_per_rank": [round(x, 3) for x in rank_ms],
-                      "gather_wait_ms_per_step_per_rank": [round(x, 3) for x in rank_gather_ms] if world > 1 else None,
-                      "numa_node_per_rank": rank_numa if world > 1 else None,
-                      # the curve the first multi-GPU run is to be checked against (DESIGN section 10), from this run's own
-                      # one-GPU step time when N = 1, else from the slowest non-root rank
-                      "predicted": predict_scaling(ms_per_step if world == 1 else (sorted(rank_ms)[0] if rank_ms else ms_per_step), B, H, W, D)},
             # The dominant kernel (bench contract): SURVEY 8d's algorithmic bytes of the launch -- 10 B/cell for the 8-path
             # aggregation, pro rata for the paths the launch carries -- over its average duration inside the timed steps
             # (hipEvent pairs on the launch stream), against the HBM3E peak; `traffic` = the launch's real HBM bytes (PMC).
@@ -888,13 +890,7 @@ def run_rank(args):
                    "what": "one frame per call (B=1), host-paced loop of 20 calls, same stages as the step"
                            + ("" if (args.no_pipeline or args.graph) else "; consecutive calls overlap like the steps (cross_step_overlap)")},
             "stage_ms": {k: round(v, 3) for k, v in stages.items()},
-            "kernel_source_sha": kernel_source_sha(),
-            "device": eng.ctx.device_name,
-        }
-        if args.graph:
-            result["graph_replays"] = eng.graph_replays()
-        if world > 1:
-            result["config"]["result_gather"] = "off (--no-gather)" if args.no_gather else "async gather to rank 0, overlapped"
+        })
         if world == 1 and args.cpu_frames > 0:
             gpu_out = local_step(outs[0], use_occ)[: min(args.cpu_frames, n_unique)].cpu().numpy()
             result["cpu_baseline"], epe = cpu_baseline(min(args.cpu_frames, n_unique), gpu_out)
@@ -954,6 +950,46 @@ def run_rank(args):
                     "runs": [hs.measure(H, W, D, P_HINTS, 384), hs.measure(375, 1242, 192, 0.05, 384)]}
             except Exception as e:  # noqa: BLE001  (a measurement next to the headline: its failure must not lose the line)
                 result["host_stream"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+
+    result = None
+    if rank == 0:
+        agg_frames = eng.time_aggregate_frames()  # frames per launch (the batch is split over sub-streams)
+        occ_txt = "occlusion heuristic + " if use_occ else ""
+        result = {
+            "metric": f"Mdisparities/s (HxWxD / s) VPP+rSGM at {H}x{W}xD={D}",
+            "value": round(value, 1), "unit": "Mdisparities/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u16",
+            "data": "synthetic (uniform random u8)" if args.uniform_random else "synthetic",
+            "config": {"workload": f"{H}x{W} RGB pair, {100 * P_HINTS:g}% hints, {occ_txt}VPP(rnd, wsize 3)+rSGM D={D} subpixel, "
+                                   f"{B} frames/GPU/step resident in HBM", "frames_per_step": n_total,
+                       "H": H, "W": W, "D": D, "hint_density": P_HINTS, "g_occ": "occlusion_heuristic" if use_occ else None,
+                       "parts": (f"the library runs a call of {B} frames as {-(-B // agg_frames)} consecutive parts of {agg_frames} frames (one round of "
+                                 "the lock-step aggregation kernel each; results do not depend on the split; VPPX_CHUNK=0 keeps whole batches)"
+                                 if 0 < agg_frames < B else None),
+                       "cross_step_overlap": (None if (args.no_pipeline or args.graph) else
+                                              "front stage of step k+1 (occlusion heuristic, VPP, pad+gray, census) on a second "
+                                              "stream under the sum/WTA and post kernels of step k; inputs are resident and declared "
+                                              "ready (vppx_inputs_ready_event), outputs are delivered in launch-stream order; "
+                                              "ms_per_step_unpipelined (--full) is the same loop with the overlap off")},
+            "ranks": {"launched": args.gpus, "seen": dist.get_world_size() if world > 1 else 1,
+                      "backend": (backend if backend != "nccl" else "nccl (RCCL)") if world > 1 else None,
+                      "ms_per_step_per_rank": [round(x, 3) for x in rank_ms],
+                      "gather_wait_ms_per_step_per_rank": [round(x, 3) for x in rank_gather_ms] if world > 1 else None,
+                      "numa_node_per_rank": rank_numa if world > 1 else None,
+                      # the curve the first multi-GPU run is to be checked against (DESIGN section 10), from this run's own
+                      # one-GPU step time when N = 1, else from the slowest non-root rank
+                      "predicted": predict_scaling(ms_per_step if world == 1 else (sorted(rank_ms)[0] if rank_ms else ms_per_step), B, H, W, D)},
+            "kernel_source_sha": kernel_source_sha(),
+            "device": eng.ctx.device_name,
+        }
+        if args.graph:
+            result["graph_replays"] = eng.graph_replays()
+        if world > 1:
+            result["config"]["result_gather"] = "off (--no-gather)" if args.no_gather else "async gather to rank 0, overlapped"
+        if args.full:
+            full_legs(result)
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

@@ -122,3 +122,22 @@ def test_dump_outputs_fits_the_budget_at_the_headline_shape_and_samples_the_same
     bench.dump_outputs(str(tmp_path / "c"), {"disparity": small})
     whole = np.load(str(tmp_path / "c" / "disparity.npy"))
     assert whole.shape == small.shape and np.array_equal(whole, small)
+
+
+def test_side_legs_wait_for_full():
+    """A plain run times the headline alone; `--full` adds every figure that takes runs of its own."""
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full"]).full is True
+
+
+def test_inputs_made_on_worker_processes_are_make_batch_bit_for_bit(monkeypatch):
+    """The step's scenes are synthesised on spawned processes: the same arrays, frame for frame, as synth.make_batch."""
+    import numpy as np
+    import synth
+    for name, v in (("H", 60), ("W", 112), ("D", 64), ("P_HINTS", 0.04)):
+        monkeypatch.setattr(bench, name, v)
+    want = synth.make_batch(5, 60, 112, 64, 0.04, seed=1234, frame0=3)
+    for procs in (1, 3):
+        got = bench.make_inputs(5, 3, procs)
+        for k in ("left", "right", "hints"):
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (procs, k)

@@ -5,15 +5,16 @@
 out=$1; settings=$2; rounds=$3; shift; shift; shift
 cd "${GRAFT_REPO_ROOT:?}"
 mkdir -p gpurun_out
+tmp=$(mktemp -d)
 echo "[" > $out
 first=1
 for r in $(seq 1 $rounds); do
     for s in $settings; do
-        env ${s//,/ } python3 bench.py --sustained-steps 0 --no-other-configs --cpu-frames 0 "$@" > gpurun_out/ab.tmp 2> gpurun_out/ab.err
+        env ${s//,/ } python3 bench.py --full --sustained-steps 0 --no-other-configs --cpu-frames 0 "$@" > $tmp/line 2> $tmp/err
         [ $first = 1 ] || echo "," >> $out
         first=0
-        line=$(grep '^{' gpurun_out/ab.tmp | tail -1)
-        if [ -z "$line" ]; then line="{\"error\": \"$(tail -3 gpurun_out/ab.err | tr '"\n' "' ")\"}"; fi
+        line=$(grep '^{' $tmp/line | tail -1)
+        if [ -z "$line" ]; then line="{\"error\": \"$(tail -3 $tmp/err | tr '"\n' "' ")\"}"; fi
         echo "{\"setting\": \"$s\", \"round\": $r, \"line\": $line}" >> $out
     done
 done

@@ -8,16 +8,18 @@ out=$1; rounds=$2; trees=$3; shift; shift; shift
 cd "${GRAFT_REPO_ROOT:?}"
 root=$PWD
 mkdir -p gpurun_out
+tmp=$(mktemp -d)
 echo "[" > $out
 first=1
 for r in $(seq 1 $rounds); do
     for t in $trees; do
+        full=$(grep -q '"--full"' $root/$t/bench.py && echo --full)   # a tree's bench.py from before --full runs every leg by default
         for mode in "" "--no-pipeline"; do
-            (cd $root/$t && python3 bench.py --no-other-configs --cpu-frames 0 $mode "$@") > gpurun_out/abt.tmp 2> gpurun_out/abt.err
+            (cd $root/$t && python3 bench.py $full --no-other-configs --cpu-frames 0 $mode "$@") > $tmp/line 2> $tmp/err
             [ $first = 1 ] || echo "," >> $out
             first=0
-            line=$(grep '^{' gpurun_out/abt.tmp | tail -1)
-            if [ -z "$line" ]; then line="{\"error\": \"$(tail -3 gpurun_out/abt.err | tr '"\n' "' ")\"}"; fi
+            line=$(grep '^{' $tmp/line | tail -1)
+            if [ -z "$line" ]; then line="{\"error\": \"$(tail -3 $tmp/err | tr '"\n' "' ")\"}"; fi
             echo "{\"tree\": \"$t\", \"mode\": \"${mode:-pipelined}\", \"round\": $r, \"line\": $line}" >> $out
         done
     done

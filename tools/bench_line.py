@@ -1,4 +1,4 @@
-"""tools/bench_line.py < bench.json : the handful of numbers of a bench line that matter while iterating."""
+"""tools/bench_line.py < bench.json : the handful of numbers of a `bench.py --full` line that matter while iterating."""
 import json
 import sys
 

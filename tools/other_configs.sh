@@ -3,13 +3,14 @@
 out=$1
 cd "${GRAFT_REPO_ROOT:?}"
 mkdir -p gpurun_out
+tmp=$(mktemp)
 echo "[" > $out
 first=1
 run() {
-    python3 bench.py --steps 6 --warmup 2 --cpu-frames 0 "$@" > gpurun_out/oc.tmp 2>/dev/null
+    python3 bench.py --full --steps 6 --warmup 2 --cpu-frames 0 "$@" > $tmp 2>/dev/null
     [ $first = 1 ] || echo "," >> $out
     first=0
-    grep '^{' gpurun_out/oc.tmp | tail -1 >> $out
+    grep '^{' $tmp | tail -1 >> $out
 }
 run --shape 375 1242 192 0.05
 run --shape 1536 2048 256 0.01 --batch 8
