@@ -18,6 +18,7 @@
  *   compute_rsgm()                      rsgm.py:250-294             vppx_rsgm_host / vppx_rsgm_dev
  *   occlusion_heuristic()               filter.py:246-292           vppx_occlusion_heuristic_host/_dev
  *   test.py:158-225 (VPP -> rSGM per frame)                         vppx_vpp_rsgm_dev (fused, batched)
+ *   guided_metrics()                    losses.py:13-24             vppx_guided_metrics_host / _dev, vppx_occ_vpp_rsgm_eval_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -320,6 +321,47 @@ int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams *op, const 
                                   const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out,
                                   uint8_t *l_vpp_out, uint8_t *r_vpp_out, float *disp_out, float *disp_small, uint64_t *draws_out);
 
+/* ---- evaluation metrics (losses.py:13-24 guided_metrics; test.py:150-152, :251-252) ------------------------------------
+ * What test.py reports per frame: over the pixels with validgt > 0, with e = |disp - gt| and d2 = (disp - gt)^2 in float32,
+ * bad_t = n(e > t) / n_valid for t = 1, 2, 3, 4, avgerr = sum(e) / n_valid, rms = sqrt(sum(d2) / n_valid): exact integer
+ * counts, float64 sums of the float32 terms, float64 results (all six NaN when no pixel is valid).  The sums are added in a
+ * fixed order that depends on the frame's shape only (no floating-point atomics): a frame's record is the same bytes alone,
+ * as frame 17 of 32, or in a flushed part batch of a frame stream.  NaN disparities (vppx_status) go through the same
+ * expressions as in numpy: compares false, sums NaN. */
+typedef struct VppxMetrics {
+    double bad1, bad2, bad3, bad4; /* 'bad 1.0' ... 'bad 4.0' */
+    double avgerr, rms;
+    double n_valid;                /* pixels with validgt > 0 (an integer) */
+    double reserved;
+} VppxMetrics;                     /* 64 bytes */
+typedef struct VppxEvalParams {
+    int32_t gt_scale;  /* >= 1, default 1: --oscale (test.py:150-152): gt and validgt are read at every gt_scale-th row and
+                        * column (F.interpolate nearest) and gt is divided by gt_scale (float32 true division) */
+    int32_t reserved0;
+} VppxEvalParams;
+void vppx_eval_params_default(VppxEvalParams *p);
+
+/* losses.guided_metrics for a batch: device pointers, stream-ordered, no synchronisation.  disp float32 [B,Ho,Wo]; gt, validgt
+ * float32 [B,Hg,Wg] (validgt > 0 is valid: the reference's float mask); (Hg / gt_scale, Wg / gt_scale) (integer division)
+ * must be (Ho, Wo), else VPPX_E_INVALID_ARG before anything is launched (the reference dies in a numpy broadcast there).
+ * metrics_out: device VppxMetrics[B]; errormap (device float32 [B,Ho,Wo], may be NULL) receives the reference's seventh
+ * entry, error * (validgt > 0).  ep == NULL: gt_scale 1. */
+int vppx_guided_metrics_dev(vppx_ctx *ctx, const VppxEvalParams *ep, int B, int Ho, int Wo, const float *disp, int Hg, int Wg,
+                            const float *gt, const float *validgt, VppxMetrics *metrics_out, float *errormap);
+/* The same on host pointers, synchronous. */
+int vppx_guided_metrics_host(vppx_ctx *ctx, const VppxEvalParams *ep, int B, int Ho, int Wo, const float *disp, int Hg, int Wg,
+                             const float *gt, const float *validgt, VppxMetrics *metrics_out, float *errormap);
+/* vppx_occ_vpp_rsgm_scaled_dev and, behind it on the same stream, the metrics of its result: test.py:136-252 in one call.  sp
+ * may be NULL (unscaled); validhints NULL = unguided; gt / validgt are float32 [B,H,W] (the full frame shape) and ep->gt_scale
+ * must take them to (Ho, Wo); disp_out is required.  The metrics are queued on the launch stream behind the post stage: once,
+ * over the whole batch, also when the call runs in parts (vppx_last_call_parts), with vppx_set_pipeline, and inside the
+ * captured graph of vppx_set_graph_mode. */
+int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                               const VppxScaleParams *sp, const VppxEvalParams *ep, int B, int H, int W, int C, const uint8_t *left,
+                               const uint8_t *right, const float *g, const uint8_t *g_occ, const float *validhints, const float *gt,
+                               const float *validgt, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
+                               float *disp_small, VppxMetrics *metrics_out, float *errormap);
+
 /* ---- frame stream: the hot path for callers that hold one host frame at a time ---------------------------------------
  * test.py:291-311 iterates a DataLoader with batch size 1 and runs :154-225 per frame on numpy arrays; the kernels want
  * batches of one lock-step round, resident.  A frame stream takes (left, right, hints[, g_occ]) host arrays one frame at a
@@ -345,6 +387,8 @@ int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams *op, const 
 #define VPPX_FS_MASK 2
 #define VPPX_FS_GOCC 4
 #define VPPX_FS_GUIDED 8
+#define VPPX_FS_METRICS 16  /* every push brings gt + validgt (vppx_fstream_push_eval); pop can return the frame's VppxMetrics */
+#define VPPX_FS_NO_DISP 32  /* needs VPPX_FS_METRICS: disparities are not copied out; pop's disp_out must be NULL */
 typedef struct vppx_fstream vppx_fstream;
 int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int batch,
                         int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out);
@@ -373,6 +417,24 @@ int vppx_fstream_flush(vppx_fstream *fs);
  * outstanding (frames of a batch still being filled need vppx_fstream_flush). */
 int vppx_fstream_pop(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out,
                      uint64_t *draws_out, int *got);
+/* An evaluating stream (flags must hold VPPX_FS_METRICS): every push brings the frame's ground truth at the full frame shape,
+ * float32 gt [H,W] and validgt [H,W] (> 0 is valid; the ring keeps one byte per pixel of it), and the metrics of every batch
+ * are computed on the device behind its kernels -- vppx_guided_metrics_dev of the stream's disparities with ep->gt_scale, which
+ * must take (H, W) to the shape of the returned map -- and come down with the other results, 64 bytes per frame.  With
+ * VPPX_FS_NO_DISP the disparity maps stay on the device.  sp may be NULL (unscaled), ep NULL means gt_scale 1.  A batch re-run
+ * after a lost lock step re-runs its metrics: what a pop returns belongs to the disparities that pop verified. */
+int vppx_fstream_create_eval(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                             const VppxScaleParams *sp, const VppxEvalParams *ep, int batch, int depth, int H, int W, int C, int flags,
+                             int copy_threads, vppx_fstream **out);
+/* One frame with its ground truth in; validhints NULL unless VPPX_FS_GUIDED.  As vppx_fstream_push otherwise (a failed submit
+ * included).  vppx_fstream_push / _push_guided on a VPPX_FS_METRICS stream and this call on any other stream fail with
+ * VPPX_E_INVALID_ARG. */
+int vppx_fstream_push_eval(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ,
+                           const float *validhints, const float *gt, const float *validgt);
+/* vppx_fstream_pop plus the frame's metrics (metrics_out may be NULL; non-NULL needs a VPPX_FS_METRICS stream).  disp_out may
+ * be NULL here, and must be on a VPPX_FS_NO_DISP stream (VPPX_E_INVALID_ARG otherwise, also from vppx_fstream_pop). */
+int vppx_fstream_pop_eval(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out,
+                          uint64_t *draws_out, VppxMetrics *metrics_out, int *got);
 /* Frames pushed since creation, frames of the batch being filled, frames submitted and not yet popped, batches re-run
  * after a lost lock step (any pointer may be NULL). */
 int vppx_fstream_counts(vppx_fstream *fs, int64_t *pushed, int64_t *filling, int64_t *unpopped, int64_t *reruns);

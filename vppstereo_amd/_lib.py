@@ -33,8 +33,12 @@ EXPORTS = [
     "vppx_occ_vpp_rsgm_guided_dev", "vppx_occ_vpp_rsgm_guided_host", "vppx_fstream_push_guided",
     "vppx_scale_params_default", "vppx_scaled_shape", "vppx_occ_vpp_rsgm_scaled_dev", "vppx_occ_vpp_rsgm_scaled_host",
     "vppx_fstream_create_scaled",
+    "vppx_eval_params_default", "vppx_guided_metrics_dev", "vppx_guided_metrics_host", "vppx_occ_vpp_rsgm_eval_dev",
+    "vppx_fstream_create_eval", "vppx_fstream_push_eval", "vppx_fstream_pop_eval",
 ]
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
+FS_METRICS, FS_NO_DISP = 16, 32
+METRIC_KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')  # the reference's dict keys (losses.py:24), VppxMetrics order
 
 
 class VppxVppParams(C.Structure):
@@ -62,6 +66,15 @@ class VppxOccParams(C.Structure):
 
 class VppxScaleParams(C.Structure):
     _fields_ = [("iscale", C.c_int32), ("oscale", C.c_int32)]
+
+
+class VppxEvalParams(C.Structure):
+    _fields_ = [("gt_scale", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class VppxMetrics(C.Structure):
+    _fields_ = [("bad1", C.c_double), ("bad2", C.c_double), ("bad3", C.c_double), ("bad4", C.c_double), ("avgerr", C.c_double),
+                ("rms", C.c_double), ("n_valid", C.c_double), ("reserved", C.c_double)]
 
 
 class VppxError(Exception):
@@ -194,6 +207,15 @@ def load():
         lib.vppx_fstream_create_scaled.argtypes = [vp, po, pv, pr, ps, i, i, i, i, i, i, i, C.POINTER(vp)]
         p64 = C.POINTER(C.c_int64)
         lib.vppx_fstream_counts.argtypes = [vp, p64, p64, p64, p64]
+        pe = C.POINTER(VppxEvalParams)
+        lib.vppx_eval_params_default.argtypes = [pe]
+        lib.vppx_eval_params_default.restype = None
+        lib.vppx_guided_metrics_dev.argtypes = [vp, pe, i, i, i, vp, i, i, vp, vp, vp, vp]
+        lib.vppx_guided_metrics_host.argtypes = [vp, pe, i, i, i, vp, i, i, vp, vp, vp, vp]
+        lib.vppx_occ_vpp_rsgm_eval_dev.argtypes = [vp, po, pv, pr, ps, pe, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.vppx_fstream_create_eval.argtypes = [vp, po, pv, pr, ps, pe, i, i, i, i, i, i, i, C.POINTER(vp)]
+        lib.vppx_fstream_push_eval.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.vppx_fstream_pop_eval.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(VppxMetrics), C.POINTER(C.c_int)]
         _lib = lib
         return lib
 
@@ -342,6 +364,28 @@ def scale_params(**kw):
     p = VppxScaleParams()
     load().vppx_scale_params_default(C.byref(p))
     return _fill(p, kw)
+
+
+def eval_params(**kw):
+    """VppxEvalParams: gt_scale = --oscale of test.py:150-152 (default 1)."""
+    p = VppxEvalParams()
+    load().vppx_eval_params_default(C.byref(p))
+    return _fill(p, kw)
+
+
+def check_gt_shape(Hg, Wg, gt_scale, Ho, Wo, what="gt"):
+    """What the library checks before it launches anything (vppx_guided_metrics_dev): gt_scale takes gt to the map's shape."""
+    s = int(gt_scale)
+    if s < 1:
+        raise ValueError(f"gt_scale {s} (>= 1)")
+    if (Hg // s, Wg // s) != (Ho, Wo):
+        raise ValueError(f"{what} of {Hg} x {Wg} at gt_scale {s} is {Hg // s} x {Wg // s}, the disparity map is {Ho} x {Wo}")
+
+
+def metrics_dict(rec):
+    """One VppxMetrics record (ctypes struct or a sequence of its 8 doubles) -> the reference's dict (losses.py:24)."""
+    v = [rec.bad1, rec.bad2, rec.bad3, rec.bad4, rec.avgerr, rec.rms] if isinstance(rec, VppxMetrics) else [float(x) for x in rec[:6]]
+    return dict(zip(METRIC_KEYS, v))
 
 
 def scaled_shape(H, W, iscale=1, oscale=1):

@@ -12,7 +12,9 @@
 namespace vppx_host {
 
 // one frame is 5-7 MB, one core moves 8-20 GB/s
-struct CopyJob { void *dst; const void *src; size_t bytes; };
+// kind 0: bytes copied as they are.  kind 1: src is float32, dst one byte per element, `bytes` of them: dst[i] = src[i] > 0
+// (an evaluating stream's validity plane: the copy touches every element anyway)
+struct CopyJob { void *dst; const void *src; size_t bytes; int kind = 0; };
 class CopyPool {
 public:
     explicit CopyPool(int nthreads)
@@ -35,12 +37,14 @@ public:
         pieces_.clear();
         for (int i = 0; i < n; i++) {
             if (!jobs[i].dst || !jobs[i].src) continue;
-            for (size_t o = 0; o < jobs[i].bytes; o += piece)
-                pieces_.push_back({(char *)jobs[i].dst + o, (const char *)jobs[i].src + o, jobs[i].bytes - o < piece ? jobs[i].bytes - o : piece});
+            const size_t step = jobs[i].kind == 1 ? piece / 4 : piece; // (a piece READS 256 KB either way)
+            for (size_t o = 0; o < jobs[i].bytes; o += step)
+                pieces_.push_back({(char *)jobs[i].dst + o, (const char *)jobs[i].src + (jobs[i].kind == 1 ? 4 * o : o),
+                                   jobs[i].bytes - o < step ? jobs[i].bytes - o : step, jobs[i].kind});
         }
         if (pieces_.empty()) return;
         if (workers_.empty() || pieces_.size() == 1) {
-            for (auto &p : pieces_) memcpy(p.dst, p.src, p.bytes);
+            for (auto &p : pieces_) one(p);
             return;
         }
         {
@@ -61,13 +65,23 @@ public:
     }
 
 private:
+    static void one(const CopyJob &p)
+    {
+        if (p.kind == 1) {
+            const float *src = (const float *)p.src;
+            unsigned char *dst = (unsigned char *)p.dst;
+            for (size_t i = 0; i < p.bytes; i++) dst[i] = src[i] > 0.f;
+        } else {
+            memcpy(p.dst, p.src, p.bytes);
+        }
+    }
     void work()
     {
         int mine = 0;
         for (;;) {
             const size_t i = next_.fetch_add(1);
             if (i >= pieces_.size()) break;
-            memcpy(pieces_[i].dst, pieces_[i].src, pieces_[i].bytes);
+            one(pieces_[i]);
             mine++;
         }
         if (mine) left_.fetch_sub(mine, std::memory_order_release);

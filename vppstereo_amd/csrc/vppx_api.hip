@@ -1654,6 +1654,17 @@ static int scale_tables(vppx_ctx *ctx, int H, int W, const VppxScaleParams &sp, 
     return 0;
 }
 
+// guided_metrics of a finished map on the launch stream (ctx->eval: vppx_occ_vpp_rsgm_eval_dev).  The partial records have their
+// own workspace slot: a pipelined next call's front stage runs next to this and shares nothing with it.
+static int eval_launch(vppx_ctx *ctx, int B, int Ho, int Wo, const float *disp)
+{
+    const vppx_ctx::EvalReq &e = ctx->eval;
+    void *part = nullptr;
+    int rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part);
+    if (rc) return rc;
+    return metrics_launch(ctx, B, Ho, Wo, disp, e.Hg, e.Wg, e.gt_scale, e.gt, e.valid, e.valid_is_u8, part, e.out, e.errormap);
+}
+
 // The scaled call on device pointers: resize + decimation (scale_front_kernel), the unchanged hot path at (h, w) on the
 // library-owned scaled buffers, then the restore (scale_restore_kernel) on the launch stream.
 static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
@@ -1693,6 +1704,7 @@ static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPara
     if ((rc = ws_get(ctx, set ? WS_SCALE_G1 : WS_SCALE_G0, np, &gs))) return rc;
     if (validhints && (rc = ws_get(ctx, set ? WS_SCALE_V1 : WS_SCALE_V0, np, &vhs))) return rc;
     const bool restore = scale_restores(*sp);
+    if (ctx->eval.active) ctx->eval.after_restore = restore; // (the metrics read the restored map: queued below, not by the hot path)
     float *dsmall = restore ? disp_small : disp_out;
     if (restore && !dsmall && (rc = ws_get(ctx, WS_SCALE_DSMALL, np, &dsmall))) return rc;
     ScaleFrontArgs a;
@@ -1735,6 +1747,7 @@ static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPara
         const int *ry = tab + 4 * h + 4 * w, *rx = ry + Ho;
         if ((rc = scale_launch_restore(ctx, B, h, w, Ho, Wo, dsmall, disp_out, ry, rx, sp->iscale, sp->oscale))) return rc;
         route_note(ctx, "scale_restore");
+        if (ctx->eval.active && (rc = eval_launch(ctx, B, Ho, Wo, disp_out))) return rc;
     } else if (disp_small) {
         VPPX_HIP(hipMemcpyAsync(disp_small, disp_out, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
@@ -1809,6 +1822,117 @@ extern "C" int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams 
         if (!mine || attempt > 0) return rc;
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// evaluation metrics (losses.py:13-24; test.py:150-152, :251-252)
+// ---------------------------------------------------------------------------------------
+extern "C" void vppx_eval_params_default(VppxEvalParams *p)
+{
+    if (!p) return;
+    p->gt_scale = 1;
+    p->reserved0 = 0;
+}
+
+static int check_metrics_args(const char *name, const VppxEvalParams *ep, int B, int Ho, int Wo, int Hg, int Wg, int *gt_scale)
+{
+    const int s = ep ? ep->gt_scale : 1;
+    if (s < 1) { vppx_set_error("%s: gt_scale %d (>= 1)", name, s); return VPPX_E_INVALID_ARG; }
+    if (B < 1 || B > 65535 || Ho < 1 || Wo < 1 || Hg < 1 || Wg < 1 || (size_t)Hg * Wg > ((size_t)1 << 31)) {
+        vppx_set_error("%s: bad shape (B %d, map %d x %d, gt %d x %d)", name, B, Ho, Wo, Hg, Wg);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (Hg / s != Ho || Wg / s != Wo) {
+        vppx_set_error("%s: gt of %d x %d at gt_scale %d is %d x %d, the disparity map is %d x %d", name, Hg, Wg, s, Hg / s, Wg / s, Ho, Wo);
+        return VPPX_E_INVALID_ARG;
+    }
+    *gt_scale = s;
+    return 0;
+}
+
+static int guided_metrics_dev(vppx_ctx *ctx, const char *name, const VppxEvalParams *ep, int B, int Ho, int Wo, const float *disp, int Hg,
+                              int Wg, const float *gt, const void *valid, int valid_is_u8, VppxMetrics *metrics_out, float *errormap)
+{
+    int rc, s = 1;
+    if (!disp || !gt || !valid || !metrics_out) { vppx_set_error("%s: NULL argument", name); return VPPX_E_INVALID_ARG; }
+    if ((rc = check_metrics_args(name, ep, B, Ho, Wo, Hg, Wg, &s))) return rc;
+    void *part = nullptr;
+    if ((rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part))) return rc;
+    return metrics_launch(ctx, B, Ho, Wo, disp, Hg, Wg, s, gt, valid, valid_is_u8, part, metrics_out, errormap);
+}
+
+extern "C" int vppx_guided_metrics_dev(vppx_ctx *ctx, const VppxEvalParams *ep, int B, int Ho, int Wo, const float *disp, int Hg, int Wg,
+                                       const float *gt, const float *validgt, VppxMetrics *metrics_out, float *errormap)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx); // (its only scratch is a slot no front stage touches)
+    return guided_metrics_dev(ctx, "vppx_guided_metrics_dev", ep, B, Ho, Wo, disp, Hg, Wg, gt, validgt, 0, metrics_out, errormap);
+}
+
+extern "C" int vppx_guided_metrics_host(vppx_ctx *ctx, const VppxEvalParams *ep, int B, int Ho, int Wo, const float *disp, int Hg, int Wg,
+                                        const float *gt, const float *validgt, VppxMetrics *metrics_out, float *errormap)
+{
+    VPPX_ENTER(ctx);
+    int rc, s = 1;
+    if (!disp || !gt || !validgt || !metrics_out) { vppx_set_error("vppx_guided_metrics_host: NULL argument"); return VPPX_E_INVALID_ARG; }
+    if ((rc = check_metrics_args("vppx_guided_metrics_host", ep, B, Ho, Wo, Hg, Wg, &s))) return rc;
+    const size_t npo = (size_t)B * Ho * Wo, npg = (size_t)B * Hg * Wg;
+    void *dd, *dg, *dv, *dm, *de = nullptr;
+    if ((rc = upload(ctx, WS_STAGE_A, disp, npo * sizeof(float), &dd))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_B, gt, npg * sizeof(float), &dg))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_C, validgt, npg * sizeof(float), &dv))) return rc;
+    if ((rc = ws_reserve(ctx, WS_METRICS_OUT, (size_t)B * sizeof(VppxMetrics), &dm))) return rc;
+    if (errormap && (rc = ws_reserve(ctx, WS_STAGE_E, npo * sizeof(float), &de))) return rc;
+    if ((rc = guided_metrics_dev(ctx, "vppx_guided_metrics_host", ep, B, Ho, Wo, (const float *)dd, Hg, Wg, (const float *)dg, dv, 0,
+                                 (VppxMetrics *)dm, (float *)de)))
+        return rc;
+    if ((rc = download(ctx, metrics_out, dm, (size_t)B * sizeof(VppxMetrics)))) return rc;
+    if (de && (rc = download(ctx, errormap, de, npo * sizeof(float)))) return rc;
+    VPPX_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// The scaled call with ctx->eval set for its duration: the hot path (or scaled_call, behind a restore) queues the metrics.
+// validgt: float32, or one byte per pixel (an evaluating frame stream's ring).
+int vppx_eval_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
+                            const VppxEvalParams *ep, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g,
+                            const uint8_t *g_occ, const float *validhints, const float *gt, const void *validgt, int valid_is_u8,
+                            uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out,
+                            float *errormap)
+{
+    int rc, s = 1;
+    if (!gt || !validgt || !metrics_out || !disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_eval: NULL argument"); return VPPX_E_INVALID_ARG; }
+    VppxScaleParams one = {1, 1};
+    if (!sp) sp = &one;
+    int h, w, Ho, Wo;
+    if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
+    if ((rc = check_metrics_args("vppx_occ_vpp_rsgm_eval", ep, B, Ho, Wo, H, W, &s))) return rc;
+    {   // the records' slot is sized before anything is queued (and before a capture could begin)
+        void *part = nullptr;
+        if ((rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part))) return rc;
+    }
+    vppx_ctx::EvalReq &e = ctx->eval;
+    e.active = true;
+    e.after_restore = false;
+    e.gt = gt; e.valid = validgt; e.valid_is_u8 = valid_is_u8;
+    e.gt_scale = s; e.Hg = H; e.Wg = W;
+    e.out = metrics_out; e.errormap = errormap;
+    rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out, disp_small);
+    ctx->eval = vppx_ctx::EvalReq();
+    ctx->inputs_ev = nullptr; // one-shot, whatever happened
+    return rc;
+}
+
+extern "C" int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                          const VppxScaleParams *sp, const VppxEvalParams *ep, int B, int H, int W, int C, const uint8_t *left,
+                                          const uint8_t *right, const float *g, const uint8_t *g_occ, const float *validhints, const float *gt,
+                                          const float *validgt, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
+                                          float *disp_small, VppxMetrics *metrics_out, float *errormap)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx);
+    return vppx_eval_call_internal(ctx, op, vp, rp, sp, ep, B, H, W, C, left, right, g, g_occ, validhints, gt, validgt, 0, conf_out, l_vpp, r_vpp,
+                                   disp_out, disp_small, metrics_out, errormap);
 }
 
 // Batches larger than one round of the lock-step kernel are run as consecutive parts of one round each ("batch quantum":
@@ -1907,6 +2031,17 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
 extern "C" int vppx_last_call_parts(vppx_ctx *ctx) { return ctx ? ctx->last_parts : 0; }
 extern "C" int vppx_we_last_pieces(vppx_ctx *ctx) { return ctx ? ctx->we_last_pieces : 0; }
 
+// The parts of a call and, for an evaluating call whose map is complete with them, its metrics: once, over the whole batch,
+// behind the last part -- and inside the capture when the call is being captured.
+static int vpp_rsgm_parts_eval(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
+                               int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
+                               const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+{
+    const int rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+    if (rc || !ctx->eval.active || ctx->eval.after_restore) return rc;
+    return eval_launch(ctx, B, H, W, disp_out);
+}
+
 static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
                           int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
                           const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
@@ -1933,6 +2068,11 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         key.has_op = op ? 1 : 0;
         if (op) key.op = *op;
         key.stream = (void *)ctx->stream;
+        if (ctx->eval.active && !ctx->eval.after_restore) {
+            const vppx_ctx::EvalReq &e = ctx->eval;
+            key.eval_ptr[0] = e.gt; key.eval_ptr[1] = e.valid; key.eval_ptr[2] = e.out; key.eval_ptr[3] = e.errormap;
+            key.eval_scale[0] = e.gt_scale; key.eval_scale[1] = e.Hg; key.eval_scale[2] = e.Wg; key.eval_scale[3] = e.valid_is_u8;
+        }
         key.ws_gen = ctx->ws_gen;
         // the graph does not contain the penalty-table upload: it must still be the table of these parameters
         const bool lut_ok = ctx->lut_valid && ctx->lut_p2min == rp->p2min && ctx->lut_gamma == rp->gamma && ctx->lut_alpha == rp->alpha;
@@ -1948,7 +2088,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
                 ctx->capturing = true;
-                rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+                rc = vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
                 ctx->capturing = false;
                 hipGraph_t graph = nullptr;
                 e = hipStreamEndCapture(ctx->stream, &graph);
@@ -1978,15 +2118,15 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             // capture is not possible here (e.g. the legacy default stream): stay on the eager path
             (void)hipGetLastError();
             ctx->graph_mode = false;
-            return vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+            return vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
         }
-        rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+        rc = vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
         key.ws_gen = ctx->ws_gen; // the workspace as this call left it
         ctx->lastkey = key;
         ctx->have_lastkey = (rc == 0);
         return rc;
     }
-    if (nsub <= 1) return vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+    if (nsub <= 1) return vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
     // Frames are independent: split the batch over child contexts (own stream + arena).  The
     // latency-bound stages of one part (VPP replay, post-processing) then overlap the
     // bandwidth-bound stages of another (aggregation stores, sum/WTA loads).
@@ -2025,6 +2165,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         VPPX_HIP(hipStreamWaitEvent(ctx->stream, ctx->sub_done[i], 0));
         lo += nb;
     }
+    if (ctx->eval.active && !ctx->eval.after_restore && (rc = eval_launch(ctx, B, H, W, disp_out))) return rc;
     // timing helpers look at the last geometry of the first child
     ctx->have_last = false;
     ctx->last_parts = 0; // the children's arenas hold the per-frame draw totals, not this context's (vppx_occ_vpp_rsgm_host reports 0)

@@ -31,6 +31,11 @@ extern "C" int vppx_occ_vpp_rsgm_scaled_dev(vppx_ctx *ctx, const VppxOccParams *
                                             const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
                                             const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp,
                                             uint8_t *r_vpp, float *disp_out, float *disp_small);
+int vppx_eval_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
+                            const VppxEvalParams *ep, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g,
+                            const uint8_t *g_occ, const float *validhints, const float *gt, const void *validgt, int valid_is_u8,
+                            uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out,
+                            float *errormap); // vppx_api.hip
 
 namespace {
 
@@ -68,8 +73,12 @@ struct vppx_fstream {
     size_t img_s = 0, px_s = 0, px_o = 0;
     size_t in_frame = 0, out_frame = 0;     // ring bytes per frame
     size_t o_left = 0, o_right = 0, o_hint = 0, o_gocc = 0, o_valid = 0;          // offsets inside a slot's input area (planes of `batch` frames)
+    size_t o_gt = 0, o_vgt = 0;             // VPPX_FS_METRICS: float32 gt and ONE BYTE of validgt > 0 per pixel, at the full frame shape
     size_t o_disp = 0, o_lv = 0, o_rv = 0, o_conf = 0, o_draws = 0;  // offsets inside a slot's output area
+    size_t o_metrics = 0;                   // VPPX_FS_METRICS: `batch` VppxMetrics records
     size_t in_bytes = 0, out_bytes = 0;
+    size_t out_host_bytes = 0;              // the host ring's part of the output area: with VPPX_FS_NO_DISP the map, laid out last, stays on the device
+    VppxEvalParams ep = {1, 0};
     std::vector<Slot> slots;
     hipStream_t s_in = nullptr, s_out = nullptr;
     CopyPool *pool = nullptr;
@@ -114,7 +123,7 @@ static int fs_free(vppx_fstream *fs)
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                     int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
+                     const VppxEvalParams *ep, bool eval, int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
 {
     if (!ctx) { vppx_set_error("context is NULL (vppx_create failed? there is no CPU fallback)"); return VPPX_E_NO_DEVICE; }
     if (!out || !vp || !rp) { vppx_set_error("vppx_fstream_create: NULL argument"); return VPPX_E_INVALID_ARG; }
@@ -125,6 +134,12 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     }
     if (op && (flags & VPPX_FS_GOCC)) { vppx_set_error("vppx_fstream_create: either the occlusion heuristic (op) or pushed masks (VPPX_FS_GOCC)"); return VPPX_E_INVALID_ARG; }
     if ((flags & VPPX_FS_MASK) && !op) { vppx_set_error("vppx_fstream_create: VPPX_FS_MASK returns the mask of the occlusion heuristic (op is NULL)"); return VPPX_E_INVALID_ARG; }
+    if (eval != ((flags & VPPX_FS_METRICS) != 0)) {
+        vppx_set_error("vppx_fstream_create: VPPX_FS_METRICS streams are created with vppx_fstream_create_eval, and only they");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((flags & VPPX_FS_NO_DISP) && !(flags & VPPX_FS_METRICS)) { vppx_set_error("vppx_fstream_create: VPPX_FS_NO_DISP needs VPPX_FS_METRICS"); return VPPX_E_INVALID_ARG; }
+    if (eval && ep && ep->gt_scale < 1) { vppx_set_error("vppx_fstream_create_eval: gt_scale %d (>= 1)", ep->gt_scale); return VPPX_E_INVALID_ARG; }
     if (ctx->is_child || ctx->nsub > 1 || ctx->graph_mode || ctx->stage_timing || ctx->legacy_stream) {
         vppx_set_error("vppx_fstream_create: the context must launch on a stream of its own, without sub-streams, graph mode or stage timing");
         return VPPX_E_INVALID_ARG;
@@ -142,6 +157,13 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
         const int rc = vppx_check_hot_path_args_internal(vp, rp, batch, hs, ws, C);
         if (rc) return rc;
     }
+    if (eval) {
+        const int s = ep ? ep->gt_scale : 1;
+        if (H / s != Ho || W / s != Wo) {
+            vppx_set_error("vppx_fstream_create_eval: gt of %d x %d at gt_scale %d is %d x %d, the disparity map is %d x %d", H, W, s, H / s, W / s, Ho, Wo);
+            return VPPX_E_INVALID_ARG;
+        }
+    }
     DevGuard g(ctx->device);
     vppx_fstream *fs = new vppx_fstream();
     fs->ctx = ctx;
@@ -157,6 +179,7 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     fs->img = fs->px * C;
     fs->scaled = sp != nullptr;
     if (sp) fs->sp = *sp;
+    if (eval && ep) fs->ep = *ep;
     fs->px_s = (size_t)hs * ws;
     fs->img_s = fs->px_s * C;
     fs->px_o = (size_t)Ho * Wo;
@@ -167,13 +190,22 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     fs->o_hint = o;  o += up256(fs->px * 4 * batch);
     fs->o_gocc = o;  if (flags & VPPX_FS_GOCC) o += up256(fs->px_s * batch);
     fs->o_valid = o; if (flags & VPPX_FS_GUIDED) o += up256(fs->px * 4 * batch);
+    fs->o_gt = o;    if (flags & VPPX_FS_METRICS) o += up256(fs->px * 4 * batch);
+    fs->o_vgt = o;   if (flags & VPPX_FS_METRICS) o += up256(fs->px * batch);
     fs->in_bytes = o;
     o = 0;
-    fs->o_disp = o;  o += up256(fs->px_o * 4 * batch);
+    const bool no_disp = (flags & VPPX_FS_NO_DISP) != 0;
+    fs->o_disp = o;  if (!no_disp) o += up256(fs->px_o * 4 * batch);
     fs->o_lv = o;    if (flags & VPPX_FS_PATTERNS) o += up256(fs->img_s * batch);
     fs->o_rv = o;    if (flags & VPPX_FS_PATTERNS) o += up256(fs->img_s * batch);
     fs->o_conf = o;  if (flags & VPPX_FS_MASK) o += up256(fs->px_s * batch);
     fs->o_draws = o; o += up256((size_t)8 * batch);
+    fs->o_metrics = o; if (flags & VPPX_FS_METRICS) o += up256(sizeof(VppxMetrics) * batch);
+    fs->out_host_bytes = o;
+    if (no_disp) { // the device keeps the map (the metrics read it): behind everything that comes down
+        fs->o_disp = o;
+        o += up256(fs->px_o * 4 * batch);
+    }
     fs->out_bytes = o;
     fs->slots.resize(depth);
     auto fail = [&](const char *what, hipError_t e) {
@@ -193,7 +225,7 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     if ((e = hipStreamCreateWithPriority(&fs->s_out, hipStreamNonBlocking, prio_least)) != hipSuccess) return fail("hipStreamCreate", e);
     for (auto &s : fs->slots) {
         if ((e = hipHostMalloc((void **)&s.h_in, fs->in_bytes, hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc", e);
-        if ((e = hipHostMalloc((void **)&s.h_out, fs->out_bytes, hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc", e);
+        if ((e = hipHostMalloc((void **)&s.h_out, fs->out_host_bytes, hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc", e);
         if ((e = hipMalloc((void **)&s.d_in, fs->in_bytes)) != hipSuccess) return fail("hipMalloc", e);
         if ((e = hipMalloc((void **)&s.d_out, fs->out_bytes)) != hipSuccess) return fail("hipMalloc", e);
         if ((e = hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming)) != hipSuccess) return fail("hipEventCreate", e);
@@ -216,7 +248,7 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
 extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
                                    int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
 {
-    return fs_create(ctx, op, vp, rp, nullptr, batch, depth, H, W, C, flags, copy_threads, out);
+    return fs_create(ctx, op, vp, rp, nullptr, nullptr, false, batch, depth, H, W, C, flags, copy_threads, out);
 }
 
 extern "C" int vppx_fstream_create_scaled(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
@@ -224,7 +256,15 @@ extern "C" int vppx_fstream_create_scaled(vppx_ctx *ctx, const VppxOccParams *op
                                           vppx_fstream **out)
 {
     const bool unscaled = !sp || (sp->iscale == 1 && sp->oscale == 1);
-    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, batch, depth, H, W, C, flags, copy_threads, out);
+    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, nullptr, false, batch, depth, H, W, C, flags, copy_threads, out);
+}
+
+extern "C" int vppx_fstream_create_eval(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                        const VppxScaleParams *sp, const VppxEvalParams *ep, int batch, int depth, int H, int W, int C, int flags,
+                                        int copy_threads, vppx_fstream **out)
+{
+    const bool unscaled = !sp || (sp->iscale == 1 && sp->oscale == 1);
+    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, ep, true, batch, depth, H, W, C, flags, copy_threads, out);
 }
 
 extern "C" void vppx_fstream_destroy(vppx_fstream *fs) { fs_free(fs); }
@@ -240,9 +280,9 @@ extern "C" void vppx_fstream_destroy(vppx_fstream *fs) { fs_free(fs); }
 #define FS_COPY_WGS 8
 #endif
 struct FsCopySegs {
-    const uint4 *src[5];
-    uint4 *dst[5];
-    unsigned long long n16[5];
+    const uint4 *src[6];
+    uint4 *dst[6];
+    unsigned long long n16[6];
     int n;
 };
 __global__ void __launch_bounds__(256) fs_copy_out_kernel(FsCopySegs a)
@@ -271,13 +311,14 @@ static int fs_copy_out(vppx_fstream *fs, Slot &s, bool behind_last_aggregation)
         a.n16[a.n] = (bytes + 15) / 16;
         a.n++;
     };
-    seg(fs->o_disp, fs->px_o * 4 * nb);
+    if (!(fs->flags & VPPX_FS_NO_DISP)) seg(fs->o_disp, fs->px_o * 4 * nb);
     if (fs->flags & VPPX_FS_PATTERNS) {
         seg(fs->o_lv, fs->img_s * nb);
         seg(fs->o_rv, fs->img_s * nb);
     }
     if (fs->flags & VPPX_FS_MASK) seg(fs->o_conf, fs->px_s * nb);
     if (s.out_method_rnd) seg(fs->o_draws, (size_t)8 * nb);
+    if (fs->flags & VPPX_FS_METRICS) seg(fs->o_metrics, sizeof(VppxMetrics) * nb);
     fs_copy_out_kernel<<<FS_COPY_WGS, 256, 0, fs->s_out>>>(a);
     VPPX_HIP(hipGetLastError());
     VPPX_HIP(hipEventRecord(s.ev_out, fs->s_out));
@@ -309,6 +350,10 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gocc, s.h_in + fs->o_gocc, fs->px_s * nb, hipMemcpyHostToDevice, fs->s_in));
         if (fs->flags & VPPX_FS_GUIDED)
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_valid, s.h_in + fs->o_valid, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
+        if (fs->flags & VPPX_FS_METRICS) {
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gt, s.h_in + fs->o_gt, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_vgt, s.h_in + fs->o_vgt, fs->px * nb, hipMemcpyHostToDevice, fs->s_in));
+        }
         VPPX_HIP(hipEventRecord(s.ev_in, fs->s_in));
     }
     VppxVppParams vp = fs->vp;
@@ -324,7 +369,17 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         rc = vppx_inputs_ready_event(ctx, (void *)s.ev_in);
         if (rc) return rc;
         ctx->draws_dst = (vp.method == VPPX_METHOD_RND) ? (unsigned long long *)(s.d_out + fs->o_draws) : nullptr;
-        if (fs->scaled)
+        if (fs->flags & VPPX_FS_METRICS) {
+            // the batch and, behind its post stage on the launch stream, its metrics (a re-run queues them again with the batch):
+            // they read the ring's gt and one-byte validity planes, which the inputs event covers like the other inputs
+            rc = vppx_eval_call_internal(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, fs->scaled ? &fs->sp : nullptr, &fs->ep, nb, fs->H, fs->W,
+                                         fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
+                                         (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
+                                         (fs->flags & VPPX_FS_GUIDED) ? (const float *)(s.d_in + fs->o_valid) : nullptr,
+                                         (const float *)(s.d_in + fs->o_gt), s.d_in + fs->o_vgt, 1,
+                                         (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp), nullptr,
+                                         (VppxMetrics *)(s.d_out + fs->o_metrics), nullptr);
+        } else if (fs->scaled)
             rc = vppx_occ_vpp_rsgm_scaled_dev(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, &fs->sp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left,
                                               s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
                                               (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
@@ -389,13 +444,14 @@ static int fs_close_batch(vppx_fstream *fs)
 }
 
 static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ,
-                   const float *validhints, const char *name)
+                   const float *validhints, const float *gt, const float *validgt, const char *name)
 {
     if (!left || !right || !hints || (((fs->flags & VPPX_FS_GOCC) != 0) != (g_occ != nullptr))) {
         vppx_set_error("%s: left, right, hints%s", name, (fs->flags & VPPX_FS_GOCC) ? " and g_occ (VPPX_FS_GOCC)" : "; g_occ only with VPPX_FS_GOCC");
         return VPPX_E_INVALID_ARG;
     }
     if ((fs->flags & VPPX_FS_GUIDED) && !validhints) { vppx_set_error("%s: validhints is NULL", name); return VPPX_E_INVALID_ARG; }
+    if ((fs->flags & VPPX_FS_METRICS) && (!gt || !validgt)) { vppx_set_error("%s: gt and validgt are required", name); return VPPX_E_INVALID_ARG; }
     DevGuard g(fs->ctx->device);
     if (fs->fill_count >= fs->batch) {
         // the push that filled this batch could not submit it (its error was returned): submit it now, or take nothing -- a
@@ -410,12 +466,14 @@ static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, 
         return VPPX_E_INVALID_ARG;
     }
     const int i = fs->fill_count;
-    CopyJob jobs[5] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
+    CopyJob jobs[7] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
                        {s.h_in + fs->o_right + fs->img * i, right, fs->img},
                        {s.h_in + fs->o_hint + fs->px * 4 * i, hints, fs->px * 4},
                        {g_occ ? s.h_in + fs->o_gocc + fs->px_s * i : nullptr, g_occ, fs->px_s},
-                       {validhints ? s.h_in + fs->o_valid + fs->px * 4 * i : nullptr, validhints, fs->px * 4}};
-    fs->pool->copy(jobs, 5);
+                       {validhints ? s.h_in + fs->o_valid + fs->px * 4 * i : nullptr, validhints, fs->px * 4},
+                       {gt ? s.h_in + fs->o_gt + fs->px * 4 * i : nullptr, gt, fs->px * 4},
+                       {validgt ? s.h_in + fs->o_vgt + fs->px * i : nullptr, validgt, fs->px, 1}}; // validgt > 0 as one byte
+    fs->pool->copy(jobs, 7);
     fs->fill_count++;
     fs->pushed++;
     if (fs->fill_count == fs->batch) return fs_close_batch(fs);
@@ -425,22 +483,45 @@ static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, 
 extern "C" int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ)
 {
     if (!fs) { vppx_set_error("vppx_fstream_push: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_METRICS) {
+        vppx_set_error("vppx_fstream_push: the stream was created with VPPX_FS_METRICS; push frames with vppx_fstream_push_eval");
+        return VPPX_E_INVALID_ARG;
+    }
     if (fs->flags & VPPX_FS_GUIDED) {
         vppx_set_error("vppx_fstream_push: the stream was created with VPPX_FS_GUIDED; push frames with vppx_fstream_push_guided");
         return VPPX_E_INVALID_ARG;
     }
-    return fs_push(fs, left, right, hints, g_occ, nullptr, "vppx_fstream_push");
+    return fs_push(fs, left, right, hints, g_occ, nullptr, nullptr, nullptr, "vppx_fstream_push");
 }
 
 extern "C" int vppx_fstream_push_guided(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints,
                                         const uint8_t *g_occ, const float *validhints)
 {
     if (!fs) { vppx_set_error("vppx_fstream_push_guided: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_METRICS) {
+        vppx_set_error("vppx_fstream_push_guided: the stream was created with VPPX_FS_METRICS; push frames with vppx_fstream_push_eval");
+        return VPPX_E_INVALID_ARG;
+    }
     if (!(fs->flags & VPPX_FS_GUIDED)) {
         vppx_set_error("vppx_fstream_push_guided: the stream was created without VPPX_FS_GUIDED; push frames with vppx_fstream_push");
         return VPPX_E_INVALID_ARG;
     }
-    return fs_push(fs, left, right, hints, g_occ, validhints, "vppx_fstream_push_guided");
+    return fs_push(fs, left, right, hints, g_occ, validhints, nullptr, nullptr, "vppx_fstream_push_guided");
+}
+
+extern "C" int vppx_fstream_push_eval(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ,
+                                      const float *validhints, const float *gt, const float *validgt)
+{
+    if (!fs) { vppx_set_error("vppx_fstream_push_eval: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (!(fs->flags & VPPX_FS_METRICS)) {
+        vppx_set_error("vppx_fstream_push_eval: the stream was created without VPPX_FS_METRICS; push frames with vppx_fstream_push / _push_guided");
+        return VPPX_E_INVALID_ARG;
+    }
+    if (((fs->flags & VPPX_FS_GUIDED) != 0) != (validhints != nullptr)) {
+        vppx_set_error("vppx_fstream_push_eval: validhints %s", (fs->flags & VPPX_FS_GUIDED) ? "is NULL (VPPX_FS_GUIDED)" : "only with VPPX_FS_GUIDED");
+        return VPPX_E_INVALID_ARG;
+    }
+    return fs_push(fs, left, right, hints, g_occ, validhints, gt, validgt, "vppx_fstream_push_eval");
 }
 
 extern "C" int vppx_fstream_flush(vppx_fstream *fs)
@@ -505,13 +586,19 @@ static int fs_verify(vppx_fstream *fs, Slot &head)
     return VPPX_E_HIP; // (the message of the last check stands)
 }
 
-extern "C" int vppx_fstream_pop(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out,
-                                uint64_t *draws_out, int *got)
+static int fs_pop(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out, uint64_t *draws_out,
+                  VppxMetrics *metrics_out, bool eval_call, int *got)
 {
     if (!fs || !got) { vppx_set_error("vppx_fstream_pop: NULL argument"); return VPPX_E_INVALID_ARG; }
     *got = 0;
     if (fs->pop_batch == fs->sub_batches) return 0; // nothing submitted is outstanding (frames of an unfinished batch: vppx_fstream_flush)
-    if (!disp_out) { vppx_set_error("vppx_fstream_pop: disp_out is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_NO_DISP) {
+        if (disp_out) { vppx_set_error("vppx_fstream_pop: the stream was created with VPPX_FS_NO_DISP: disp_out must be NULL"); return VPPX_E_INVALID_ARG; }
+    } else if (!disp_out && !eval_call) {
+        vppx_set_error("vppx_fstream_pop: disp_out is NULL");
+        return VPPX_E_INVALID_ARG;
+    }
+    if (metrics_out && !(fs->flags & VPPX_FS_METRICS)) { vppx_set_error("vppx_fstream_pop_eval: the stream was created without VPPX_FS_METRICS"); return VPPX_E_INVALID_ARG; }
     if ((l_vpp_out || r_vpp_out) && !(fs->flags & VPPX_FS_PATTERNS)) { vppx_set_error("vppx_fstream_pop: the stream was created without VPPX_FS_PATTERNS"); return VPPX_E_INVALID_ARG; }
     if (conf_out && !(fs->flags & VPPX_FS_MASK)) { vppx_set_error("vppx_fstream_pop: the stream was created without VPPX_FS_MASK"); return VPPX_E_INVALID_ARG; }
     DevGuard g(fs->ctx->device);
@@ -527,10 +614,23 @@ extern "C" int vppx_fstream_pop(vppx_fstream *fs, float *disp_out, uint8_t *l_vp
                        {conf_out, s.h_out + fs->o_conf + fs->px_s * i, fs->px_s}};
     fs->pool->copy(jobs, 4);
     if (draws_out) *draws_out = fs->vp.method == VPPX_METHOD_RND ? ((const uint64_t *)(s.h_out + fs->o_draws))[i] : 0;
+    if (metrics_out) *metrics_out = ((const VppxMetrics *)(s.h_out + fs->o_metrics))[i];
     *got = 1;
     if (++fs->pop_idx == s.nb) {
         fs->pop_idx = 0;
         fs->pop_batch++;
     }
     return 0;
+}
+
+extern "C" int vppx_fstream_pop(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out,
+                                uint64_t *draws_out, int *got)
+{
+    return fs_pop(fs, disp_out, l_vpp_out, r_vpp_out, conf_out, draws_out, nullptr, false, got);
+}
+
+extern "C" int vppx_fstream_pop_eval(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out,
+                                     uint64_t *draws_out, VppxMetrics *metrics_out, int *got)
+{
+    return fs_pop(fs, disp_out, l_vpp_out, r_vpp_out, conf_out, draws_out, metrics_out, true, got);
 }

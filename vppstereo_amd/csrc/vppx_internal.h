@@ -132,6 +132,8 @@ enum WsSlot {
     WS_SCALE_DSMALL, // the disparities at the scaled shape, when the caller does not want them (the restore kernel reads them)
     WS_SCALE_TAB,    // index / weight tables of the resize and the restore (scale_tables)
     WS_SCALE_HOST_D, // vppx_occ_vpp_rsgm_scaled_host: device copy of disp_small
+    WS_METRICS_PART, // guided_metrics: one partial record per (frame, block) (metrics_kernels.hip)
+    WS_METRICS_OUT,  // vppx_guided_metrics_host: device copy of the result records
     WS_NUM
 };
 
@@ -271,6 +273,8 @@ struct vppx_ctx {
         VppxVppParams vp;
         VppxRsgmParams rp;
         const void *ptr[9];
+        const void *eval_ptr[4]; // gt, validgt, metrics_out, errormap of an evaluating call
+        int eval_scale[4];       // gt_scale, Hg, Wg, validgt is bytes
         VppxOccParams op;
         int has_op;
         void *stream;
@@ -297,6 +301,18 @@ struct vppx_ctx {
     const void *scale_tab_at = nullptr;
     int scale_parity = 0;
     hipEvent_t ev_scaled = nullptr;
+    // guided_metrics behind the running fused call (vppx_occ_vpp_rsgm_eval_dev, an evaluating frame stream): queued on the launch
+    // stream once the whole batch's map is complete -- behind the last part, inside a graph capture, behind the restore
+    struct EvalReq {
+        bool active = false;
+        bool after_restore = false; // the map the metrics read is the restored one: scaled_call queues them, not the hot path
+        const float *gt = nullptr;
+        const void *valid = nullptr;
+        int valid_is_u8 = 0;
+        int gt_scale = 1, Hg = 0, Wg = 0;
+        VppxMetrics *out = nullptr;
+        float *errormap = nullptr;
+    } eval;
 };
 
 int ws_reserve(vppx_ctx *ctx, WsSlot s, size_t bytes, void **out);
@@ -438,6 +454,15 @@ struct ScaleFrontArgs {
 int scale_launch_front(vppx_ctx *ctx, const ScaleFrontArgs &a);
 int scale_launch_restore(vppx_ctx *ctx, int B, int h, int w, int Ho, int Wo, const float *src, float *out, const int *ry,
                          const int *rx, int iscale, int oscale);
+
+// metrics_kernels.hip (losses.guided_metrics, losses.py:13-24)
+#define METRICS_PARTIAL_BYTES 64
+#define METRICS_MAX_BLOCKS 64
+int metrics_blocks_per_frame(size_t npx); // a function of the frame's shape only: results do not depend on the batch
+// gt / valid: [B, Hg, Wg] read at every gt_scale-th row and column, gt divided by gt_scale; valid: float32, or one byte per pixel
+// (valid_is_u8); partials: B * metrics_blocks_per_frame(Ho * Wo) records of METRICS_PARTIAL_BYTES; errormap may be null
+int metrics_launch(vppx_ctx *ctx, int B, int Ho, int Wo, const float *disp, int Hg, int Wg, int gt_scale, const float *gt,
+                   const void *valid, int valid_is_u8, void *partials, VppxMetrics *out, float *errormap);
 
 // occ_kernels (in vpp_kernels.hip)
 int occ_launch(vppx_ctx *ctx, int B, int H, int W, const float *hints, int rx, int ry, double l, double g,

@@ -102,7 +102,8 @@ class Engine:
         return out
 
     def vpp_rsgm(self, left, right, hints, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
-                 rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None, iscale=1, oscale=1, disp_small=None):
+                 rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None, iscale=1, oscale=1, disp_small=None,
+                 gt=None, validgt=None, metrics_out=None, errormap=None):
         """The whole hot path for a batch: one call, no host round trips, no synchronisation.
 
         g_occ: None, a uint8 [B,H,W] mask tensor, or -- test.py:154 with --maskocc in the same call --
@@ -116,11 +117,21 @@ class Engine:
         iscale / oscale: --iscale / --oscale (test.py:136-148, :247-248, vppx_occ_vpp_rsgm_scaled_dev).  The inputs keep their
         full shape [B,H,W(,C)]; the call runs at (h, w) = (H // iscale, W // iscale), so g_occ, occ_out, l_vpp and r_vpp are of
         that shape, and `out` is [B,Ho,Wo] (pipeline.scaled_shape).  disp_small: float32 [B,h,w] or None, the map before the
-        restore.  With the defaults the call is exactly the unscaled one."""
+        restore.  With the defaults the call is exactly the unscaled one.
+        gt / validgt: float32 [B,H,W] (the full frame shape) or None.  Given, the call also computes losses.guided_metrics of
+        its result on the device, behind the post stage on the same stream (vppx_occ_vpp_rsgm_eval_dev: test.py:136-252 in one
+        call), with gt_scale = oscale (test.py:150-152), and returns ``(out, metrics)``: metrics is a float64 [B,8] tensor, a
+        view of the VppxMetrics records (`guided_metrics`); metrics_out: such a tensor to write into; errormap: float32
+        [B,Ho,Wo] or None, receives the reference's error map.  Without gt the call is today's, and returns `out`."""
         torch = self.torch
         heuristic = isinstance(g_occ, (str, dict))
         if isinstance(g_occ, str) and g_occ != "occlusion_heuristic":
             raise ValueError("g_occ: expected a mask tensor, None, 'occlusion_heuristic' or a dict of its parameters")
+        if gt is not None or validgt is not None:
+            return self._vpp_rsgm_eval(left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out,
+                                       inputs_ready, validhints, int(iscale), int(oscale), disp_small, gt, validgt, metrics_out, errormap)
+        if metrics_out is not None or errormap is not None:
+            raise ValueError("metrics_out / errormap are outputs of the evaluating call: pass gt and validgt")
         if int(iscale) != 1 or int(oscale) != 1 or disp_small is not None:
             return self._vpp_rsgm_scaled(left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out,
                                          inputs_ready, validhints, int(iscale), int(oscale), disp_small)
@@ -198,6 +209,87 @@ class Engine:
                                                          None if heuristic else _ptr(g_occ), _ptr(validhints), _ptr(occ_out),
                                                          _ptr(l_vpp), _ptr(r_vpp), _ptr(out), _ptr(disp_small)))
         return out
+
+    def _metrics_tensor(self, B, metrics_out):
+        torch = self.torch
+        if metrics_out is None:
+            return torch.empty((B, 8), dtype=torch.float64, device=self.device)
+        self._chk(metrics_out, torch.float64, 2, "metrics_out", (B, 8))
+        return metrics_out
+
+    def guided_metrics(self, disp, gt, validgt, gt_scale=1, errormap=None, metrics_out=None):
+        """losses.guided_metrics (losses.py:13-24) for a batch on the device, no synchronisation (vppx_guided_metrics_dev).
+        disp: float32 [B,Ho,Wo]; gt, validgt: float32 [B,Hg,Wg] with (Hg // gt_scale, Wg // gt_scale) == (Ho, Wo): gt_scale is
+        --oscale (test.py:150-152: every gt_scale-th row and column, gt / gt_scale).  Returns a float64 [B,8] tensor, one
+        VppxMetrics record per frame: bad 1.0, 2.0, 3.0, 4.0, avgerr, rms, n_valid, reserved (`_lib.metrics_dict` names
+        them); a frame's record does not depend on the batch it is in.  errormap: float32 [B,Ho,Wo] or None."""
+        torch = self.torch
+        if gt is None or validgt is None:
+            raise ValueError("gt and validgt go together")
+        self._chk(disp, torch.float32, 3, "disp")
+        B, Ho, Wo = disp.shape
+        self._chk(gt, torch.float32, 3, "gt")
+        _, Hg, Wg = gt.shape
+        self._chk(gt, torch.float32, 3, "gt", (B, Hg, Wg))
+        self._chk(validgt, torch.float32, 3, "validgt", (B, Hg, Wg))
+        _lib.check_gt_shape(Hg, Wg, gt_scale, Ho, Wo)
+        if errormap is not None:
+            self._chk(errormap, torch.float32, 3, "errormap", (B, Ho, Wo))
+        m = self._metrics_tensor(B, metrics_out)
+        self._bind_stream()
+        ep = _lib.eval_params(gt_scale=int(gt_scale))
+        _lib.check(self.lib.vppx_guided_metrics_dev(self.ctx.handle, C.byref(ep), B, Ho, Wo, _ptr(disp), Hg, Wg, _ptr(gt), _ptr(validgt),
+                                                    _ptr(m), _ptr(errormap)))
+        return m
+
+    def _vpp_rsgm_eval(self, left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
+                       validhints, iscale, oscale, disp_small, gt, validgt, metrics_out, errormap):
+        torch = self.torch
+        if gt is None or validgt is None:
+            raise ValueError("gt and validgt go together")
+        self._chk(left, torch.uint8, 4, "left")
+        B, H, W, Cc = left.shape
+        if Cc not in (1, 3):
+            raise ValueError("left: channels must be 1 or 3")
+        self._chk(right, torch.uint8, 4, "right", left.shape)
+        self._chk(hints, torch.float32, 3, "hints", (B, H, W))
+        sp = _lib.scale_params(iscale=iscale, oscale=oscale)
+        h, w, Ho, Wo = _lib.scaled_shape(H, W, iscale, oscale)
+        self._chk(gt, torch.float32, 3, "gt", (B, H, W))
+        self._chk(validgt, torch.float32, 3, "validgt", (B, H, W))
+        _lib.check_gt_shape(H, W, oscale, Ho, Wo)
+        if g_occ is not None and not heuristic:
+            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
+        if validhints is not None:
+            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
+        if out is None:
+            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
+        if disp_small is not None:
+            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
+        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
+            if t is not None:
+                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
+        if occ_out is not None:
+            if not heuristic:
+                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
+            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
+        if errormap is not None:
+            self._chk(errormap, torch.float32, 3, "errormap", (B, Ho, Wo))
+        m = self._metrics_tensor(B, metrics_out)
+        self._bind_stream()
+        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
+        rp = _lib.rsgm_params(**(rsgm_kw or {}))
+        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
+        ep = _lib.eval_params(gt_scale=oscale)
+        if inputs_ready is not None:
+            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        _lib.check(self.lib.vppx_occ_vpp_rsgm_eval_dev(self.ctx.handle, C.byref(op) if heuristic else None, C.byref(vp), C.byref(rp),
+                                                       C.byref(sp), C.byref(ep), B, H, W, Cc, _ptr(left), _ptr(right), _ptr(hints),
+                                                       None if heuristic else _ptr(g_occ), _ptr(validhints), _ptr(gt), _ptr(validgt),
+                                                       _ptr(occ_out), _ptr(l_vpp), _ptr(r_vpp), _ptr(out), _ptr(disp_small), _ptr(m),
+                                                       _ptr(errormap)))
+        return out, m
 
     def occlusion_heuristic(self, hints, rx=9, ry=7, l=2, g=0.4375, th_conf=1, th_filter=0.1, out=None):
         torch = self.torch

@@ -45,7 +45,7 @@ def _scaled_hints(gt, iscale):
 
 
 def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw=None, rsgm_kw=None, return_patterns=False,
-              validhints=None, iscale=1, oscale=1):
+              validhints=None, iscale=1, oscale=1, gt=None, validgt=None, return_errormap=False):
     """left, right: uint8 [H,W,3] or [H,W]; hints: float [H,W] (0 = none).  maskocc: compute g_occ with the occlusion heuristic
     (test.py:154) -- else `g_occ` (uint8 [H,W] or None) is used as given.  vpp_kw: keywords of `vpp_standalone.vpp`
     (wsize, blending, c_occ, ...); rsgm_kw: keywords of `rsgm.compute_rsgm` (dmax, p1, ...).  validhints: float [H,W] or None;
@@ -53,13 +53,23 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
     validhints > 0.  Returns the float32 disparity map, or (disparity, left_vpp, right_vpp, conf_map or None) with
     return_patterns.  iscale / oscale: --iscale / --oscale (test.py:136-148, :247-248): the full-size frame is resized on the
     device, the call runs at (h, w) = (H // iscale, W // iscale) -- g_occ and the returned patterns and mask have that shape --
-    and the map comes back at (Ho, Wo) (`scaled_shape`)."""
+    and the map comes back at (Ho, Wo) (`scaled_shape`).
+    gt / validgt: float [H,W] (the full frame shape) or None.  Given, the frame's evaluation metrics (losses.guided_metrics,
+    test.py:251-252, with the --oscale decimation of the ground truth, test.py:150-152) are computed on the device and the call
+    returns ``(result_as_above, metrics)``: a dict with the reference's keys 'bad 1.0' ... 'bad 4.0', 'avgerr', 'rms' (floats),
+    plus 'errormap' (float32 [Ho,Wo]) with return_errormap."""
     vk = dict(vpp_kw or {})
     method = vk.pop("method", "rnd")
     assert method in ["rnd", "maxDistance"]
+    evaluate = gt is not None or validgt is not None
+    if evaluate and (gt is None or validgt is None):
+        raise ValueError("gt and validgt go together")
+    if return_errormap and not evaluate:
+        raise ValueError("return_errormap needs gt and validgt")
+    gt_eval, vgt_eval = gt, validgt
     left = np.ascontiguousarray(left, np.uint8)
     right = np.ascontiguousarray(right, np.uint8)
-    gt = np.ascontiguousarray(np.asarray(hints, dtype=np.float32))
+    gt = np.ascontiguousarray(np.asarray(hints, dtype=np.float32))   # (the hints: `g` / `gt` of vpp_core_opt.pyx:53)
     if left.shape != right.shape or left.shape[:2] != gt.shape:
         raise ValueError("left, right and hints must agree in height and width")
     vh = None
@@ -71,6 +81,12 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
     scaled = (iscale, oscale) != (1, 1)
     H, W = gt.shape
     h, w, Ho, Wo = scaled_shape(H, W, iscale, oscale) if scaled else (H, W, H, W)
+    if evaluate:
+        gt_eval = np.ascontiguousarray(np.asarray(gt_eval, dtype=np.float32))
+        vgt_eval = np.ascontiguousarray(np.asarray(vgt_eval, dtype=np.float32))
+        if gt_eval.shape != (H, W) or vgt_eval.shape != (H, W):
+            raise ValueError(f"gt, validgt: expected shape {(H, W)}, got {gt_eval.shape}, {vgt_eval.shape}")
+        _lib.check_gt_shape(H, W, oscale, Ho, Wo)
     ch = 1 if left.ndim == 2 else left.shape[2]
     dmin, dmax = hint_range(_scaled_hints(gt, iscale) if iscale != 1 else gt)
     no_hints = dmin is None
@@ -121,7 +137,18 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
         raise Exception(str(e)) from e   # the reference raises bare Exception(msg) (rsgm.py:31-40,166)
     if method == "rnd":
         _lib.check(lib.vppx_rand_advance(ctx.handle, int(draws[0])))
-    return (disp, lc, rc, conf) if return_patterns else disp
+    result = (disp, lc, rc, conf) if return_patterns else disp
+    if not evaluate:
+        return result
+    rec = _lib.VppxMetrics()
+    emap = np.empty((Ho, Wo), np.float32) if return_errormap else None
+    ep = _lib.eval_params(gt_scale=oscale)
+    _lib.check(lib.vppx_guided_metrics_host(ctx.handle, C.byref(ep), 1, Ho, Wo, _lib.np_ptr(disp), H, W, _lib.np_ptr(gt_eval),
+                                            _lib.np_ptr(vgt_eval), C.byref(rec), _lib.np_ptr(emap)))
+    metrics = _lib.metrics_dict(rec)
+    if return_errormap:
+        metrics['errormap'] = emap
+    return result, metrics
 
 
 class FrameStream:
@@ -147,10 +174,20 @@ class FrameStream:
     `run_frame(..., validhints=...)` with seed + f.
     iscale / oscale: --iscale / --oscale (test.py:136-148, :247-248): pushes take full-size frames (and, with_g_occ, masks of the
     scaled shape); disparities come back at (Ho, Wo), patterns and mask at (h, w) (`scaled_shape`), and frame f equals
-    `run_frame(..., iscale=, oscale=)` with seed + f.  batch=None then takes the batch quantum of the scaled shape."""
+    `run_frame(..., iscale=, oscale=)` with seed + f.  batch=None then takes the batch quantum of the scaled shape.
+    metrics=True: an evaluating stream (test.py:251-252).  Frames go in through ``push_eval``, which also brings the frame's ground
+    truth, ``gt=`` and ``validgt=`` (float [H,W], the full frame shape; > 0 is valid), the metrics of every batch are computed on the device behind its kernels
+    (with the --oscale decimation of test.py:150-152) and each result becomes ``(result_as_above, metrics)`` -- metrics: the
+    dict of `run_frame`, without an error map; `last_metrics_record` holds the popped frame's eight doubles (VppxMetrics).
+    return_disp=False (needs metrics=True): the disparity maps stay on the device and each result is the metrics dict alone."""
 
     def __init__(self, height, width, channels=3, batch=None, depth=3, seed=1, maskocc=False, with_g_occ=False, occ_kw=None,
-                 vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1, guided=False, iscale=1, oscale=1):
+                 vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1, guided=False, iscale=1, oscale=1,
+                 metrics=False, return_disp=True):
+        if not return_disp and not metrics:
+            raise ValueError("return_disp=False needs metrics=True (a stream that returns nothing)")
+        if not return_disp and return_patterns:
+            raise ValueError("return_disp=False returns the metrics alone: not with return_patterns")
         vk = dict(vpp_kw or {})
         method = vk.pop("method", "rnd")
         assert method in ["rnd", "maxDistance"]
@@ -177,6 +214,9 @@ class FrameStream:
         else:
             self.hs, self.ws, self.ho, self.wo = self.h, self.w, self.h, self.w
         self._shape_s = (self.hs, self.ws) if self.ch == 1 else (self.hs, self.ws, self.ch)
+        self._metrics, self._return_disp = bool(metrics), bool(return_disp)
+        if self._metrics:
+            _lib.check_gt_shape(self.h, self.w, self.oscale, self.ho, self.wo)
         self._ctx = _lib.Context(device)
         if batch is None:
             batch = int(self._lib.vppx_batch_quantum(self._ctx.handle, self.hs, self.ws, int(rp.dmax))) or 16
@@ -185,9 +225,17 @@ class FrameStream:
         self._guided = bool(guided)
         flags = (_lib.FS_PATTERNS if self._patterns else 0) | (_lib.FS_MASK if self._mask else 0) | (_lib.FS_GOCC if self._gocc else 0)
         flags |= _lib.FS_GUIDED if self._guided else 0
+        flags |= (_lib.FS_METRICS if self._metrics else 0) | (0 if self._return_disp else _lib.FS_NO_DISP)
         self._h = C.c_void_p()
+        self.last_metrics_record = None
         try:
-            if self._scaled:
+            if self._metrics:
+                ep = _lib.eval_params(gt_scale=self.oscale)
+                _lib.check(self._lib.vppx_fstream_create_eval(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p),
+                                                              C.byref(rp), C.byref(sp) if self._scaled else None, C.byref(ep), self.batch,
+                                                              self.depth, self.h, self.w, self.ch, flags, int(copy_threads),
+                                                              C.byref(self._h)))
+            elif self._scaled:
                 _lib.check(self._lib.vppx_fstream_create_scaled(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p),
                                                                 C.byref(rp), C.byref(sp), self.batch, self.depth, self.h, self.w, self.ch,
                                                                 flags, int(copy_threads), C.byref(self._h)))
@@ -233,7 +281,22 @@ class FrameStream:
     def push(self, left, right, hints, g_occ=None, validhints=None):
         """One frame in (copied before the call returns).  The frame that completes a batch submits it; if that submit fails
         the push raises but HAS taken the frame, and the next push or `flush()` submits the batch again.  validhints: float
-        [H,W], required on a guided stream and refused on any other."""
+        [H,W], required on a guided stream and refused on any other.  A metrics=True stream takes its frames through
+        `push_eval`."""
+        if self._metrics:
+            raise ValueError("the stream was created with metrics=True: every push brings gt and validgt (push_eval)")
+        self._push(left, right, hints, g_occ, validhints, None, None)
+
+    def push_eval(self, left, right, hints, g_occ=None, validhints=None, gt=None, validgt=None):
+        """`push` on a metrics=True stream (vppx_fstream_push_eval): the frame and its ground truth, gt and validgt, float [H,W]
+        at the full frame shape (validgt > 0 is valid).  Refused on any other stream."""
+        if not self._metrics:
+            raise ValueError("gt / validgt given but the stream was created without metrics=True")
+        if gt is None or validgt is None:
+            raise ValueError("the stream was created with metrics=True: every push brings gt and validgt")
+        self._push(left, right, hints, g_occ, validhints, gt, validgt)
+
+    def _push(self, left, right, hints, g_occ, validhints, gt, validgt):
         left = self._arr(left, np.uint8, self._shape, "left")
         right = self._arr(right, np.uint8, self._shape, "right")
         hints = self._arr(hints, np.float32, (self.h, self.w), "hints")
@@ -253,6 +316,9 @@ class FrameStream:
             vh = self._arr(validhints, np.float32, (self.h, self.w), "validhints")
         elif validhints is not None:
             raise ValueError("validhints given but the stream was created without guided=True")
+        if self._metrics:
+            gt = self._arr(gt, np.float32, (self.h, self.w), "gt")
+            validgt = self._arr(validgt, np.float32, (self.h, self.w), "validgt")
         # a full batch whose submit failed (an earlier push raised, having taken its frame): submit it before anything else --
         # raises again, and takes nothing, if it still fails
         if self._fill == self.batch:
@@ -263,7 +329,11 @@ class FrameStream:
                 self._early.append(self._pop_native())
         try:
             occ_p = occ.ctypes.data if occ is not None else None
-            if vh is not None:
+            if self._metrics:
+                _lib.check(self._lib.vppx_fstream_push_eval(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data, occ_p,
+                                                            vh.ctypes.data if vh is not None else None, gt.ctypes.data,
+                                                            validgt.ctypes.data))
+            elif vh is not None:
                 _lib.check(self._lib.vppx_fstream_push_guided(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data, occ_p,
                                                               vh.ctypes.data))
             else:
@@ -292,7 +362,8 @@ class FrameStream:
 
     # ---- one frame out ----
     def _pop_native(self):
-        disp = np.empty((self.ho, self.wo), np.float32)
+        disp = np.empty((self.ho, self.wo), np.float32) if self._return_disp else None
+        rec = _lib.VppxMetrics() if self._metrics else None
         lc = rc = conf = None
         if self._patterns:
             lc, rc = np.empty(self._shape_s, np.uint8), np.empty(self._shape_s, np.uint8)
@@ -300,9 +371,16 @@ class FrameStream:
             conf = np.empty((self.hs, self.ws), np.uint8)
         draws, got = C.c_uint64(0), C.c_int(0)
         try:
-            _lib.check(self._lib.vppx_fstream_pop(self._h, disp.ctypes.data, lc.ctypes.data if lc is not None else None,
-                                                  rc.ctypes.data if rc is not None else None, conf.ctypes.data if conf is not None else None,
-                                                  C.byref(draws), C.byref(got)))
+            if self._metrics:
+                _lib.check(self._lib.vppx_fstream_pop_eval(self._h, disp.ctypes.data if disp is not None else None,
+                                                           lc.ctypes.data if lc is not None else None,
+                                                           rc.ctypes.data if rc is not None else None,
+                                                           conf.ctypes.data if conf is not None else None, C.byref(draws), C.byref(rec),
+                                                           C.byref(got)))
+            else:
+                _lib.check(self._lib.vppx_fstream_pop(self._h, disp.ctypes.data, lc.ctypes.data if lc is not None else None,
+                                                      rc.ctypes.data if rc is not None else None, conf.ctypes.data if conf is not None else None,
+                                                      C.byref(draws), C.byref(got)))
         except _lib.VppxError as e:
             raise Exception(str(e)) from e
         if not got.value:
@@ -311,7 +389,13 @@ class FrameStream:
         self._inflight[0] -= 1
         if self._inflight[0] == 0:
             self._inflight.pop(0)
-        return ((disp, lc, rc, conf) if self._patterns else disp), int(draws.value)
+        res = (disp, lc, rc, conf) if self._patterns else disp
+        if self._metrics:
+            record = np.array([rec.bad1, rec.bad2, rec.bad3, rec.bad4, rec.avgerr, rec.rms, rec.n_valid, rec.reserved], np.float64)
+            md = _lib.metrics_dict(rec)
+            res = (res, md) if self._return_disp else md
+            return res, int(draws.value), record
+        return res, int(draws.value), None
 
     def pop(self):
         """The next result in input order (waits for its batch), or None when nothing submitted is outstanding."""
@@ -319,6 +403,7 @@ class FrameStream:
         if r is None:
             return None
         self.last_draws = r[1]
+        self.last_metrics_record = r[2]
         return r[0]
 
     @property
@@ -334,9 +419,10 @@ class FrameStream:
 
     def run(self, frames):
         """Generator: results for an iterable of (left, right, hints[, g_occ]) in input order -- on a guided stream
-        (left, right, hints, g_occ or None, validhints) -- keeps about `depth` batches in flight."""
+        (left, right, hints, g_occ or None, validhints); on a metrics=True stream the two extra entries gt, validgt come at
+        the end: (left, right, hints, g_occ or None, validhints or None, gt, validgt) -- keeps about `depth` batches in flight."""
         for fr in frames:
-            self.push(*fr)
+            (self.push_eval if self._metrics else self.push)(*fr)
             # whole batches that must be complete by now: everything but the last depth - 1 submitted ones
             while self._early:
                 yield self.pop()
