@@ -550,6 +550,25 @@ int vppx_we_last_pieces(vppx_ctx *ctx);
  * children of VPPX_SUBSTREAMS keep lists of their own, which are not merged: a call split over them lists nothing.
  * Writes at most n - 1 characters and a NUL to buf (buf may be NULL when n == 0); returns the length of the whole list. */
 int vppx_last_routes(vppx_ctx *ctx, char *buf, int n);
+/* The same for the front stage -- the occlusion heuristic, the virtual pattern projection and the bilateral filling -- in a
+ * list of its own (vppx_last_routes never names these): every kernel the last call launched from that stage, with its
+ * template arguments and the host decisions that select a code path inside it, distinct names in launch order.  Names:
+ * occ_warp4 | occ_warp, occ_test<NJ,PT> (NJ = 1..4 window rounds of 64 positions, 0 = any; PT = 4 or, next to a sum / WTA
+ * kernel that leaves less than 12 KB of LDS, 2 pixels per thread), occ_dmap (the filtered map); hint_range,
+ * compact<dist|plain>, rowscan, rand; l_bits<NW,ROWS> (first L pass: window width 1 / 3 / 5 / 7, rows per block 4 or 1),
+ * l_heavy<NW> (second L pass: pixels with an occluded hint in their window), l_wide (wsize >= 9); r_rows<u16|u32,mode=M,seg=N>,
+ * one entry per launch (mode 1 = apply, 2 = build the hint lists, 3 = both; N column segments per row);
+ * vpp_order<independent|late|inplace,side|main> (the launch order: the sides do not depend on each other / the original right
+ * image is kept and the L passes that replay it come last / R is patterned in place, so mode 2 comes first and mode 1 last; and
+ * whether the L side ran on the side stream); maxdist_wave | maxdist_lds | maxdist_global; gray_ctx, bilateral_fill.
+ * The list is cleared at the entry of every call that can launch one of these kernels: vppx_vpp_dev / _host and the two
+ * vppx_virtual_projection_scan_* built on them, vppx_occlusion_heuristic_* (all four), vppx_vpp_rsgm_dev, vppx_occ_vpp_rsgm_*
+ * (guided, scaled, evaluating or not, _dev and _host) and with them every batch of a frame stream.  A call that runs in parts
+ * lists the union over its parts.  A graph replay (vppx_set_graph_mode) reports what the captured call recorded.  The children
+ * of VPPX_SUBSTREAMS keep lists of their own, which are not merged: a call split over them lists nothing, as in
+ * vppx_last_routes.  Same calling convention: writes at most n - 1 characters and a NUL to buf (buf may be NULL when n == 0),
+ * returns the length of the whole list; VPPX_E_INVALID_ARG on a bad buffer. */
+int vppx_last_front_routes(vppx_ctx *ctx, char *buf, int n);
 /* Per-stage hipEvent timing of the last vppx_vpp_rsgm_dev/vppx_rsgm_dev call when stage
  * timing is enabled: fills ms[0..n) and returns the number of stages; names via
  * vppx_stage_name(i). */

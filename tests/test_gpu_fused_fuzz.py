@@ -194,12 +194,23 @@ def _env_engine(**env):
                 os.environ[k] = v
 
 
-# (engine environment, B, H, W, occlusion parameters): what the front stage of a PIPELINED call at dmax = 256 picks when the
-# previous call's sum / WTA kernel leaves little LDS (vpp_rsgm_one: front_lds_budget; vpp_kernels.hip: occ_test_kernel<NJ, 2>,
-# apply_l_bits_kernel<NW, 1>, r_rows_kernel in column segments).  Fewer than 6 frames: 8-path layout, uniform ring of 153 KB,
-# 6.5 KB left -> the small variants, rows of 450 / 333 / 211 columns = 3 / 2 / 2 segments of unequal width; 8 frames with
-# sum_trap1 / sum_trap0 (trapezoid ring without spare slots: 42 KB left, uniform ring: 6.5 KB): the fused layout's budgets;
-# the default (spare slots: nothing fits next to the kernel, the front stage keeps its stand-alone shapes).
+# (engine environment, B, H, W, occlusion parameters): what the front stage of a PIPELINED call at dmax = 256 picks
+# when the previous call's sum / WTA kernel leaves little LDS (vpp_rsgm_one: front_lds_budget; vpp_kernels.hip:
+# occ_test_kernel<NJ, 2>, apply_l_bits_kernel<NW, 1>, r_rows_kernel in column segments).  Fewer than 6 frames: 8-path layout,
+# uniform ring of 153 KB, 6592 bytes left -> the small variants, rows of 450 / 333 / 211 columns = 2 / 2 / 1 segments of at most
+# 253 columns; 8 frames with sum_trap1 / sum_trap0 (trapezoid ring without spare slots: 42 KB left, uniform ring: 6592 bytes):
+# the fused layout's budgets; the default (spare slots: nothing runs next to the kernel, the front stage keeps its stand-alone
+# shapes).  The routes are those of Engine.last_front_routes() (tests/test_gpu_vpp_routes.py holds the table).
+def _front(warp, nj, pt, seg):
+    return [warp, f"occ_test<{nj},{pt}>", "compact<plain>", "rowscan", "rand", "vpp_order<late,side>", "l_bits<3,1>",
+            f"r_rows<u16,mode=3,seg={seg}>", "l_heavy<3>"]
+
+
+# by (frames, width) of the cases below
+_FRONT_AT_D256 = {(3, 450): _front("occ_warp", 2, 2, 2), (5, 333): _front("occ_warp", 4, 2, 2), (2, 211): _front("occ_warp", 0, 2, 1),
+                  (8, 1500): _front("occ_warp4", 2, 4, 1), (8, 420): _front("occ_warp4", 4, 2, 2), (8, 300): _front("occ_warp4", 2, 4, 1)}
+
+
 @pytest.mark.parametrize("env,B,H,W,occ", [
     (dict(), 3, 20, 450, dict()),
     (dict(), 5, 14, 333, dict(rx=17, ry=13, th_filter=0.5)),       # 238 window positions: occ_test_kernel<4, 2>
@@ -233,6 +244,7 @@ def test_pipelined_front_stage_at_d256_matches_unpipelined_and_oracle(env, B, H,
     eng.synchronize()
     if "VPPX_VERT" in env:
         assert eng.uses_vert() == 3
+    assert sorted(eng.last_front_routes()) == sorted(_FRONT_AT_D256[(B, W)]), eng.last_front_routes()
     for s in range(3):
         occ_o = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
         lv = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)

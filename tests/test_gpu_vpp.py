@@ -27,6 +27,19 @@ def gpu():
     return vpp_core_opt
 
 
+def _assert_maxdist_route(direction, wsize, agg_y, W):
+    """Which of the three maxDistance kernels the scan that just ran on the default context took (vppx_last_front_routes): the
+    row-wavefront kernel by default for left-to-right scans, the LDS ring for right-to-left ones, and what VPPX_VARIANT
+    maxdist_lds / maxdist_global force (test_gpu_variants.py runs these tests under both)."""
+    from vppstereo_amd import _lib
+    rad = (wsize - 1) // 2 + (agg_y - 1) // 2
+    assert rad <= 15 and 64 * W <= 132 * 1024 and 2 * (2 * rad + 1) * W <= 60 * 1024   # small enough for each of the three
+    variant = os.environ.get("VPPX_VARIANT", "")
+    want = "maxdist_global" if "maxdist_global" in variant else ("maxdist_lds" if "maxdist_lds" in variant or not direction else "maxdist_wave")
+    got = [r for r in _lib.last_front_routes(_lib.load(), _lib.default_context().handle) if r.startswith("maxdist")]
+    assert got == [want], (got, want, direction, rad, W)
+
+
 def test_device_glibc_rand_stream_matches_fixture_and_libc():
     from vppstereo_amd import _lib
     lib, ctx = _lib.load(), _lib.default_context()
@@ -77,6 +90,7 @@ def test_maxdist_golden_cases_bit_exact(gpu):
     bad = []
     for case in cases:
         n, l, r = run_case(gpu, case, store)
+        _assert_maxdist_route(case["direction"], case["wsize"], case["agg_y"], l.shape[1])
         ok = n == case["n_hints"] and np.array_equal(l, store[case["name"] + "_l"]) and \
             np.array_equal(r, store[case["name"] + "_r"])
         if not ok:
@@ -107,6 +121,7 @@ def test_maxdist_vs_oracle_random_inputs(gpu):
                                                          occ, discard, interp)
             n1 = gpu.virtual_projection_scan_max_dist(a1, b1, g, W, H, C, uniform, wsize, ax, ay, direction, c, c_occ, occ,
                                                       discard, interp)
+            _assert_maxdist_route(direction, wsize, ay, W)
             cfg = dict(uniform=uniform, direction=direction, interp=interp, discard=discard, wsize=wsize, ax=ax, ay=ay)
             assert n0 == n1, cfg
             assert np.array_equal(a0, a1), (cfg, int((a0 != a1).sum()))
@@ -120,6 +135,7 @@ def test_maxdist_full_size_anchor_hash(gpu, anchors):
     c = {c["name"]: c for c in meta["cases"]}["maxdist_occ1"]
     a, b = l.copy(), r.copy()
     n = gpu.virtual_projection_scan_max_dist(a, b, g, W, H, 3, False, 3, 64, 3, 1, 0.4, 0.0, occ1, False, True)
+    _assert_maxdist_route(1, 3, 3, W)
     assert n == c["n_hints"] and _sha(a) == c["l"] and _sha(b) == c["r"]
 
 

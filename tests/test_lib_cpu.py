@@ -174,3 +174,23 @@ def test_route_query_is_exported_declared_and_bound():
         "paths<8,24,exact,guided,u16,dirs=ff>", "sum_lr<12,u16,8,64,spare,nosw4,general,16,partw>", "wta_right_t"]
     assert _lib.split_routes("") == []
     assert re.search(r"VPPX_GUIDED_PART_MB\s", hdr)
+
+
+def test_front_route_query_is_exported_declared_and_bound():
+    """vppx_last_front_routes, the twin of vppx_last_routes for the front stage: declared with its signature, exported, bound in
+    Python (_lib.last_front_routes, Engine.last_front_routes); a NULL context fails with -7 and a message; its names split at the
+    commas outside <> like the others."""
+    import inspect
+    from vppstereo_amd import engine
+    lib = _lib.load()
+    hdr = open(os.path.join(ROOT, "include", "vppx.h")).read()
+    assert "int vppx_last_front_routes(vppx_ctx *ctx, char *buf, int n);" in hdr
+    assert "vppx_last_front_routes" in _lib.EXPORTS and hasattr(lib, "vppx_last_front_routes")
+    assert lib.vppx_last_front_routes.argtypes == [C.c_void_p, C.c_char_p, C.c_int]
+    assert callable(_lib.last_front_routes)
+    assert list(inspect.signature(engine.Engine.last_front_routes).parameters) == ["self"]
+    buf = C.create_string_buffer(8)
+    assert lib.vppx_last_front_routes(C.c_void_p(), buf, 8) == -7 and b"context is NULL" in lib.vppx_last_error()
+    assert lib.vppx_last_front_routes(C.c_void_p(), None, 0) == -7
+    assert _lib.split_routes("occ_warp4,occ_test<2,4>,compact<plain>,vpp_order<late,side>,r_rows<u16,mode=3,seg=2>") == [
+        "occ_warp4", "occ_test<2,4>", "compact<plain>", "vpp_order<late,side>", "r_rows<u16,mode=3,seg=2>"]

@@ -45,6 +45,7 @@ __host__ __device__ inline int vpp_bits_words(int W) { return (W + 63) / 64 + 2;
 struct VppK {
     int B, H, W, C;
     int n, direction, uniform, discard, interp, use_dist, use_bil;
+    int wsize_m1;        // patch_size - 1 of the distance patch (vpp_standalone.py:9): 2n for an odd wsize, 2n + 1 for an even one
     float c, c_occ, dmin, dmax;
     const float2 *range; // use_distance_patch with per_frame_range: [B] {dmin, dmax} of every frame's own hints (hint_range_kernel), else null
     double inv_gamma;
@@ -87,7 +88,7 @@ __device__ __forceinline__ int patch_radius(const VppK &k, int f, float gv)
     const float den = __fsub_rn(dmax, dmin);
     const float ratio = __fdiv_rn(num, den);
     const double gw = pow((double)ratio, k.inv_gamma);
-    const double ws = rint(__dadd_rn(__dmul_rn(gw, (double)(2 * k.n)), 1.0)); // patch_size-1 == 2n for odd wsize
+    const double ws = rint(__dadd_rn(__dmul_rn(gw, (double)k.wsize_m1), 1.0));
     long long wsize = (long long)ws;
     long long a = wsize - 1;
     long long nn = a >= 0 ? a / 2 : -((-a + 1) / 2);
@@ -1842,6 +1843,7 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
     VppK k;
     k.B = g.B; k.H = g.H; k.W = g.W; k.C = g.C;
     k.n = (p.wsize - 1) / 2;
+    k.wsize_m1 = p.wsize - 1;
     k.direction = p.direction != 0;
     k.uniform = p.uniform_color != 0;
     k.discard = p.discard_occluded != 0;
@@ -1870,6 +1872,7 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
         float2 *range;
         if ((rc = ws_get(ctx, WS_HINT_RANGE, (size_t)g.B, &range))) return rc;
         hint_range_kernel<<<dim3(g.B), 1024, 0, ctx->stream>>>(gmap, (size_t)g.H * g.W, range);
+        front_route_note(ctx, "hint_range");
         VPPX_CHECK_LAUNCH();
         k.range = range;
     }
@@ -1882,8 +1885,10 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
         if (k.use_dist) compact_kernel<true><<<dim3((g.H + 3) / 4, g.B), 256, 0, ctx->stream>>>(k);
         else compact_kernel<false><<<dim3((g.H + 3) / 4, g.B), 256, 0, ctx->stream>>>(k);
         VPPX_CHECK_LAUNCH();
+        front_route_note(ctx, "compact<%s>", k.use_dist ? "dist" : "plain");
         rowscan_kernel<<<dim3(g.B), 256, 0, ctx->stream>>>(k, (long long *)n_hints_dev);
         VPPX_CHECK_LAUNCH();
+        front_route_note(ctx, "rowscan");
         stage_mark(ctx, ST_VPP_COMPACT);
         MdK m;
         m.k = k;
@@ -1903,10 +1908,13 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
                 attr_set[ctx->device & (VPPX_MAX_DEVICES - 1)] = true;
             }
             maxdist_wave_kernel<<<dim3(g.B * g.C), 64 * MD_NW, lds_wave, ctx->stream>>>(m, rad);
+            front_route_note(ctx, "maxdist_wave");
         } else if (lds <= 60 * 1024 && md != 2) {
             maxdist_lds_kernel<<<dim3(g.B * g.C), 64, lds, ctx->stream>>>(m, rad);
+            front_route_note(ctx, "maxdist_lds");
         } else {
             maxdist_kernel<<<dim3(g.B * g.C), 64, 0, ctx->stream>>>(m);
+            front_route_note(ctx, "maxdist_global");
         }
         VPPX_CHECK_LAUNCH();
         stage_mark(ctx, ST_VPP_APPLY);
@@ -1926,12 +1934,15 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
     if (k.use_dist) compact_kernel<true><<<dim3((g.H + 3) / 4, g.B), 256, 0, ctx->stream>>>(k);
         else compact_kernel<false><<<dim3((g.H + 3) / 4, g.B), 256, 0, ctx->stream>>>(k);
     VPPX_CHECK_LAUNCH();
+    front_route_note(ctx, "compact<%s>", k.use_dist ? "dist" : "plain");
     rowscan_kernel<<<dim3(g.B), 256, 0, ctx->stream>>>(k, (long long *)n_hints_dev);
     VPPX_CHECK_LAUNCH();
+    front_route_note(ctx, "rowscan");
     stage_mark(ctx, ST_VPP_COMPACT);
     rand_kernel<<<dim3((nblk + 63) / 64, g.B), 64, 0, ctx->stream>>>(rnd, cap, k.frame_tot, seeds_dev, p.seed,
                                                                       qoff_for(p.rand_offset), tab, nblk);
     VPPX_CHECK_LAUNCH();
+    front_route_note(ctx, "rand");
     stage_mark(ctx, ST_VPP_RAND);
     const int npairs = ((g.W + 255) / 256) * g.H; // (apply_l_wide_kernel: a bounded grid per frame, strided)
     dim3 grid((unsigned)(npairs < 1024 ? npairs : 1024), g.B);
@@ -1956,7 +1967,8 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
         // (with a mask that does not discard them: two_pass), and otherwise there are none to act on.
         const bool r4 = (long long)g.B * g.H >= 4 * 1024 && ctx->front_lds_budget >= 18 * 1024; // (17 KB of LDS against 4.5)
         const dim3 bg((unsigned)((g.W + 1023) / 1024), (unsigned)(r4 ? (g.H + 3) / 4 : g.H), (unsigned)g.B);
-#define LB(NW) do { if (r4) apply_l_bits_kernel<NW, 4><<<bg, 256, 0, st>>>(k); else apply_l_bits_kernel<NW, 1><<<bg, 256, 0, st>>>(k); } while (0)
+#define LB(NW) do { if (r4) apply_l_bits_kernel<NW, 4><<<bg, 256, 0, st>>>(k); else apply_l_bits_kernel<NW, 1><<<bg, 256, 0, st>>>(k); \
+                    front_route_note(ctx, "l_bits<%d,%d>", NW, r4 ? 4 : 1); } while (0)
         switch (k.n) {
         case 0: LB(1); break;
         case 1: LB(3); break;
@@ -1968,10 +1980,12 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
     auto launch_l_heavy = [&](hipStream_t st) {
         const dim3 hg((unsigned)(g.B * 512 < 32768 ? g.B * 512 : 32768)); // (about one deferred pixel per pair of lanes at 3 % hints: the replays are latency chains)
         switch (k.n) {
-        case 0: apply_l_heavy_kernel<1><<<hg, 64, 0, st>>>(k); break;
-        case 1: apply_l_heavy_kernel<3><<<hg, 64, 0, st>>>(k); break;
-        case 2: apply_l_heavy_kernel<5><<<hg, 64, 0, st>>>(k); break;
-        default: apply_l_heavy_kernel<7><<<hg, 64, 0, st>>>(k); break;
+#define LH(NW) do { apply_l_heavy_kernel<NW><<<hg, 64, 0, st>>>(k); front_route_note(ctx, "l_heavy<%d>", NW); } while (0)
+        case 0: LH(1); break;
+        case 1: LH(3); break;
+        case 2: LH(5); break;
+        default: LH(7); break;
+#undef LH
         }
     };
     // R side: r_rows_kernel, a block per row of up to 2048 columns (45 KB of LDS with 16-bit list entries), per part of at
@@ -1991,6 +2005,11 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
     auto launch_r_rows = [&](int mode) {
         if (wide_ids) r_rows_kernel<u32, 16, RR_NT><<<dim3(g.H * rr_nseg, g.B), RR_NT, rows_lds, ctx->stream>>>(k, mode, rr_sw);
         else r_rows_kernel<unsigned short, 11, RR_NT><<<dim3(g.H * rr_nseg, g.B), RR_NT, rows_lds, ctx->stream>>>(k, mode, rr_sw);
+        front_route_note(ctx, "r_rows<%s,mode=%d,seg=%d>", wide_ids ? "u32" : "u16", mode, rr_nseg);
+    };
+    auto launch_l_wide = [&](hipStream_t st) {
+        apply_l_wide_kernel<<<grid, 256, 0, st>>>(k);
+        front_route_note(ctx, "l_wide");
     };
     hipStream_t ls = ctx->stream;
     if (split) { // the L side on the side stream from here on
@@ -1998,11 +2017,12 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
         VPPX_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
         ls = ctx->stream2;
     }
+    front_route_note(ctx, "vpp_order<%s,%s>", !need_lists ? "independent" : (split_late ? "late" : "inplace"), split ? "side" : "main");
     if (!need_lists) {
         // no L kernel looks at R: the two sides are independent
         launch_l_hint(ls);
         VPPX_CHECK_LAUNCH();
-        if (k.n > 3) apply_l_wide_kernel<<<grid, 256, 0, ls>>>(k);
+        if (k.n > 3) launch_l_wide(ls);
         VPPX_CHECK_LAUNCH();
         launch_r_rows(1);
         VPPX_CHECK_LAUNCH();
@@ -2018,7 +2038,7 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
         VPPX_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
         VPPX_HIP(hipStreamWaitEvent(ls, ctx->ev_fork, 0));
         if (two_pass) launch_l_heavy(ls);
-        else apply_l_wide_kernel<<<grid, 256, 0, ls>>>(k); // (n > 3)
+        else launch_l_wide(ls); // (n > 3)
         VPPX_CHECK_LAUNCH();
     } else {
         // R is patterned in place: every L pass that reads it comes first
@@ -2027,7 +2047,7 @@ int vpp_launch(vppx_ctx *ctx, const VppxVppParams &p, const VppGeom &g, u8 *l, u
         launch_l_hint(ls);
         VPPX_CHECK_LAUNCH();
         if (two_pass) launch_l_heavy(ls);
-        if (k.n > 3) apply_l_wide_kernel<<<grid, 256, 0, ls>>>(k);
+        if (k.n > 3) launch_l_wide(ls);
         VPPX_CHECK_LAUNCH();
         launch_r_rows(1);
         VPPX_CHECK_LAUNCH();
@@ -2092,6 +2112,7 @@ int vpp_launch_bilateral_fill(vppx_ctx *ctx, const VppxVppParams &p, const VppGe
     if ((rc = ws_get(ctx, WS_GRAY_CTX, npix, &gray))) return rc;
     gray_ctx_kernel<<<dim3((unsigned)((npix + 255) / 256)), 256, 0, ctx->stream>>>(left, gray, npix, g.C);
     VPPX_CHECK_LAUNCH();
+    front_route_note(ctx, "gray_ctx");
     // the reference divides by 2*o^2 (vpp_standalone.py:386); a multiplication by the reciprocal
     // would round differently, so the kernel receives the divisors
     dim3 grid((g.W + 255) / 256, g.H, g.B);
@@ -2099,6 +2120,7 @@ int vpp_launch_bilateral_fill(vppx_ctx *ctx, const VppxVppParams &p, const VppGe
                                                           2.0 * (p.bilateral_o_xy * p.bilateral_o_xy),
                                                           2.0 * (p.bilateral_o_i * p.bilateral_o_i), p.bilateral_th);
     VPPX_CHECK_LAUNCH();
+    front_route_note(ctx, "bilateral_fill");
     return 0;
 }
 
@@ -2333,15 +2355,19 @@ int occ_launch(vppx_ctx *ctx, int B, int H, int W, const float *hints, int rx, i
         if (rc) return rc;
     }
     VPPX_HIP(hipMemsetAsync(omap, 0, n * sizeof(float), ctx->stream));
-    if (W % 4 == 0 && ((size_t)hints & 15) == 0)
+    if (W % 4 == 0 && ((size_t)hints & 15) == 0) {
         occ_warp4_kernel<<<dim3((W / 4 + 255) / 256, H, B), 256, 0, ctx->stream>>>((const float4 *)hints, (int *)omap, H, W);
-    else
+        front_route_note(ctx, "occ_warp4");
+    } else {
         occ_warp_kernel<<<grid, 256, 0, ctx->stream>>>(hints, (int *)omap, H, W);
+        front_route_note(ctx, "occ_warp");
+    }
     VPPX_CHECK_LAUNCH();
     rx /= 2, ry /= 2; // filter.py:142-143
     const long long nwin = (2LL * rx + 1) * (2LL * ry + 2);
 #define OCC_TEST(NJ) do { if (small) occ_test_kernel<NJ, 2><<<grid_t, 256, 0, ctx->stream>>>(hints, omap, conf_out, tmp, H, W, rx, ry, l, g, th_conf, th_filter); \
-                          else occ_test_kernel<NJ, 4><<<grid_t, 256, 0, ctx->stream>>>(hints, omap, conf_out, tmp, H, W, rx, ry, l, g, th_conf, th_filter); } while (0)
+                          else occ_test_kernel<NJ, 4><<<grid_t, 256, 0, ctx->stream>>>(hints, omap, conf_out, tmp, H, W, rx, ry, l, g, th_conf, th_filter); \
+                          front_route_note(ctx, "occ_test<%d,%d>", NJ, small ? 2 : 4); } while (0)
     if (nwin <= 64) OCC_TEST(1);
     else if (nwin <= 128) OCC_TEST(2);
     else if (nwin <= 192) OCC_TEST(3);
@@ -2352,6 +2378,7 @@ int occ_launch(vppx_ctx *ctx, int B, int H, int W, const float *hints, int rx, i
     if (dmap_out) {
         occ_dmap_kernel<<<grid, 256, 0, ctx->stream>>>(tmp, omap, dmap_out, H, W);
         VPPX_CHECK_LAUNCH();
+        front_route_note(ctx, "occ_dmap");
     }
     return 0;
 }

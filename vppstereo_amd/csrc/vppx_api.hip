@@ -28,6 +28,13 @@ extern "C" const char *vppx_last_error(void) { return g_err; }
 // ---------------------------------------------------------------------------------------
 // routes: the kernel instantiations the last rSGM-bearing call launched (vppx_last_routes)
 // ---------------------------------------------------------------------------------------
+static void note_once(std::vector<std::string> &list, const char *name)
+{
+    for (const std::string &r : list)
+        if (r == name) return;
+    list.emplace_back(name);
+}
+
 void route_note(vppx_ctx *ctx, const char *fmt, ...)
 {
     char buf[128];
@@ -35,17 +42,25 @@ void route_note(vppx_ctx *ctx, const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    for (const std::string &r : ctx->routes)
-        if (r == buf) return;
-    ctx->routes.emplace_back(buf);
+    note_once(ctx->routes, buf);
 }
 
-extern "C" int vppx_last_routes(vppx_ctx *ctx, char *buf, int n)
+void front_route_note(vppx_ctx *ctx, const char *fmt, ...)
+{
+    char buf[128];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    note_once(ctx->front_routes, buf);
+}
+
+static int routes_to_buf(const char *who, vppx_ctx *ctx, const std::vector<std::string> vppx_ctx::*list, char *buf, int n)
 {
     if (!ctx) { vppx_set_error("context is NULL (vppx_create failed? there is no CPU fallback)"); return VPPX_E_NO_DEVICE; }
-    if (n < 0 || (n > 0 && !buf)) { vppx_set_error("vppx_last_routes: bad buffer"); return VPPX_E_INVALID_ARG; }
+    if (n < 0 || (n > 0 && !buf)) { vppx_set_error("%s: bad buffer", who); return VPPX_E_INVALID_ARG; }
     std::string all;
-    for (const std::string &r : ctx->routes) {
+    for (const std::string &r : ctx->*list) {
         if (!all.empty()) all += ',';
         all += r;
     }
@@ -55,6 +70,12 @@ extern "C" int vppx_last_routes(vppx_ctx *ctx, char *buf, int n)
         buf[k] = '\0';
     }
     return (int)all.size();
+}
+
+extern "C" int vppx_last_routes(vppx_ctx *ctx, char *buf, int n) { return routes_to_buf("vppx_last_routes", ctx, &vppx_ctx::routes, buf, n); }
+extern "C" int vppx_last_front_routes(vppx_ctx *ctx, char *buf, int n)
+{
+    return routes_to_buf("vppx_last_front_routes", ctx, &vppx_ctx::front_routes, buf, n);
 }
 
 extern "C" int vppx_version(void) { return VPPX_VERSION; }
@@ -1212,6 +1233,7 @@ extern "C" int vppx_vpp_dev(vppx_ctx *ctx, const VppxVppParams *p, int B, int H,
     if (!p || !l || !r || !g) { vppx_set_error("vppx_vpp: NULL argument"); return VPPX_E_INVALID_ARG; }
     if (B <= 0 || H <= 0 || W <= 0) { vppx_set_error("bad shape B=%d H=%d W=%d", B, H, W); return VPPX_E_INVALID_ARG; }
     if ((rc = check_vpp_params(*p))) return rc;
+    front_routes_reset(ctx);
     VppGeom vg = {B, H, W, C};
     stage_begin(ctx);
     if (p->use_bilateral_patch && !filled_g) {
@@ -1386,9 +1408,11 @@ static int vpp_rsgm_one(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPar
                                                                                                           : (B >= VPPX_FUSED_MIN_FRAMES ? 4 : 8);
         const size_t sum_lds = rsgm_sum_lds_bytes(ctx, rp->dmax, nvol_prev), cu_lds = 160 * 1024;
         const size_t left_over = cu_lds > sum_lds + 512 ? cu_lds - sum_lds - 512 : 2048;
-        // (less than 6 KB left -- D = 256 on the trapezoid ring with spare slots, whose 4 x 125 VGPRs per SIMD leave no registers
-        // either: nothing of the front stage can run NEXT to that kernel, so its kernels keep their efficient shapes and run in its tail)
-        ctx->front_lds_budget = (piped && left_over < 64 * 1024 && left_over >= 6 * 1024) ? left_over : 64 * 1024;
+        // Less than 6 KB left (D = 200 .. 248): nothing of the front stage fits.  D = 256 on the trapezoid ring with spare slots
+        // leaves 8736 bytes, but its 4 x 125 VGPRs per SIMD leave no registers: nothing of the front stage can run NEXT to that
+        // kernel either.  In both cases its kernels keep their efficient shapes and run in the sum kernel's tail.
+        const bool sum_fills_cu = rp->dmax == 256 && nvol_prev == 4 && ctx->knobs.sum_trap == 2 && !ctx->knobs.sum_general;
+        ctx->front_lds_budget = (piped && !sum_fills_cu && left_over < 64 * 1024 && left_over >= 6 * 1024) ? left_over : 64 * 1024;
     }
     stage_begin(ctx);
     if (op) { // test.py:154: g_occ = occlusion_heuristic(hints)[1]
@@ -1495,6 +1519,7 @@ static int occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxV
         if ((rc = ws_get(ctx, WS_OCC_OMAP, np, &omap))) return rc;
         if ((rc = ws_reserve(ctx, WS_STAGE_D, np, &dconf))) return rc;
         ctx->front_lds_budget = 64 * 1024;
+        front_routes_reset(ctx);
         if ((rc = occ_launch(ctx, B, H, W, (const float *)dg, op->rx, op->ry, op->l, op->g, op->th_conf, op->th_filter, omap, (u8 *)dconf))) return rc;
         docc = dconf; // from here on a given mask
         if (!conf_out) dconf = nullptr;
@@ -1507,6 +1532,7 @@ static int occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxV
     if ((rc = ws_reserve(ctx, WS_HANDOFF_H, np * sizeof(float), &dout))) return rc;
     for (int attempt = 0;; attempt++) {
         const unsigned serial_before = ctx->v3.serial;
+        ctx->front_routes_keep = op != nullptr; // (vppx_last_front_routes: the heuristic above belongs to this call)
         rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, (const u8 *)dl, (const u8 *)dr, (const float *)dg, (const u8 *)docc,
                             (const float *)dvh, nullptr, (u8 *)dlv, (u8 *)drv, (float *)dout);
         ctx->inputs_ev = nullptr;
@@ -2048,6 +2074,9 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
 {
     int rc;
     routes_reset(ctx); // (sub-stream children record into their own lists: not merged here)
+    if (!ctx->front_routes_keep) front_routes_reset(ctx);
+    ctx->front_routes_keep = false;
+    const size_t front_base = ctx->front_routes.size(); // (what a host wrapper queued before this: not part of a captured graph)
     if ((rc = lockstep_check(ctx))) return rc;
     if (!vp || !rp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_vpp_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
     if ((rc = check_frames(B, H, W, C))) return rc;
@@ -2080,6 +2109,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             VPPX_HIP(hipGraphLaunch(ctx->gexec, ctx->stream));
             ctx->graph_replays++;
             ctx->routes = ctx->graph_routes; // what the captured call launched
+            for (const std::string &r : ctx->graph_front_routes) front_route_note(ctx, "%s", r.c_str());
             return 0;
         }
         if (lut_ok && ctx->have_lastkey && memcmp(&key, &ctx->lastkey, sizeof(key)) == 0) {
@@ -2105,6 +2135,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
                         ctx->gkey = key;
                         ctx->have_gkey = true;
                         ctx->graph_routes = ctx->routes;
+                        ctx->graph_front_routes.assign(ctx->front_routes.begin() + front_base, ctx->front_routes.end());
                         ctx->graph_captures++;
                         VPPX_HIP(hipGraphLaunch(ctx->gexec, ctx->stream));
                         ctx->graph_replays++;
@@ -2283,6 +2314,7 @@ extern "C" int vppx_occlusion_heuristic_full_dev(vppx_ctx *ctx, int B, int H, in
     float *omap;
     if ((rc = ws_get(ctx, WS_OCC_OMAP, n, &omap))) return rc;
     ctx->front_lds_budget = 64 * 1024;
+    front_routes_reset(ctx);
     return occ_launch(ctx, B, H, W, hints, rx, ry, l, g, th_conf, th_filter, omap, conf_out, dmap_out);
 }
 

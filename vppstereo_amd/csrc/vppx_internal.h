@@ -179,6 +179,11 @@ struct vppx_ctx {
     // entry of every such call, appended to by the launchers where the template arguments are known
     std::vector<std::string> routes;
     std::vector<std::string> graph_routes; // those of the captured call: a replay launches nothing from the host and restores them
+    // the same for the front stage (occlusion heuristic, VPP, bilateral filling: vppx_last_front_routes), a list of its own so
+    // that vppx_last_routes keeps its content: cleared at the entry of every call that can launch a front-stage kernel
+    std::vector<std::string> front_routes;
+    std::vector<std::string> graph_front_routes;
+    bool front_routes_keep = false; // one-shot: the host wrapper has queued the heuristic already, vpp_rsgm_entry adds to the list
     int use_vert = -1;             // VPPX_VERT: -1 pick by shape (default), 0 eight line-parallel paths, 1 band marching, 3 fused vertical kernel
     int last_vert = 0;             // what the last aggregation used (vppx_uses_vert)
     int last_parts = 1;            // parts the last fused call ran as (vppx_last_call_parts)
@@ -328,6 +333,10 @@ static inline int ws_get(vppx_ctx *ctx, WsSlot s, size_t count, T **out)
 // vppx_last_routes: the launcher of a kernel instantiation records it (printf-style name, e.g. "we12<12>"); duplicates are dropped
 void route_note(vppx_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 static inline void routes_reset(vppx_ctx *ctx) { ctx->routes.clear(); }
+// vppx_last_front_routes: the launchers of vpp_kernels.hip record every kernel they launch and the host decisions that select a
+// code path inside one (e.g. "r_rows<u16,mode=3,seg=2>"); duplicates are dropped
+void front_route_note(vppx_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static inline void front_routes_reset(vppx_ctx *ctx) { ctx->front_routes.clear(); }
 
 // stage ids (vppx_stage_name)
 enum {

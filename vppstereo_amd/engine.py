@@ -504,6 +504,12 @@ class Engine:
         e.g. ["paths<4,16,exact,census,u8,dirs=ff>", "sum_lr<4,u8,8,64,spare,sw4,fast,16,fullw>"]."""
         return _lib.last_routes(self.lib, self.ctx.handle)
 
+    def last_front_routes(self):
+        """The same for the front stage, a list of its own (vppx_last_front_routes): the occlusion heuristic, VPP and bilateral
+        filling kernels the last call launched, e.g. ["occ_warp4", "occ_test<2,4>", "compact<plain>", "rowscan", "rand",
+        "vpp_order<late,side>", "l_bits<3,1>", "r_rows<u16,mode=3,seg=1>", "l_heavy<3>"]."""
+        return _lib.last_front_routes(self.lib, self.ctx.handle)
+
     def fused_pixels_per_wave(self):
         """16 / 8: which fused vertical kernel the last call used (sgm_vert4_kernel / sgm_vert3_kernel); 0: none."""
         return int(self.lib.vppx_fused_pixels_per_wave(self.ctx.handle))
