@@ -246,6 +246,32 @@ int vppx_median3x3(vppx_ctx *ctx, const float *src, float *dst, int w, int h);
 int vppx_rsgm_post_dev(vppx_ctx *ctx, int B, int H, int W, const float *disp_l_pad, const float *disp_r_pad, int subpixel,
                        float *disp_out);
 
+/* Stage API: three more stages of compute_rsgm on device buffers, each through the very launch the whole call makes (the
+ * pyrSGM-style entries above run kernels of their own).  Like vppx_rsgm_post_dev they queue on the context's stream, do not
+ * synchronise, use no workspace and leave vppx_last_routes / vppx_last_front_routes as they were.  Hp, Wp = H, W rounded up
+ * to multiples of 16, the frame centred as rsgm.py:254-260 pads it (pad_l = (Wp - W) / 2, pad_t = (Hp - H) / 2).
+ *
+ * vppx_rsgm_front_dev: reflect pad (rsgm.py:258-260), RGB -> gray for C = 3 (the plane itself for C = 1) and the 5x5
+ * census (rsgm.py:25-26) of three images in one launch.  left / left_vpp / right_vpp: uint8 [B,H,W,C], H, W >= 5.
+ * gray_left: uint8 [B,Hp,Wp], the padded gray image of `left` (the P2 image, rsgm.py:270).  census_l / census_r: uint32
+ * [B,Hp,Wp], the census codes of the padded gray images of left_vpp / right_vpp (zero on the 2-pixel border). */
+int vppx_rsgm_front_dev(vppx_ctx *ctx, int B, int H, int W, int C, const uint8_t *left, const uint8_t *left_vpp,
+                        const uint8_t *right_vpp, uint8_t *gray_left, uint32_t *census_l, uint32_t *census_r);
+/* vppx_rsgm_guided_rows_dev: the cost rows of --guided (_guided_dsi, rsgm.py:116-127, on the rows of
+ * costMeasureCensus5x5_xyd_SSE) at the hint pixels only.  census_l / census_r: uint32 [B,Hp,Wp]; row x of census_r is read
+ * at x - d for d <= x only, never in front of a row, so census_r needs no guard words in front of it.  hints / validhints:
+ * float32 [B,H,W], un-padded (rsgm.py:266-267 pads them with zeros: a padding pixel owns no row).  gmap: int32 [B,Hp,Wp],
+ * receives the row index of every padded pixel with validhints > 0 and -1 elsewhere; the indices are 0 .. n-1 in no
+ * particular order.  rows: uint16 [n][dmax]; n is not known beforehand, so reserve B*H*W rows as the whole call does.
+ * count: one uint32, receives n.  dmax: a multiple of 8 in 8 .. 256 (VPPX_E_DMAX_MOD8 / VPPX_E_DMAX_GT256 otherwise). */
+int vppx_rsgm_guided_rows_dev(vppx_ctx *ctx, int B, int H, int W, int dmax, const uint32_t *census_l, const uint32_t *census_r,
+                              const float *hints, const float *validhints, int32_t *gmap, uint16_t *rows, uint32_t *count);
+/* vppx_rsgm_mid_dev: median3x3_SSE -> _linear_interpolate(., 15, 3) -> np.clip(., 0, None) of the left and the right
+ * disparity map (rsgm.py:145-151, 173-179) in one launch.  All four: float32 [B,Hp,Wp]; the outputs must not alias the
+ * inputs.  Hp, Wp: multiples of 16, at least 16 (VPPX_E_INVALID_ARG otherwise). */
+int vppx_rsgm_mid_dev(vppx_ctx *ctx, int B, int Hp, int Wp, const float *disp_l, const float *disp_r, float *out_l,
+                      float *out_r);
+
 /* left / left_vpp / right_vpp: uint8 [B,H,W,C] (C = 1 or 3); disp_out: float32 [B,H,W].
  * hints / validhints: float32 [B,H,W] or both NULL; non-NULL = --guided (_guided_dsi, rsgm.py:116-127). */
 int vppx_rsgm_host(vppx_ctx *ctx, const VppxRsgmParams *p, int B, int H, int W, int C, const uint8_t *left,

@@ -26,12 +26,35 @@ _LIB_OVERRIDE = os.environ.get("ORACLE_LIB")
 
 
 def build(force=False):
-    """Compile oracle/liboracle.so with gcc (Makefile in this directory)."""
+    """Compile oracle/liboracle.so with gcc (Makefile in this directory).
+
+    Safe when several processes ask at once (bench.py forks one worker per core, and each loads the library): one of them
+    compiles, into a file of its own name that is renamed over the library when complete, so that nobody ever loads a
+    half-written file; the others wait for it and find the library fresh."""
     srcs = [os.path.join(_HERE, f) for f in ("vpp_oracle.c", "rsgm_oracle.c", "Makefile")]
-    if (not force and os.path.exists(_LIB_PATH)
-            and all(os.path.getmtime(_LIB_PATH) >= os.path.getmtime(s) for s in srcs)):
+
+    def fresh(since=None):
+        if not os.path.exists(_LIB_PATH):
+            return False
+        t = os.path.getmtime(_LIB_PATH)
+        return t >= since if since is not None else all(t >= os.path.getmtime(s) for s in srcs)
+
+    if not force and fresh():
         return _LIB_PATH
-    subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
+    import fcntl
+    import time
+    asked = time.time()
+    with open(_LIB_PATH + ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        # (built by another process while this one waited for the lock: that build is as good as this one's)
+        if not (fresh(asked) if force else fresh()):
+            tmp = f"liboracle.so.{os.getpid()}.tmp"
+            try:
+                subprocess.check_call(["make", "-C", _HERE, "-B", f"OUT={tmp}", tmp], stdout=subprocess.DEVNULL)
+                os.replace(os.path.join(_HERE, tmp), _LIB_PATH)
+            finally:
+                if os.path.exists(os.path.join(_HERE, tmp)):
+                    os.unlink(os.path.join(_HERE, tmp))
     return _LIB_PATH
 
 

@@ -52,6 +52,15 @@ def test_calls_without_a_context_fail_with_a_message():
     for rc in (lib.vppx_set_stream_legacy(null), lib.vppx_rand_advance(null, 1), lib.vppx_synchronize(null)):
         assert rc == -7
         assert b"context is NULL" in lib.vppx_last_error()
+    # the stage entries of the fused front, guided-row and median/interpolate kernels: arguments that would pass every
+    # other check (the pointers are never read: the context comes first)
+    buf = np.zeros(16 * 16 * 8, np.uint32)
+    p = C.c_void_p(buf.ctypes.data)
+    for call in (lambda: lib.vppx_rsgm_front_dev(null, 1, 16, 16, 1, p, p, p, p, p, p),
+                 lambda: lib.vppx_rsgm_guided_rows_dev(null, 1, 16, 16, 8, p, p, p, p, p, p, p),
+                 lambda: lib.vppx_rsgm_mid_dev(null, 1, 16, 16, p, p, p, p)):
+        assert call() == -7
+        assert b"context is NULL" in lib.vppx_last_error()
 
 
 def _has_gpu():

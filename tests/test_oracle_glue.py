@@ -110,3 +110,20 @@ def test_hint_range_equals_the_reference_wrappers_numpy_statements():
         with pytest.raises(ValueError):
             hint_range(bad)
     assert hint_range(np.zeros((0, 4), np.float32)) == (None, None)
+
+
+def _build_and_load(_):
+    import ctypes
+    import oracle
+    path = oracle.build(force=True)
+    return ctypes.CDLL(path).rsgmo_get_simd()
+
+
+def test_oracle_build_is_safe_when_many_processes_ask_at_once():
+    """bench.py's all-cores CPU leg forks one worker per core and each loads the oracle: with a stale library every one of them
+    used to run the compiler onto the same file, and some loaded it half written ("file too short").  Now one compiles into a
+    file of its own, renamed when complete, and the others wait."""
+    import multiprocessing as mp
+    with mp.get_context("fork").Pool(6) as pool:
+        assert pool.map(_build_and_load, range(6), chunksize=1) == [0] * 6
+    assert not [f for f in os.listdir(os.path.dirname(oracle.__file__)) if f.endswith(".tmp")]

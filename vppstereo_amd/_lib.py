@@ -35,6 +35,7 @@ EXPORTS = [
     "vppx_fstream_create_scaled",
     "vppx_eval_params_default", "vppx_guided_metrics_dev", "vppx_guided_metrics_host", "vppx_occ_vpp_rsgm_eval_dev",
     "vppx_fstream_create_eval", "vppx_fstream_push_eval", "vppx_fstream_pop_eval",
+    "vppx_rsgm_front_dev", "vppx_rsgm_guided_rows_dev", "vppx_rsgm_mid_dev",
 ]
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 FS_METRICS, FS_NO_DISP = 16, 32
@@ -153,6 +154,9 @@ def load():
         lib.vppx_rsgm_host.argtypes = [vp, pr, i, i, i, i, vp, vp, vp, vp, vp, vp]
         lib.vppx_rsgm_dev.argtypes = [vp, pr, i, i, i, i, vp, vp, vp, vp, vp, vp]
         lib.vppx_rsgm_post_dev.argtypes = [vp, i, i, i, vp, vp, i, vp]
+        lib.vppx_rsgm_front_dev.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, vp]
+        lib.vppx_rsgm_guided_rows_dev.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
+        lib.vppx_rsgm_mid_dev.argtypes = [vp, i, i, i, vp, vp, vp, vp]
         lib.vppx_vpp_rsgm_dev.argtypes = [vp, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
         po = C.POINTER(VppxOccParams)
         lib.vppx_occ_vpp_rsgm_host.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64)]

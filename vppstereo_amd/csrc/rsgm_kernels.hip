@@ -3895,7 +3895,8 @@ int rsgm_launch_median(vppx_ctx *ctx, int B, int Hp, int Wp, const float *src, f
 }
 
 // ---------------------------------------------------------------------------------------
-// _linear_interpolate(dmap, 15, 3) (rsgm.py:67-113) + np.clip(.,0,None) (:151,179).
+// Fused median3x3 -> _linear_interpolate(dmap, 15, 3) (rsgm.py:67-113) -> np.clip(.,0,None) for the left and the right
+// view (rsgm.py:145-151, 173-179).
 // The reference walks each row in place.  A fill only happens for a gap (maximal run of
 // values <= 0 between two valid pixels xl < xr of the same row) with xr-xl <= 14, and it is
 // triggered by the first hole pixel, in raster order, that sees both ends inside its +-7
@@ -3903,51 +3904,12 @@ int rsgm_launch_median(vppx_ctx *ctx, int B, int Hp, int Wp, const float *src, f
 // every pixel of [xl, xr] is overwritten with (float)(m*(x-x_t)+q); the two end points come
 // back bit-identical (the float64 error is far below half a float32 ulp), so gaps are
 // independent and every hole pixel can evaluate its own value: one thread per pixel.
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) linear_interp_clip_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                                 int Hp, int Wp)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y, f = blockIdx.z;
-    if (x >= Wp) return;
-    const float *row = src + ((size_t)f * Hp + y) * Wp;
-    float v = row[x];
-    if (v <= 0) {
-        int xl = -1, xr = -1;
-        for (int k = 1; k <= 13; k++)
-            if (x - k >= 0 && row[x - k] > 0) { xl = x - k; break; }
-        if (xl >= 0) {
-            for (int k = 1; k <= 14 - (x - xl); k++)
-                if (x + k < Wp && row[x + k] > 0) { xr = x + k; break; }
-        }
-        if (xl >= 0 && xr >= 0) { // xr - xl <= 14 by construction
-            const double n_left = (double)row[xl], n_right = (double)row[xr];
-            if (fabs(n_left - n_right) < 3.0) {
-                const int xt = max(xl + 1, xr - 7);
-                const int n_leftx = xl - xt, n_rightx = xr - xt;
-                const double m = __ddiv_rn(n_right - n_left, (double)(n_rightx - n_leftx));
-                const double q = __dsub_rn(n_left, __dmul_rn(m, (double)n_leftx));
-                v = (float)__dadd_rn(__dmul_rn(m, (double)(x - xt)), q);
-            }
-        }
-    }
-    dst[((size_t)f * Hp + y) * Wp + x] = (v >= 0) ? v : 0.0f; // np.clip(., 0, None)
-}
-
-int rsgm_launch_linear_interp_clip(vppx_ctx *ctx, int B, int Hp, int Wp, const float *src, float *dst)
-{
-    dim3 grid((Wp + 255) / 256, Hp, B);
-    linear_interp_clip_kernel<<<grid, 256, 0, ctx->stream>>>(src, dst, Hp, Wp);
-    VPPX_CHECK_LAUNCH();
-    return 0;
-}
-
-// Fused median3x3 -> _linear_interpolate -> clip for the left and the right view (rsgm.py:145-151,
-// 173-179): one block per row; the row's medians go to LDS, together with a bitmap of the valid (> 0) ones; a hole pixel
+// One block per row; the row's medians go to LDS, together with a bitmap of the valid (> 0) ones; a hole pixel
 // finds its nearest valid neighbours (at most 13 to the left, then as far to the right as the reference's window of 14
 // allows) with two bit scans of a 27-bit window of that bitmap instead of two loops over LDS -- the pad columns make every
-// row end in holes, and one hole keeps its whole wave in those loops.  (Same arithmetic as the two stand-alone kernels
-// above, which the stage API keeps using.)
+// row end in holes, and one hole keeps its whole wave in those loops.  (The median is median3x3_kernel's, which the stage
+// API keeps; nothing else computes the interpolation.  Stage entry: vppx_rsgm_mid_dev.)
+// ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) median_interp_clip_kernel(ImgSet io, int B, int Hp, int Wp)
 {
     extern __shared__ __attribute__((aligned(16))) float s_med[]; // [Wp] medians, then the bitmap: [Wp / 64 + 3] 64-bit words

@@ -1178,6 +1178,56 @@ extern "C" int vppx_rsgm_post_dev(vppx_ctx *ctx, int B, int H, int W, const floa
     return rsgm_launch_post(ctx, g, disp_l_pad, disp_r_pad, subpixel, disp_out);
 }
 
+// Stage entries of the three fused kernels that have no pyrSGM-style stage of their own.  Each one queues the launcher
+// rsgm_core / run_aggregation call, on the caller's buffers; like vppx_rsgm_post_dev they keep no record of the call (no
+// route names, no last_gl / last_cl / last_cr) and leave the workspace alone.
+extern "C" int vppx_rsgm_front_dev(vppx_ctx *ctx, int B, int H, int W, int C, const uint8_t *left, const uint8_t *left_vpp,
+                                   const uint8_t *right_vpp, uint8_t *gray_left, uint32_t *census_l, uint32_t *census_r)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!left || !left_vpp || !right_vpp || !gray_left || !census_l || !census_r) {
+        vppx_set_error("vppx_rsgm_front: NULL argument");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = check_frames(B, H, W, C))) return rc;
+    RsgmGeom g;
+    make_geom(B, H, W, C, 64, g);
+    return rsgm_launch_pad_gray_census(ctx, g, left, left_vpp, right_vpp, gray_left, census_l, census_r);
+}
+
+extern "C" int vppx_rsgm_guided_rows_dev(vppx_ctx *ctx, int B, int H, int W, int dmax, const uint32_t *census_l,
+                                         const uint32_t *census_r, const float *hints, const float *validhints, int32_t *gmap,
+                                         uint16_t *rows, uint32_t *count)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!census_l || !census_r || !hints || !validhints || !gmap || !rows || !count) {
+        vppx_set_error("vppx_rsgm_guided_rows: NULL argument");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = check_frames(B, H, W, 1))) return rc;
+    VppxRsgmParams p;
+    vppx_rsgm_params_default(&p);
+    p.dmax = dmax;
+    if ((rc = check_rsgm_params(p))) return rc;
+    RsgmGeom g;
+    make_geom(B, H, W, 1, dmax, g);
+    return rsgm_launch_guided_rows(ctx, g, census_l, census_r, hints, validhints, gmap, rows, count);
+}
+
+extern "C" int vppx_rsgm_mid_dev(vppx_ctx *ctx, int B, int Hp, int Wp, const float *disp_l, const float *disp_r, float *out_l,
+                                 float *out_r)
+{
+    VPPX_ENTER(ctx);
+    if (!disp_l || !disp_r || !out_l || !out_r) { vppx_set_error("vppx_rsgm_mid: NULL argument"); return VPPX_E_INVALID_ARG; }
+    if (B <= 0 || Hp < 16 || Wp < 16 || Hp % 16 != 0 || Wp % 16 != 0) {
+        vppx_set_error("vppx_rsgm_mid: padded maps are [B][Hp][Wp] with Hp, Wp multiples of 16 (got B=%d Hp=%d Wp=%d)", B, Hp, Wp);
+        return VPPX_E_INVALID_ARG;
+    }
+    return rsgm_launch_median_interp_clip(ctx, B, Hp, Wp, disp_l, out_l, disp_r, out_r);
+}
+
 extern "C" int vppx_rsgm_host(vppx_ctx *ctx, const VppxRsgmParams *p, int B, int H, int W, int C, const uint8_t *left,
                               const uint8_t *left_vpp, const uint8_t *right_vpp, const float *hints,
                               const float *validhints, float *disp_out)

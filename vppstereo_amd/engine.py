@@ -101,6 +101,63 @@ class Engine:
                                                int(bool(subpixel)), _ptr(out)))
         return out
 
+    @staticmethod
+    def _padded(h, w):
+        return -(-int(h) // 16) * 16, -(-int(w) // 16) * 16
+
+    def rsgm_front(self, left, left_vpp, right_vpp):
+        """Stage API: the front stage of compute_rsgm (rsgm.py:254-263) through the one launch the whole call makes: reflect
+        pad, gray, 5x5 census.  left / left_vpp / right_vpp: uint8 [B,H,W,C].  Returns (gray_left uint8, census_l uint32,
+        census_r uint32), each [B,Hp,Wp]: the padded gray image of `left`, the census codes of the padded patterned pair."""
+        torch = self.torch
+        self._chk(left, torch.uint8, 4, "left")
+        B, H, W, Cc = left.shape
+        if Cc not in (1, 3):
+            raise ValueError("left: channels must be 1 or 3")
+        self._chk(left_vpp, torch.uint8, 4, "left_vpp", left.shape)
+        self._chk(right_vpp, torch.uint8, 4, "right_vpp", left.shape)
+        Hp, Wp = self._padded(H, W)
+        gray = torch.empty((B, Hp, Wp), dtype=torch.uint8, device=self.device)
+        cl = torch.empty((B, Hp, Wp), dtype=torch.uint32, device=self.device)
+        cr = torch.empty((B, Hp, Wp), dtype=torch.uint32, device=self.device)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_rsgm_front_dev(self.ctx.handle, B, H, W, Cc, _ptr(left), _ptr(left_vpp), _ptr(right_vpp),
+                                                _ptr(gray), _ptr(cl), _ptr(cr)))
+        return gray, cl, cr
+
+    def rsgm_guided_rows(self, census_l, census_r, hints, validhints, dmax):
+        """Stage API: the compact re-weighted cost rows of --guided (_guided_dsi, rsgm.py:116-127) through the launch the
+        whole call makes.  census_l / census_r: uint32 [B,Hp,Wp]; hints / validhints: float32 [B,H,W] with Hp, Wp = H, W
+        rounded up to multiples of 16.  Returns (gmap int32 [B,Hp,Wp], rows uint16 [B*H*W, dmax], count uint32 [1]): gmap is
+        the row index of every pixel with validhints > 0 (-1 elsewhere), count the number of rows written."""
+        torch = self.torch
+        self._chk(hints, torch.float32, 3, "hints")
+        B, H, W = hints.shape
+        self._chk(validhints, torch.float32, 3, "validhints", hints.shape)
+        Hp, Wp = self._padded(H, W)
+        self._chk(census_l, torch.uint32, 3, "census_l", (B, Hp, Wp))
+        self._chk(census_r, torch.uint32, 3, "census_r", (B, Hp, Wp))
+        gmap = torch.empty((B, Hp, Wp), dtype=torch.int32, device=self.device)
+        rows = torch.empty((B * H * W, int(dmax)), dtype=torch.uint16, device=self.device)
+        count = torch.empty((1,), dtype=torch.uint32, device=self.device)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_rsgm_guided_rows_dev(self.ctx.handle, B, H, W, int(dmax), _ptr(census_l), _ptr(census_r),
+                                                      _ptr(hints), _ptr(validhints), _ptr(gmap), _ptr(rows), _ptr(count)))
+        return gmap, rows, count
+
+    def rsgm_mid(self, disp_l, disp_r):
+        """Stage API: median3x3 -> _linear_interpolate(., 15, 3) -> clip (rsgm.py:145-151, 173-179) of the padded left /
+        right disparity maps, float32 [B,Hp,Wp] with Hp, Wp multiples of 16, through the launch the whole call makes.
+        Returns (out_l, out_r)."""
+        torch = self.torch
+        self._chk(disp_l, torch.float32, 3, "disp_l")
+        B, Hp, Wp = disp_l.shape
+        self._chk(disp_r, torch.float32, 3, "disp_r", disp_l.shape)
+        out_l, out_r = torch.empty_like(disp_l), torch.empty_like(disp_r)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_rsgm_mid_dev(self.ctx.handle, B, Hp, Wp, _ptr(disp_l), _ptr(disp_r), _ptr(out_l), _ptr(out_r)))
+        return out_l, out_r
+
     def vpp_rsgm(self, left, right, hints, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
                  rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None, iscale=1, oscale=1, disp_small=None,
                  gt=None, validgt=None, metrics_out=None, errormap=None):
