@@ -19,6 +19,9 @@
  *   occlusion_heuristic()               filter.py:246-292           vppx_occlusion_heuristic_host/_dev
  *   test.py:158-225 (VPP -> rSGM per frame)                         vppx_vpp_rsgm_dev (fused, batched)
  *   guided_metrics()                    losses.py:13-24             vppx_guided_metrics_host / _dev, vppx_occ_vpp_rsgm_eval_dev
+ *   color_error_image_kitti()           utils.py:17-36              vppx_error_colors_host / _dev
+ *   guided_visualize()                  utils.py:39-79              vppx_guided_visualize_host / _dev
+ *   test.py:318, :325-326, :343 (max_val, applyColorMap)            vppx_finite_max_dev, vppx_colorize_host / _dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -387,6 +390,49 @@ int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op, const Vpp
                                const uint8_t *right, const float *g, const uint8_t *g_occ, const float *validhints, const float *gt,
                                const float *validgt, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
                                float *disp_small, VppxMetrics *metrics_out, float *errormap);
+
+/* ---- pictures (utils.py:17-79; test.py:318-343) --------------------------------------------------------------------------
+ * What test.py --outdir renders per frame, for a batch: inputs float32 [B,H,W], pictures uint8 [B,H,W,3].  Every call takes a
+ * `dilation` d >= 0, applied to the coloured picture as the reference does with cv2.dilate(img, np.ones((d, d))): per channel
+ * the maximum over the offsets -(d/2) .. d-1-(d/2) in both axes (anchor d/2: an even window leans up and left), pixels outside
+ * the frame ignored, frames of a batch independent; d = 0 and d = 1 are the identity.  The dilation is fused with the colouring
+ * (no un-dilated picture goes through device memory).  d above VPPX_VIZ_MAX_DILATION: VPPX_E_UNSUPPORTED.  The window is a
+ * restatement of OpenCV's documented behaviour; for d <= 1 the pictures are pinned to the reference.
+ * Argument checks (VPPX_E_INVALID_ARG, nothing launched, `out` untouched): a NULL pointer, B / H / W <= 0, dilation < 0,
+ * which == 0 or with a bit outside VPPX_VIZ_ALL, scale not > 0.  A picture is a function of its own frame only. */
+#define VPPX_VIZ_MAX_DILATION 31
+enum { /* planes of vppx_guided_visualize_*, in the reference's key order */
+    VPPX_VIZ_BAD1 = 1, VPPX_VIZ_BAD2 = 2, VPPX_VIZ_BAD3 = 4, VPPX_VIZ_BAD4 = 8, VPPX_VIZ_AVGERR = 16, VPPX_VIZ_RMS = 32,
+    VPPX_VIZ_ALL = 63
+};
+/* color_error_image_kitti: the ten rows of _color_map_errors_kitti in order, a later row overwrites an earlier one, both ends
+ * of a bin inclusive (a value on an edge takes the higher bin); the float32 error is compared in double against lo / scale and
+ * hi / scale (float64 quotients); NaN matches no bin and stays (0,0,0), +inf takes the last bin.  mask (may be NULL): pixels
+ * with mask == 0 are black -- a negative or NaN mask value keeps its colour.  bgr == 0 swaps channels 0 and 2 (before the
+ * dilation).  Device pointers, stream-ordered, no synchronisation. */
+int vppx_error_colors_dev(vppx_ctx *ctx, int B, int H, int W, const float *errors, const float *mask, double scale, int bgr,
+                          int dilation, uint8_t *out);
+/* The same on host pointers, synchronous. */
+int vppx_error_colors_host(vppx_ctx *ctx, int B, int H, int W, const float *errors, const float *mask, double scale, int bgr,
+                           int dilation, uint8_t *out);
+/* guided_visualize: with e = |disp - gt| in float32, plane 'bad k' (k = 1..4) is (49,54,149) where e > k, (165,0,38) where
+ * e <= k, black for a NaN; 'avgerr' is the error colours of e, 'rms' those of sqrt((disp - gt)^2) in float32; valid == 0 is
+ * black everywhere, any other value of valid is drawn.  out: six pictures uint8 [6][B,H,W,3] in the order of the VPPX_VIZ_*
+ * bits; only the planes whose bit is set in `which` are computed and written, the others are not touched. */
+int vppx_guided_visualize_dev(vppx_ctx *ctx, int B, int H, int W, const float *disp, const float *gt, const float *valid,
+                              double scale, int dilation, unsigned which, uint8_t *out);
+int vppx_guided_visualize_host(vppx_ctx *ctx, int B, int H, int W, const float *disp, const float *gt, const float *valid,
+                               double scale, int dilation, unsigned which, uint8_t *out);
+/* test.py:325-326, :343: out = lut[uint8(clamp(x, 0, max_val) / max_val * 255)]: clamp, divide, multiply, each rounded to
+ * float32, then truncated.  max_val: one float per frame [B]; lut: uint8 [256][3], the user colour map cv2.applyColorMap takes.
+ * Where the reference's cast is undefined the index is 0: x NaN, max_val not > 0 (NaN included), or a NaN quotient (inf / inf). */
+int vppx_colorize_dev(vppx_ctx *ctx, int B, int H, int W, const float *x, const float *max_val, const uint8_t *lut, int dilation,
+                      uint8_t *out);
+int vppx_colorize_host(vppx_ctx *ctx, int B, int H, int W, const float *x, const float *max_val, const uint8_t *lut, int dilation,
+                       uint8_t *out);
+/* test.py:318: max_out[f] = the maximum of frame f with +inf and -inf replaced by -inf (-inf when nothing else is there); a NaN
+ * in the frame gives NaN, as torch's max does.  Device pointers, stream-ordered; B <= 65535. */
+int vppx_finite_max_dev(vppx_ctx *ctx, int B, int H, int W, const float *x, float *max_out);
 
 /* ---- frame stream: the hot path for callers that hold one host frame at a time ---------------------------------------
  * test.py:291-311 iterates a DataLoader with batch size 1 and runs :154-225 per frame on numpy arrays; the kernels want

@@ -7,6 +7,7 @@ Drop-in modules (same names / signatures as the reference's):
     vppstereo_amd.rsgm.compute_rsgm             <- models/rsgm/rsgm.py:250
     vppstereo_amd.filter.occlusion_heuristic    <- filter.py:246
     vppstereo_amd.losses.{sample_hints,guided_metrics} <- losses.py
+    vppstereo_amd.utils.{color_error_image_kitti,guided_visualize} <- utils.py:17, :39
 Batched, device-resident front-end (torch tensors as plumbing): vppstereo_amd.engine.
 All compute runs in libvppx.so (HIP, gfx950); there is no CPU fallback.
 """

@@ -36,9 +36,14 @@ EXPORTS = [
     "vppx_eval_params_default", "vppx_guided_metrics_dev", "vppx_guided_metrics_host", "vppx_occ_vpp_rsgm_eval_dev",
     "vppx_fstream_create_eval", "vppx_fstream_push_eval", "vppx_fstream_pop_eval",
     "vppx_rsgm_front_dev", "vppx_rsgm_guided_rows_dev", "vppx_rsgm_mid_dev",
+    "vppx_error_colors_dev", "vppx_error_colors_host", "vppx_guided_visualize_dev", "vppx_guided_visualize_host",
+    "vppx_colorize_dev", "vppx_colorize_host", "vppx_finite_max_dev",
 ]
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 FS_METRICS, FS_NO_DISP = 16, 32
+VIZ_KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')  # utils.guided_visualize's dict keys (utils.py:79), VPPX_VIZ_* bit order
+VIZ_ALL = 63
+VIZ_MAX_DILATION = 31
 METRIC_KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')  # the reference's dict keys (losses.py:24), VppxMetrics order
 
 
@@ -221,6 +226,12 @@ def load():
         lib.vppx_fstream_create_eval.argtypes = [vp, po, pv, pr, ps, pe, i, i, i, i, i, i, i, C.POINTER(vp)]
         lib.vppx_fstream_push_eval.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         lib.vppx_fstream_pop_eval.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(VppxMetrics), C.POINTER(C.c_int)]
+        u = C.c_uint
+        for sfx in ("dev", "host"):
+            getattr(lib, "vppx_error_colors_" + sfx).argtypes = [vp, i, i, i, vp, vp, d, i, i, vp]
+            getattr(lib, "vppx_guided_visualize_" + sfx).argtypes = [vp, i, i, i, vp, vp, vp, d, i, u, vp]
+            getattr(lib, "vppx_colorize_" + sfx).argtypes = [vp, i, i, i, vp, vp, vp, i, vp]
+        lib.vppx_finite_max_dev.argtypes = [vp, i, i, i, vp, vp]
         _lib = lib
         return lib
 
@@ -399,6 +410,25 @@ def metrics_dict(rec):
     """One VppxMetrics record (ctypes struct or a sequence of its 8 doubles) -> the reference's dict (losses.py:24)."""
     v = [rec.bad1, rec.bad2, rec.bad3, rec.bad4, rec.avgerr, rec.rms] if isinstance(rec, VppxMetrics) else [float(x) for x in rec[:6]]
     return dict(zip(METRIC_KEYS, v))
+
+
+def viz_which(which):
+    """`which` of guided_visualize: None (all six), a VPPX_VIZ_* bit mask, one of the reference's keys, or an iterable of keys."""
+    if which is None:
+        return VIZ_ALL
+    if isinstance(which, str):
+        which = [which]
+    if isinstance(which, int):
+        w = which
+    else:
+        w = 0
+        for k in which:
+            if k not in VIZ_KEYS:
+                raise ValueError(f"which: unknown map {k!r} (one of {VIZ_KEYS})")
+            w |= 1 << VIZ_KEYS.index(k)
+    if w <= 0 or w & ~VIZ_ALL:
+        raise ValueError(f"which: {which!r} selects no map of {VIZ_KEYS}")
+    return w
 
 
 def scaled_shape(H, W, iscale=1, oscale=1):

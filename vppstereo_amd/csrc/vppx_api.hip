@@ -2731,3 +2731,139 @@ extern "C" int vppx_uses_vert(vppx_ctx *ctx)
     if (!ctx || !ctx->have_last) return 0;
     return ctx->last_vert;
 }
+
+// ---------------------------------------------------------------------------------------
+// pictures (utils.py:17-79; test.py:318-343): viz_kernels.hip
+// ---------------------------------------------------------------------------------------
+static int check_viz_args(const char *name, int B, int H, int W, int dilation, bool all_pointers)
+{
+    if (!all_pointers) { vppx_set_error("%s: NULL argument", name); return VPPX_E_INVALID_ARG; }
+    if (B < 1 || H < 1 || W < 1) { vppx_set_error("%s: bad shape (B %d, %d x %d)", name, B, H, W); return VPPX_E_INVALID_ARG; }
+    if (dilation < 0) { vppx_set_error("%s: dilation %d (>= 0)", name, dilation); return VPPX_E_INVALID_ARG; }
+    if (dilation > VIZ_MAX_DILATION) {
+        vppx_set_error("%s: dilation %d is above this build's limit of %d", name, dilation, VIZ_MAX_DILATION);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+static int check_viz_scale(const char *name, double scale)
+{
+    if (!(scale > 0.0)) { vppx_set_error("%s: scale %g (> 0)", name, scale); return VPPX_E_INVALID_ARG; }
+    return 0;
+}
+
+static int check_viz_which(const char *name, unsigned which)
+{
+    if (which == 0 || (which & ~(unsigned)VPPX_VIZ_ALL)) {
+        vppx_set_error("%s: which 0x%x (one or more of the VPPX_VIZ_* bits)", name, which);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vppx_error_colors_dev(vppx_ctx *ctx, int B, int H, int W, const float *errors, const float *mask, double scale, int bgr,
+                                     int dilation, uint8_t *out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx); // (no scratch)
+    int rc;
+    if ((rc = check_viz_args("vppx_error_colors_dev", B, H, W, dilation, errors && out))) return rc;
+    if ((rc = check_viz_scale("vppx_error_colors_dev", scale))) return rc;
+    return viz_launch_error_colors(ctx, B, H, W, errors, mask, scale, bgr, dilation, out);
+}
+
+extern "C" int vppx_error_colors_host(vppx_ctx *ctx, int B, int H, int W, const float *errors, const float *mask, double scale, int bgr,
+                                      int dilation, uint8_t *out)
+{
+    VPPX_ENTER(ctx);
+    int rc;
+    if ((rc = check_viz_args("vppx_error_colors_host", B, H, W, dilation, errors && out))) return rc;
+    if ((rc = check_viz_scale("vppx_error_colors_host", scale))) return rc;
+    const size_t npx = (size_t)B * H * W;
+    void *de, *dm = nullptr, *dout;
+    if ((rc = upload(ctx, WS_STAGE_A, errors, npx * sizeof(float), &de))) return rc;
+    if (mask && (rc = upload(ctx, WS_STAGE_B, mask, npx * sizeof(float), &dm))) return rc;
+    if ((rc = ws_reserve(ctx, WS_VIZ_OUT, npx * 3, &dout))) return rc;
+    if ((rc = viz_launch_error_colors(ctx, B, H, W, (const float *)de, (const float *)dm, scale, bgr, dilation, (u8 *)dout))) return rc;
+    if ((rc = download(ctx, out, dout, npx * 3))) return rc;
+    VPPX_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int vppx_guided_visualize_dev(vppx_ctx *ctx, int B, int H, int W, const float *disp, const float *gt, const float *valid,
+                                         double scale, int dilation, unsigned which, uint8_t *out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx); // (no scratch)
+    int rc;
+    if ((rc = check_viz_args("vppx_guided_visualize_dev", B, H, W, dilation, disp && gt && valid && out))) return rc;
+    if ((rc = check_viz_which("vppx_guided_visualize_dev", which))) return rc;
+    if ((rc = check_viz_scale("vppx_guided_visualize_dev", scale))) return rc;
+    return viz_launch_guided(ctx, B, H, W, disp, gt, valid, scale, dilation, which, out);
+}
+
+extern "C" int vppx_guided_visualize_host(vppx_ctx *ctx, int B, int H, int W, const float *disp, const float *gt, const float *valid,
+                                          double scale, int dilation, unsigned which, uint8_t *out)
+{
+    VPPX_ENTER(ctx);
+    int rc;
+    if ((rc = check_viz_args("vppx_guided_visualize_host", B, H, W, dilation, disp && gt && valid && out))) return rc;
+    if ((rc = check_viz_which("vppx_guided_visualize_host", which))) return rc;
+    if ((rc = check_viz_scale("vppx_guided_visualize_host", scale))) return rc;
+    const size_t npx = (size_t)B * H * W;
+    void *dd, *dg, *dv, *dout;
+    if ((rc = upload(ctx, WS_STAGE_A, disp, npx * sizeof(float), &dd))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_B, gt, npx * sizeof(float), &dg))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_C, valid, npx * sizeof(float), &dv))) return rc;
+    if ((rc = ws_reserve(ctx, WS_VIZ_OUT, 6 * npx * 3, &dout))) return rc;
+    if ((rc = viz_launch_guided(ctx, B, H, W, (const float *)dd, (const float *)dg, (const float *)dv, scale, dilation, which, (u8 *)dout)))
+        return rc;
+    for (int k = 0; k < 6; k++) // the planes that were not asked for stay as the caller left them
+        if ((which >> k & 1) && (rc = download(ctx, out + k * npx * 3, (const u8 *)dout + k * npx * 3, npx * 3))) return rc;
+    VPPX_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int vppx_colorize_dev(vppx_ctx *ctx, int B, int H, int W, const float *x, const float *max_val, const uint8_t *lut,
+                                 int dilation, uint8_t *out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx); // (no scratch)
+    int rc;
+    if ((rc = check_viz_args("vppx_colorize_dev", B, H, W, dilation, x && max_val && lut && out))) return rc;
+    return viz_launch_colorize(ctx, B, H, W, x, max_val, lut, dilation, out);
+}
+
+extern "C" int vppx_colorize_host(vppx_ctx *ctx, int B, int H, int W, const float *x, const float *max_val, const uint8_t *lut,
+                                  int dilation, uint8_t *out)
+{
+    VPPX_ENTER(ctx);
+    int rc;
+    if ((rc = check_viz_args("vppx_colorize_host", B, H, W, dilation, x && max_val && lut && out))) return rc;
+    const size_t npx = (size_t)B * H * W;
+    const size_t mv_bytes = ((size_t)B * sizeof(float) + 15) & ~(size_t)15;
+    void *dx, *daux, *dout;
+    if ((rc = upload(ctx, WS_STAGE_A, x, npx * sizeof(float), &dx))) return rc;
+    if ((rc = ws_reserve(ctx, WS_VIZ_AUX, mv_bytes + 768, &daux))) return rc;
+    VPPX_HIP(hipMemcpyAsync(daux, max_val, (size_t)B * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    VPPX_HIP(hipMemcpyAsync((u8 *)daux + mv_bytes, lut, 768, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ws_reserve(ctx, WS_VIZ_OUT, npx * 3, &dout))) return rc;
+    if ((rc = viz_launch_colorize(ctx, B, H, W, (const float *)dx, (const float *)daux, (const u8 *)daux + mv_bytes, dilation, (u8 *)dout)))
+        return rc;
+    if ((rc = download(ctx, out, dout, npx * 3))) return rc;
+    VPPX_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+extern "C" int vppx_finite_max_dev(vppx_ctx *ctx, int B, int H, int W, const float *x, float *max_out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx); // (its only scratch is a slot no front stage touches)
+    int rc;
+    if ((rc = check_viz_args("vppx_finite_max_dev", B, H, W, 0, x && max_out))) return rc;
+    if (B > 65535) { vppx_set_error("vppx_finite_max_dev: %d frames, above the limit of 65535 per call", B); return VPPX_E_UNSUPPORTED; }
+    float *part = nullptr;
+    if ((rc = ws_get(ctx, WS_VIZ_PART, (size_t)B * viz_finite_max_blocks((size_t)H * W), &part))) return rc;
+    return viz_launch_finite_max(ctx, B, H, W, x, part, max_out);
+}

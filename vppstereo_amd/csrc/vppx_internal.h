@@ -134,6 +134,9 @@ enum WsSlot {
     WS_SCALE_HOST_D, // vppx_occ_vpp_rsgm_scaled_host: device copy of disp_small
     WS_METRICS_PART, // guided_metrics: one partial record per (frame, block) (metrics_kernels.hip)
     WS_METRICS_OUT,  // vppx_guided_metrics_host: device copy of the result records
+    WS_VIZ_PART,     // vppx_finite_max_dev: one partial maximum per (frame, block) (viz_kernels.hip)
+    WS_VIZ_OUT,      // the _host renderers: device copy of the pictures
+    WS_VIZ_AUX,      // vppx_colorize_host: device copies of max_val and the colour table
     WS_NUM
 };
 
@@ -471,6 +474,18 @@ int metrics_blocks_per_frame(size_t npx); // a function of the frame's shape onl
 // (valid_is_u8); partials: B * metrics_blocks_per_frame(Ho * Wo) records of METRICS_PARTIAL_BYTES; errormap may be null
 int metrics_launch(vppx_ctx *ctx, int B, int Ho, int Wo, const float *disp, int Hg, int Wg, int gt_scale, const float *gt,
                    const void *valid, int valid_is_u8, void *partials, VppxMetrics *out, float *errormap);
+
+// viz_kernels.hip (utils.py:17-79, test.py:318-343): pictures uint8 [B,H,W,3], dilation fused (0 and 1: none)
+#define VIZ_MAX_DILATION VPPX_VIZ_MAX_DILATION
+#define VIZ_FMAX_MAX_BLOCKS 64
+int viz_launch_error_colors(vppx_ctx *ctx, int B, int H, int W, const float *errors, const float *mask, double scale, int bgr,
+                            int dilation, u8 *out); // mask may be null
+// out: six planes [6][B,H,W,3] in the reference's key order; only the planes whose bit is set in `which` are written
+int viz_launch_guided(vppx_ctx *ctx, int B, int H, int W, const float *disp, const float *gt, const float *valid, double scale,
+                      int dilation, unsigned which, u8 *out);
+int viz_launch_colorize(vppx_ctx *ctx, int B, int H, int W, const float *x, const float *max_val, const u8 *lut, int dilation, u8 *out);
+int viz_finite_max_blocks(size_t npx); // a function of the frame's shape only
+int viz_launch_finite_max(vppx_ctx *ctx, int B, int H, int W, const float *x, float *part, float *out); // part: B * viz_finite_max_blocks
 
 // occ_kernels (in vpp_kernels.hip)
 int occ_launch(vppx_ctx *ctx, int B, int H, int W, const float *hints, int rx, int ry, double l, double g,

@@ -299,6 +299,87 @@ class Engine:
                                                     _ptr(m), _ptr(errormap)))
         return m
 
+    # ---- pictures (utils.py:17-79, test.py:318-343): viz_kernels.hip ----
+    def _viz_out(self, shape, out):
+        torch = self.torch
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8, device=self.device)
+        self._chk(out, torch.uint8, len(shape), "out", shape)
+        return out
+
+    @staticmethod
+    def _viz_dilation(dilation):
+        d = int(dilation)
+        if d < 0:
+            raise ValueError(f"dilation {d} (>= 0)")
+        if d > _lib.VIZ_MAX_DILATION:
+            raise ValueError(f"dilation {d} is above this build's limit of {_lib.VIZ_MAX_DILATION}")
+        return d
+
+    def error_colors(self, errors, mask=None, scale=1, bgr=True, dilation=1, out=None):
+        """utils.color_error_image_kitti (utils.py:17-36) for a batch on the device, no synchronisation (vppx_error_colors_dev).
+        errors: float32 [B,H,W]; mask: float32 [B,H,W] or None (mask == 0 is black).  Returns uint8 [B,H,W,3]; the dilation
+        (cv2.dilate with a d x d box, fused with the colouring) is 0 or 1 for none."""
+        torch = self.torch
+        self._chk(errors, torch.float32, 3, "errors")
+        B, H, W = errors.shape
+        if mask is not None:
+            self._chk(mask, torch.float32, 3, "mask", (B, H, W))
+        if not float(scale) > 0:
+            raise ValueError(f"scale {scale} (> 0)")
+        d = self._viz_dilation(dilation)
+        out = self._viz_out((B, H, W, 3), out)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_error_colors_dev(self.ctx.handle, B, H, W, _ptr(errors), _ptr(mask), float(scale), int(bool(bgr)), d,
+                                                  _ptr(out)))
+        return out
+
+    def guided_visualize(self, disp, gt, valid, scale=1, dilation=7, which=None, out=None):
+        """utils.guided_visualize (utils.py:39-79) for a batch on the device, no synchronisation (vppx_guided_visualize_dev).
+        disp, gt, valid: float32 [B,H,W] (valid == 0 is black).  which: None (all six maps), one of the reference's keys, an
+        iterable of keys or a VPPX_VIZ_* bit mask: only those maps are computed.  out: uint8 [6,B,H,W,3] to write into (the
+        planes not selected are left alone).  Returns a dict keyed like the reference's, of uint8 [B,H,W,3] views of `out`."""
+        torch = self.torch
+        self._chk(disp, torch.float32, 3, "disp")
+        B, H, W = disp.shape
+        self._chk(gt, torch.float32, 3, "gt", (B, H, W))
+        self._chk(valid, torch.float32, 3, "valid", (B, H, W))
+        if not float(scale) > 0:
+            raise ValueError(f"scale {scale} (> 0)")
+        d = self._viz_dilation(dilation)
+        w = _lib.viz_which(which)
+        out = self._viz_out((6, B, H, W, 3), out)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_guided_visualize_dev(self.ctx.handle, B, H, W, _ptr(disp), _ptr(gt), _ptr(valid), float(scale), d, w,
+                                                      _ptr(out)))
+        return {k: out[n] for n, k in enumerate(_lib.VIZ_KEYS) if w >> n & 1}
+
+    def colorize(self, x, max_val, lut, dilation=0, out=None):
+        """The colour-mapped map of test.py:325-326, :343 for a batch on the device, no synchronisation (vppx_colorize_dev):
+        lut[uint8(clamp(x, 0, max_val) / max_val * 255)].  x: float32 [B,H,W]; max_val: float32 [B], one per frame
+        (`finite_max`); lut: uint8 [256,3], the user colour map cv2.applyColorMap takes.  Returns uint8 [B,H,W,3]."""
+        torch = self.torch
+        self._chk(x, torch.float32, 3, "x")
+        B, H, W = x.shape
+        self._chk(max_val, torch.float32, 1, "max_val", (B,))
+        self._chk(lut, torch.uint8, 2, "lut", (256, 3))
+        d = self._viz_dilation(dilation)
+        out = self._viz_out((B, H, W, 3), out)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_colorize_dev(self.ctx.handle, B, H, W, _ptr(x), _ptr(max_val), _ptr(lut), d, _ptr(out)))
+        return out
+
+    def finite_max(self, x):
+        """test.py:318 per frame: the maximum of x[f] with +-inf replaced by -inf (vppx_finite_max_dev).  x: float32 [B,H,W];
+        returns float32 [B] on the device, no synchronisation."""
+        torch = self.torch
+        self._chk(x, torch.float32, 3, "x")
+        B, H, W = x.shape
+        out = torch.empty((B,), dtype=torch.float32, device=self.device)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_finite_max_dev(self.ctx.handle, B, H, W, _ptr(x), _ptr(out)))
+        return out
+
     def _vpp_rsgm_eval(self, left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
                        validhints, iscale, oscale, disp_small, gt, validgt, metrics_out, errormap):
         torch = self.torch
