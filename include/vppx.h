@@ -609,6 +609,12 @@ int vppx_last_call_parts(vppx_ctx *ctx);
 /* Pieces per line of the last, part-filled layer of waves in the last launch of the W / E register-window kernel (its lines are
  * cut into 2..8 pieces that hand the path state on through memory when that evens out the SIMDs' load); 1 = nothing was cut. */
 int vppx_we_last_pieces(vppx_ctx *ctx);
+/* The same for the last launch of the W + sum + WTA kernel (the route "wsum<12>" of vppx_last_routes). */
+int vppx_wsum_last_pieces(vppx_ctx *ctx);
+/* The default rule of that route, without a context: 1 when an unguided launch of B padded Hp x Wp frames in the fused layout
+ * (vppx_uses_vert() == 3) with largest penalty p2max takes it on a device of `nsimd` SIMDs (4 per compute unit): dmax = 192,
+ * 3 * (24 + p2max) <= 255 and B * Hp / 4 >= 2 * nsimd.  VPPX_VARIANT=wsum / nowsum override it. */
+int vppx_wsum_default_route(int B, int Hp, int Wp, int dmax, int p2max, int nsimd);
 /* The kernel instantiations the last rSGM-bearing call launched, as a comma-separated list in launch order, each one once
  * (a call that ran in parts lists the union over its parts), e.g. "paths<8,24,exact,guided,u16,dirs=ff>,
  * sum_lr<12,u16,8,64,spare,nosw4,general,16,partw>".  Names: paths<lanes per pixel,disparities per lane,exact|partial,
@@ -665,6 +671,9 @@ const char *vppx_stage_name(int i);
  *                       gw16 (lanes per pixel of the line-parallel kernel), we_line (W / E on the line-parallel kernel), we_after (W / E never next to
  *                       an under-filled lock-step launch), we_lq0, we_lq1 (W / E kernel: left-view operands per step / per quad of steps), we_whole (W / E kernel: no line of the last layer of waves is cut into pieces; tests: we_layer=N takes a layer to be N waves, we_mute makes every later piece give up waiting and compute its line from the start, we_stale fills the
  *                       hand-off records of every cut launch with the dword the next launch's flags accept),
+ *                       wsum (the W + sum + WTA kernel -- W path, sum and both WTAs in one pass, the W/E launch makes E only -- for every
+ *                       fused D = 192 launch of 3 frames or more; by default it takes those whose line quads fill two layers of waves),
+ *                       nowsum (never: W/E, then the sum / WTA kernel; tests: wsum_cut=K cuts every line of that kernel into K pieces),
  *                       tests only: fs_fail_submit=K (the K-th batch submit of a frame stream fails with "injected submit failure",
  *                       before it enqueues anything), fs_fail_from=K (every submit from the K-th on),
  *                       maxdist_lds, maxdist_global (one-wave maxDistance kernels) */

@@ -1073,6 +1073,7 @@ struct We12Args {
     int piece_groups; // groups per piece (the last piece takes what is left)
     u32 serial;       // launch serial in the flags (a flag of another launch never matches)
     long long timeout_ticks;
+    int east_only;    // the E lines only (W is made by sgm_wsum12_kernel): units enumerate (row block, frame)
 #ifdef VPPX_EXPERIMENT
     unsigned long long *trace; // experiment builds: per block (start, end) of the 100 MHz wall clock and HW_ID / XCC_ID (tools/we_trace.py)
 #endif
@@ -1349,7 +1350,7 @@ __global__ void __launch_bounds__(64 * WE12_WPB) sgm_we12_kernel(We12Args a)
         flag = a.hand + (size_t)a.ntail * WE12_WPB * (a.pieces - 1) * (64 * (DPL / 2)) + tl;
     }
     // `unit` enumerates (row block, direction, frame); XCD-aware like sgm_paths_kernel: frame f -> XCD f % 8
-    const int nrb = a.Hp / (4 * WE12_WPB), per_frame = nrb * 2;
+    const int nrb = a.Hp / (4 * WE12_WPB), per_frame = a.east_only ? nrb : nrb * 2;
     int f, within;
     if (a.B % 8 == 0) {
         const int id = unit, xcd = id & 7, j = id >> 3;
@@ -1359,7 +1360,7 @@ __global__ void __launch_bounds__(64 * WE12_WPB) sgm_we12_kernel(We12Args a)
         f = unit / per_frame;
         within = unit % per_frame;
     }
-    const int east = within / nrb, rb = within % nrb;
+    const int east = a.east_only ? 1 : within / nrb, rb = within % nrb;
     const int y = rb * (4 * WE12_WPB) + (int)(threadIdx.x >> 4);
     const int lg = threadIdx.x & 15;
     const int Wp = a.Wp;
@@ -1393,7 +1394,7 @@ __global__ void __launch_bounds__(64 * WE12_WPB) sgm_we12_kernel(We12Args a)
 }
 
 static int launch_we12(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gray, const u32 *cl, const u32 *cr, const u16 *p2lut, int p1,
-                       void *paths)
+                       void *paths, bool east_only)
 {
     We12Args a;
     a.gray = gray; a.cl = cl; a.cr = cr; a.p2lut = p2lut; a.out = (u8 *)paths;
@@ -1401,7 +1402,8 @@ static int launch_we12(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gr
     a.p1 = p1 < 0 ? 0 : (p1 > 231 ? 231 : p1); // exact for P1 >= P2max (see rsgm_launch_paths)
     a.vol_elems = (size_t)B * Hp * Wp * D;
     // ---- the last layer of waves, cut into pieces (We12Args; VPPX_VARIANT=we_whole keeps every line whole)
-    const int nunits = B * 2 * (Hp / (4 * WE12_WPB)), dpl = D / 16, ngroups = (Wp + dpl - 1) / dpl;
+    a.east_only = east_only ? 1 : 0; // (the E volume stays where it is: the second of the two)
+    const int nunits = B * (east_only ? 1 : 2) * (Hp / (4 * WE12_WPB)), dpl = D / 16, ngroups = (Wp + dpl - 1) / dpl;
     a.hand = nullptr; a.n_whole = nunits; a.pieces = 1; a.piece_groups = ngroups; a.serial = 0; a.timeout_ticks = 0;
     a.ntail = 0; a.tail_base = nunits; a.tail_pitch = 8; a.lead = 0;
     {
@@ -1574,9 +1576,9 @@ int rsgm_launch_paths(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gra
     {
         // W + E of the fused layout at D = 128 / 192 / 256: the register-window kernel (VPPX_VARIANT we_line: the line kernel)
         const int we12 = !ctx->knobs.we_line;
-        if (we12 && (D == 128 || D == 192 || D == 256) && a.dir_mask == 0x11 && src == COST_CENSUS && elem_bytes == 1 && Hp % 16 == 0 && Wp % 16 == 0 &&
+        if (we12 && (D == 128 || D == 192 || D == 256) && (a.dir_mask == 0x11 || a.dir_mask == 0x10) && src == COST_CENSUS && elem_bytes == 1 && Hp % 16 == 0 && Wp % 16 == 0 &&
             Wp >= 16 && gw_override <= 0)
-            return launch_we12(ctx, B, Hp, Wp, D, gray, cl, cr, p2lut, p1, paths);
+            return launch_we12(ctx, B, Hp, Wp, D, gray, cl, cr, p2lut, p1, paths, a.dir_mask == 0x10);
     }
     if (D <= 64) {
         if (gw_override == 8) return launch_paths_t<8, 8>(ctx, a, B, src, elem_bytes);
@@ -3647,6 +3649,478 @@ int rsgm_launch_sum_wta_lr(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const vo
     }
     if (nvol == 8) return launch_lr_d<u16, 8>(ctx, vp, B, Hp, Wp, D, disp_l, disp_r, fu, sub, false);
     return 1;
+}
+
+// ---------------------------------------------------------------------------------------
+// W path + sum + left and right WTA in ONE pass over a line quad (fused layout, D = 192, byte volumes): sgm_wsum12_kernel.
+// The W scan of sgm_we12_kernel holds L_W(x, .) of its pixel in registers in the very layout the WTA wants (16 lanes x 12
+// disparities, packed u16 pairs).  Here it adds the pixel's E, N3 and S3 bytes to them (S = L_W + E + N3 + S3), decides the
+// left view from S right away (top2_reduce / deferred top2_final, S[best -+ 1] through a wave-private LDS scratch) and feeds the
+// right view, so that W is never stored and nothing is read back and widened a second time.
+// Right view as a register window.  Right pixel xr = c - d collects S[c][d] over 192 consecutive columns c, in the order
+// d = 0, 1, ...: a lane keeps (smallest key, second key) of the 12 right pixels its 12 disparities feed at this column; per
+// column every slot takes its cell's key (v_med3 + v_min) and the window moves on by one slot: register renaming inside a lane
+// (the loop is unrolled by 12), one DPP row_shr:1 per register between lanes; the slot that leaves lane 15 is a finished right
+// pixel, 16 of them are collected (one per lane) and decided together.
+// Keys are S << 22 | d << 14 | nb << 4 with nb = min(S[c-1][d-1], S[c+1][d+1]), the smaller of the cell's two neighbours ALONG
+// the right pixel's own diagonal (1023 where there is none), which is why the right view runs one column behind the scan.
+// The first minimum wins (d sits above nb), the second key carries the second-smallest VALUE, and the rule of DESIGN section 5
+// item 5 -- valid if unique, or if the runner-up VALUE sits at best - 1 or best + 1 -- needs of the neighbours only
+// "is one of them equal to the runner-up", i.e. nb == second: both neighbours are candidates themselves (best + 1 only if it
+// lies inside the search range, and then it is a cell of this diagonal), hence >= the runner-up value.
+// The lines of the last, part-filled layer of waves are cut into pieces exactly like sgm_we12_kernel's (same placement, priority,
+// flag protocol and bounded wait); a hand-off record is the lane's L pairs, the S pairs of the last two columns, the 24 window
+// registers, the collected finished right pixels and the kept left keys.  Flags live in a fixed region in FRONT of the records.
+// ---------------------------------------------------------------------------------------
+#define WSUM_REC 47        // dwords per lane of a hand-off record
+#define WSUM_FLAG_CAP 4096 // flag words in front of the records (one per tail line; a launch with more tail lines is not cut)
+struct WsumArgs {
+    const u8 *gray;
+    const u32 *cl;
+    const u32 *cr;
+    const u16 *p2lut;
+    const u8 *vol[3];       // E, N3, S3: [B][Hp][Wp][D] bytes
+    float *disp_l, *disp_r; // [B][Hp][Wp]
+    int Hp, Wp, p1, B;
+    u32 factor_uniq;
+    u32 *hand;              // WSUM_FLAG_CAP flag words (serial << 4 | pieces done), then [tail line][piece boundary][WSUM_REC][64 lanes]
+    int n_whole, lead, ntail, tail_base, tail_pitch, pieces, piece_groups; // as in We12Args
+    u32 serial;
+    long long timeout_ticks;
+};
+
+struct WsumState {
+    u32 L[6], minpk, prevI;
+    u32 r[12], T[3][4], CL[4], GI[4]; // as We12State (W direction, a census word and a gray byte per step)
+    u32 V[4][9];                      // E, N3, S3 words of this column and of the three ahead
+    u32 S[3][6];                      // S pairs of columns x (being made), x - 1 and x - 2, rotating
+    u32 m1[12], m2[12];               // the right view's window, rotating
+    u32 c1, c2;                       // finished right pixels, one per lane
+    u32 kl[3];                        // the left pixel this lane keeps (top2_reduce)
+};
+
+struct WsumLane {
+    __amdgpu_buffer_rsrc_t cr, cl, gray, vol[3];
+    int cr_off, cl_off, gray_off, vol_off, dbase;
+    u32 dh[3];     // (d >> 2) of the lane's pairs 0-1, 2-3, 4-5, in both halves
+    float *dl_row; // the lane's row of the two results
+    float *dr_row;
+};
+
+__device__ __forceinline__ u32 med3_u32(u32 a, u32 b, u32 c)
+{
+    u32 r;
+    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+__device__ __forceinline__ void wsum_load_quad(u32 (&T)[4], const WsumLane &ln, int Q) // columns 4Q .. 4Q+3 bring in cr[x - dbase]
+{
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ln.cr, ln.cr_off, 16 * Q, 0);
+    T[0] = v.x; T[1] = v.y; T[2] = v.z; T[3] = v.w;
+}
+
+template <int SLOT>
+__device__ __forceinline__ void wsum_load_vols(WsumState &st, const WsumLane &ln, int xa)
+{
+#pragma unroll
+    for (int v = 0; v < 3; v++) {
+        const u32x3 t = __builtin_amdgcn_raw_buffer_load_b96(ln.vol[v], ln.vol_off, 192 * xa, 2 /* nt */);
+        st.V[SLOT][3 * v] = t.x; st.V[SLOT][3 * v + 1] = t.y; st.V[SLOT][3 * v + 2] = t.z;
+    }
+}
+
+// Iteration x of a line: the W step, the sum and the left view of column x (x < Wp), then the right view's window at column
+// c = x - 1 (its "next" neighbours are the S of column x; past the row end the window only drains).
+template <int K>
+__device__ __forceinline__ void wsum_step(WsumState &st, const u32 *s_lut, u16 *scr, const WsumLane &ln, u32 fu, int t0, int te, int Wp,
+                                          u32 P1pk, bool masked, int nquads)
+{
+    constexpr int NP = 6, DPL = 12, NQ = 3, D = 192, AHEAD = 2;
+    constexpr u32 BIG = 0x03FF03FFu; // "no neighbour" (no S reaches 1023: 2 * 85 + 2 * 255)
+    const int x = t0 + K;
+    if (x >= te) return; // (wave-uniform)
+    const int l16 = threadIdx.x & 15;
+    constexpr int SN = K % 3, SC = (K + 2) % 3, SP = (K + 1) % 3;
+    if (x < Wp) {
+        // ---- the W step: we12_step<false, 12, K, 0> without its store
+        st.r[K] = st.T[K / 4][K % 4];
+        const u32 clv = st.CL[K % 4];
+        const u32 I = st.GI[K % 4];
+        {
+            int xa = x + 4;
+            xa = xa < Wp ? xa : Wp - 1;
+            st.CL[K % 4] = __builtin_amdgcn_raw_buffer_load_b32(ln.cl, ln.cl_off, 4 * xa, 0);
+            st.GI[K % 4] = (u32)__builtin_amdgcn_raw_buffer_load_b8(ln.gray, ln.gray_off, xa, 0);
+        }
+        if (K % 4 == 0) {
+            int Q = x / 4 + AHEAD;
+            Q = Q < nquads ? Q : nquads - 1;
+            wsum_load_quad(st.T[(K / 4 + AHEAD) % NQ], ln, Q);
+        }
+        if (K % 2 == 0) { // the volumes' bytes of columns x + 2 and x + 3, back to back (they share 128-byte lines)
+            const int xa = x + 2 < Wp ? x + 2 : Wp - 1, xb = x + 3 < Wp ? x + 3 : Wp - 1;
+            wsum_load_vols<(K + 2) % 4>(st, ln, xa);
+            wsum_load_vols<(K + 3) % 4>(st, ln, xb);
+        }
+        u32 C[NP];
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const u32 w0 = st.r[(K - 2 * i + 2 * DPL) % DPL];
+            const u32 w1 = st.r[(K - 2 * i - 1 + 2 * DPL) % DPL];
+            const u32 c0 = __popc(clv ^ w0), c1 = __popc(clv ^ w1);
+            C[i] = (c1 << 16) | c0;
+        }
+        if (masked) { // d > x: InvalidDispCost (a real, wave-uniform branch: we12_step)
+            const int lim = x - ln.dbase;
+#pragma unroll
+            for (int i = 0; i < NP; i++) {
+                const u32 keep = (2 * i <= lim ? 0xFFFFu : 0u) | (2 * i + 1 <= lim ? 0xFFFF0000u : 0u);
+                u32 c = (C[i] & keep) | (~keep & (INVALID_DISP_COST | (INVALID_DISP_COST << 16)));
+                asm volatile("" : "+v"(c));
+                C[i] = c;
+            }
+        }
+        const u32 di = __builtin_amdgcn_sad_u8(I, st.prevI, 0u);
+        const u32 P2pk = s_lut[di];
+        u32 inact[NP];
+#pragma unroll
+        for (int i = 0; i < NP; i++) inact[i] = 0;
+        sgm_update<NP, true, 16, true, true>(st.L, C, C, C, P1pk, P2pk, st.minpk, inact, false, false);
+        st.prevI = I;
+        // ---- S = L_W + E + N3 + S3 as u16 pairs (<= 680: plain 32-bit adds)
+        u32(&S)[NP] = st.S[SN];
+#pragma unroll
+        for (int i = 0; i < NP / 2; i++) {
+            const u32 e = st.V[K % 4][i], n3 = st.V[K % 4][3 + i], s3 = st.V[K % 4][6 + i];
+            S[2 * i] = st.L[2 * i] + __builtin_amdgcn_perm(e, e, 0x0c010c00u) + __builtin_amdgcn_perm(n3, n3, 0x0c010c00u) +
+                       __builtin_amdgcn_perm(s3, s3, 0x0c010c00u);
+            S[2 * i + 1] = st.L[2 * i + 1] + __builtin_amdgcn_perm(e, e, 0x0c030c02u) + __builtin_amdgcn_perm(n3, n3, 0x0c030c02u) +
+                           __builtin_amdgcn_perm(s3, s3, 0x0c030c02u);
+        }
+        // ---- left view: the pixel's column goes to this wave's own scratch (LDS keeps a wave's accesses in order: no barrier)
+        u16 *col = scr + (threadIdx.x >> 4) * D;
+        {
+            u32x2 *sw = (u32x2 *)(col + ln.dbase);
+#pragma unroll
+            for (int i = 0; i < NP / 2; i++) sw[i] = u32x2{S[2 * i], S[2 * i + 1]};
+        }
+        const int n = (x < D - 1 ? x : D - 1) + 1; // wave-uniform
+        const Top2 tr = top2_reduce<DPL, 16>(S, ln.dbase, n, D, [&](int d) -> u32 { return col[d]; });
+        if (l16 == (x & 15)) {
+            st.kl[0] = tr.g1; st.kl[1] = tr.g2; st.kl[2] = tr.nbv;
+        }
+        if ((x & 15) == 15) { // lane i keeps pixel x - 15 + i: 64 pixels decided at once
+            const int xi = x - 15 + l16;
+            const int ni = (xi < D - 1 ? xi : D - 1) + 1;
+            ln.dl_row[xi] = top2_final<DPL>(st.kl[0], st.kl[1], st.kl[2], ni, D, fu, true, xi >= 1 && xi <= Wp - 2);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NP; i++) st.S[SN][i] = BIG; // past the row end: column Wp - 1 has no "next" neighbours
+    }
+    // ---- right view, one column behind
+    const int c = x - 1;
+    if (c < 0) return;
+    constexpr int KC = (K + 11) % 12; // c mod 12
+    if (c < Wp) {
+        const u32(&Sp)[NP] = st.S[SP];
+        const u32(&Sc)[NP] = st.S[SC];
+        const u32(&Sn)[NP] = st.S[SN];
+        const u32 left_in = dpp_keep<0x111>(BIG, Sp[NP - 1]); // row_shr:1: lane - 1's last pair of column c - 1
+        const u32 right_in = dpp_keep<0x101>(BIG, Sn[0]);     // row_shl:1: lane + 1's first pair of column c + 1
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const u32 pa = __builtin_amdgcn_alignbit(Sp[i], i > 0 ? Sp[(i + NP - 1) % NP] : left_in, 16);   // S[c-1][d-1] of the pair's two cells
+            const u32 na = __builtin_amdgcn_alignbit(i < NP - 1 ? Sn[(i + 1) % NP] : right_in, Sn[i], 16); // S[c+1][d+1]
+            const u32 nb = pk_min(pa, na);
+            const u32 s2 = (Sc[i] << 6) | ln.dh[i >> 1];                        // per half: S << 6 | d >> 2
+            const u32 n2 = (nb << 4) | ((i & 1) ? 0xC0008000u : 0x40000000u);   // per half: (d & 3) << 14 | nb << 4
+            const u32 klo = __builtin_amdgcn_perm(s2, n2, 0x05040100u), khi = __builtin_amdgcn_perm(s2, n2, 0x07060302u);
+            const int j0 = (2 * i - KC + 12) % 12, j1 = (2 * i + 1 - KC + 12) % 12;
+            st.m2[j0] = med3_u32(st.m1[j0], st.m2[j0], klo);
+            st.m1[j0] = min(st.m1[j0], klo);
+            st.m2[j1] = med3_u32(st.m1[j1], st.m2[j1], khi);
+            st.m1[j1] = min(st.m1[j1], khi);
+        }
+    }
+    // the window moves on: the slot of d = 12 l + 11 goes to lane l + 1 (lane 0 opens an empty one), lane 15's is a finished pixel
+    constexpr int E = (11 - KC + 12) % 12;
+    st.c1 = dpp_keep<0x101>(st.m1[E], st.c1); // lanes 0-14 take lane + 1's, lane 15 its own finished slot
+    st.c2 = dpp_keep<0x101>(st.m2[E], st.c2);
+    st.m1[E] = dpp_keep<0x111>(0xFFFFFFFFu, st.m1[E]);
+    st.m2[E] = dpp_keep<0x111>(0xFFFFFFFFu, st.m2[E]);
+    if ((c & 15) == 15) { // lane i holds the right pixel that left the window at column c - 15 + i
+        const int xr = c - 15 + l16 - (D - 1);
+        if (xr >= 0 && xr < Wp) {
+            const u32 g1 = st.c1, g2 = st.c2;
+            const u32 minc = g1 >> 22, best = (g1 >> 14) & 0xFFu, nb = (g1 >> 4) & 0x3FFu;
+            const u32 sec = g2 == 0xFFFFFFFFu ? 65535u : g2 >> 22; // no second candidate
+            const bool ok = (1024u * minc <= sec * fu) || nb == sec;
+            ln.dr_row[xr] = ok ? (float)best : INVALID_DISP;
+        }
+    }
+}
+
+template <int K0, int KN>
+__device__ __forceinline__ void wsum_steps(WsumState &st, const u32 *s_lut, u16 *scr, const WsumLane &ln, u32 fu, int t0, int te, int Wp,
+                                           u32 P1pk, bool masked, int nquads)
+{
+    if constexpr (K0 < KN) {
+        wsum_step<K0>(st, s_lut, scr, ln, fu, t0, te, Wp, P1pk, masked, nquads);
+        wsum_steps<K0 + 1, KN>(st, s_lut, scr, ln, fu, t0, te, Wp, P1pk, masked, nquads);
+    }
+}
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) sgm_wsum12_kernel(WsumArgs a)
+{
+    constexpr int DPL = 12, NP = 6, NQ = 3, D = 192, AHEAD = 2;
+    __shared__ u32 s_lut[256];
+    __shared__ __attribute__((aligned(16))) u16 s_scr[4 * D];
+    for (int i = threadIdx.x; i < 256; i += 64) s_lut[i] = pk_splat(a.p2lut[i]);
+    __syncthreads();
+    // blocks [0, n_whole) run a line quad each, the blocks behind them a piece of a tail line quad: sgm_we12_kernel
+    int unit = (int)blockIdx.x - a.lead, piece = 0;
+    if (unit < 0) return;
+    const int Wp = a.Wp, nquads = Wp / 4;
+    const int ngroups = (Wp + DPL - 1) / DPL;
+    int g0 = 0, g1 = ngroups;
+    const u32 *hand_in = nullptr;
+    u32 *hand_out = nullptr, *flag = nullptr;
+    if (a.pieces > 1 && unit >= a.n_whole) {
+        if (unit < a.tail_base) return;
+        const int k = unit - a.tail_base, tail = k % a.tail_pitch;
+        piece = k / a.tail_pitch;
+        if (tail >= a.ntail) return;
+        __builtin_amdgcn_s_setprio(3);
+        unit = a.n_whole + tail;
+        g0 = piece * a.piece_groups;
+        g1 = piece == a.pieces - 1 ? ngroups : g0 + a.piece_groups;
+        u32 *rec = a.hand + WSUM_FLAG_CAP + ((size_t)tail * (a.pieces - 1)) * (64 * WSUM_REC);
+        hand_in = piece > 0 ? rec + (size_t)(piece - 1) * (64 * WSUM_REC) : nullptr;
+        hand_out = rec + (size_t)piece * (64 * WSUM_REC); // (the last piece never writes)
+        flag = a.hand + tail;
+    }
+    // `unit` enumerates (row block, frame); frame f -> XCD f % 8 as in sgm_we12_kernel
+    const int nrb = a.Hp / 4;
+    int f, rb;
+    if (a.B % 8 == 0) {
+        const int xcd = unit & 7, j = unit >> 3;
+        f = (j / nrb) * 8 + xcd;
+        rb = j % nrb;
+    } else {
+        f = unit / nrb;
+        rb = unit % nrb;
+    }
+    const int y = rb * 4 + (int)(threadIdx.x >> 4);
+    const int lg = threadIdx.x & 15, lane = threadIdx.x & 63;
+    const size_t fpix = (size_t)f * a.Hp * Wp;
+    const int npf = a.Hp * Wp; // (npf * D < 2^32: checked by the launcher)
+    WsumLane ln;
+    ln.dbase = DPL * lg;
+    ln.cr = __builtin_amdgcn_make_buffer_rsrc((void *)(a.cr + fpix - 512), 0, (npf + 512) * 4, 0x00020000);
+    ln.cl = __builtin_amdgcn_make_buffer_rsrc((void *)(a.cl + fpix), 0, npf * 4, 0x00020000);
+    ln.gray = __builtin_amdgcn_make_buffer_rsrc((void *)(a.gray + fpix), 0, npf, 0x00020000);
+#pragma unroll
+    for (int v = 0; v < 3; v++) ln.vol[v] = __builtin_amdgcn_make_buffer_rsrc((void *)(a.vol[v] + fpix * D), 0, (int)((u32)npf * (u32)D), 0x00020000);
+    const int rowoff = y * Wp;
+    ln.cr_off = (rowoff + 512 - ln.dbase) * 4;
+    ln.cl_off = rowoff * 4;
+    ln.gray_off = rowoff;
+    ln.vol_off = rowoff * D + ln.dbase;
+#pragma unroll
+    for (int k = 0; k < 3; k++) ln.dh[k] = pk_splat((u32)(3 * lg + k));
+    ln.dl_row = a.disp_l + fpix + rowoff;
+    ln.dr_row = a.disp_r + fpix + rowoff;
+    const u32 P1pk = pk_splat((u32)a.p1);
+
+    WsumState st;
+    if (g0 > 0) { // wait for the piece before this one: bounded, then the line from its start (we12_line)
+        const long long t_start = (long long)__builtin_amdgcn_s_memrealtime();
+        bool there = false;
+        for (;;) {
+            const u32 v = (u32)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            if ((v >> 4) == (a.serial & 0x0FFFFFFFu) && (int)(v & 15u) >= piece) { there = true; break; }
+            if ((long long)__builtin_amdgcn_s_memrealtime() - t_start > a.timeout_ticks) break;
+            __builtin_amdgcn_s_sleep(32);
+        }
+        if (!there) g0 = 0;
+        g0 = __builtin_amdgcn_readfirstlane(g0);
+    }
+    if (g0 > 0) { // the record comes through the XCD's L2 (all pieces of a line are on one XCD: we12_line)
+        asm volatile("" ::: "memory");
+        const u32 *hp = hand_in + lane;
+        u32 w[WSUM_REC];
+#pragma unroll
+        for (int i = 0; i < WSUM_REC; i++) w[i] = __hip_atomic_load(hp + 64 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int i = 0; i < NP; i++) { st.L[i] = w[i]; st.S[1][i] = w[6 + i]; st.S[2][i] = w[12 + i]; }
+#pragma unroll
+        for (int i = 0; i < 12; i++) { st.m1[i] = w[18 + i]; st.m2[i] = w[30 + i]; }
+        st.c1 = w[42]; st.c2 = w[43];
+        st.kl[0] = w[44]; st.kl[1] = w[45]; st.kl[2] = w[46];
+        u32 m = st.L[0];
+#pragma unroll
+        for (int i = 1; i < NP; i++) m = pk_min(m, st.L[i]);
+        u32 mm = min(m & 0xFFFFu, m >> 16);
+        mm = grp_min_u32<16>(mm);
+        st.minpk = pk_splat(mm);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NP; i++) { st.L[i] = 0; st.S[1][i] = 0x03FF03FFu; st.S[2][i] = 0x03FF03FFu; }
+#pragma unroll
+        for (int i = 0; i < 12; i++) { st.m1[i] = 0xFFFFFFFFu; st.m2[i] = 0xFFFFFFFFu; }
+        st.minpk = 0;
+        st.c1 = st.c2 = 0xFFFFFFFFu;
+        st.kl[0] = st.kl[1] = st.kl[2] = 0;
+    }
+#pragma unroll
+    for (int i = 0; i < NP; i++) st.S[0][i] = 0x03FF03FFu;
+    const int tb = g0 * DPL; // first column of this piece
+    {
+        // the census window before column tb: cr[x-dbase-(DPL-1) .. x-dbase-1] (x = tb) in slots 1..DPL-1
+        const int so = 4 * (tb - DPL);
+        u32 blk[DPL];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ln.cr, ln.cr_off + so + 16 * q, 0, 0);
+            blk[4 * q] = v.x; blk[4 * q + 1] = v.y; blk[4 * q + 2] = v.z; blk[4 * q + 3] = v.w;
+        }
+#pragma unroll
+        for (int m = 0; m < DPL; m++) st.r[m] = blk[m];
+    }
+#pragma unroll
+    for (int q = 0; q < AHEAD; q++) wsum_load_quad(st.T[q], ln, tb / 4 + q < nquads ? tb / 4 + q : nquads - 1);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int xa = tb + i < Wp ? tb + i : Wp - 1;
+        st.CL[i] = __builtin_amdgcn_raw_buffer_load_b32(ln.cl, ln.cl_off, 4 * xa, 0);
+        st.GI[i] = (u32)__builtin_amdgcn_raw_buffer_load_b8(ln.gray, ln.gray_off, xa, 0);
+    }
+    wsum_load_vols<0>(st, ln, tb);
+    wsum_load_vols<1>(st, ln, tb + 1 < Wp ? tb + 1 : Wp - 1);
+    if (tb == 0) st.prevI = st.GI[0];
+    else st.prevI = (u32)__builtin_amdgcn_raw_buffer_load_b8(ln.gray, ln.gray_off, tb - 1, 0);
+    // the last piece also drains the window: 191 right pixels are still in it after column Wp - 1, and the collected ones are
+    // decided every 16 columns (Wp + 191 is the first such column at which every pixel of the row has been decided)
+    const bool last = g1 * DPL >= Wp;
+    const int te = last ? Wp + D + 1 : g1 * DPL;
+    for (int t0 = tb; t0 < te; t0 += DPL) {
+        const bool masked = t0 < D - 1;
+        wsum_steps<0, DPL>(st, s_lut, s_scr, ln, a.factor_uniq, t0, te, Wp, P1pk, masked, nquads);
+    }
+    if (!last && !(a.serial & 0x10000000u)) { // the next piece of this line continues from here (tests mute this)
+        u32 *hp = hand_out + lane;
+        u32 w[WSUM_REC];
+#pragma unroll
+        for (int i = 0; i < NP; i++) { w[i] = st.L[i]; w[6 + i] = st.S[1][i]; w[12 + i] = st.S[2][i]; }
+#pragma unroll
+        for (int i = 0; i < 12; i++) { w[18 + i] = st.m1[i]; w[30 + i] = st.m2[i]; }
+        w[42] = st.c1; w[43] = st.c2;
+        w[44] = st.kl[0]; w[45] = st.kl[1]; w[46] = st.kl[2];
+#pragma unroll
+        for (int i = 0; i < WSUM_REC; i++) __hip_atomic_store(hp + 64 * i, w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the record is in the XCD's L2 before the flag goes out
+        if (lane == 0) __hip_atomic_store(flag, (a.serial << 4) | (u32)(piece + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+
+// Does the W + sum + WTA kernel take this launch?  (D = 192 byte volumes of the fused layout whose three-path sums fit a byte;
+// the caller has checked the layout.)  By default only where the line quads fill at least two whole layers of waves: the
+// W-only scan has half the waves of the W/E launch, and below two layers the imbalance of the uncut layers eats what the fold
+// saves.  VPPX_VARIANT=wsum forces it from 3 frames on (tests), nowsum keeps the three kernels.
+bool rsgm_wsum_shape_ok(int Hp, int Wp, int D, int maxp2)
+{
+    return D == 192 && 3 * (24 + maxp2) <= 255 && Hp % 16 == 0 && Wp % 16 == 0 && Wp >= 16 && (size_t)Hp * Wp * D < ((size_t)1 << 32);
+}
+bool rsgm_wsum_default(int B, int Hp, int Wp, int D, int maxp2, int nsimd)
+{
+    return rsgm_wsum_shape_ok(Hp, Wp, D, maxp2) && (long long)B * (Hp / 4) >= 2LL * nsimd;
+}
+bool rsgm_wsum_eligible(const vppx_ctx *ctx, int B, int Hp, int Wp, int D, int maxp2, int nsimd)
+{
+    if (ctx->knobs.wsum == 0 || ctx->knobs.we_line || ctx->knobs.gw > 0) return false;
+    if (ctx->knobs.wsum == 1) return rsgm_wsum_shape_ok(Hp, Wp, D, maxp2) && B >= 3;
+    return rsgm_wsum_default(B, Hp, Wp, D, maxp2, nsimd);
+}
+
+int rsgm_device_simds(vppx_ctx *ctx)
+{
+    static int nsimd_of[VPPX_MAX_DEVICES] = {};
+    const int dv = ctx->device & (VPPX_MAX_DEVICES - 1);
+    if (!nsimd_of[dv]) {
+        int ncu = 0;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu <= 0) ncu = 256;
+        nsimd_of[dv] = 4 * ncu;
+    }
+    return nsimd_of[dv];
+}
+
+int rsgm_launch_wsum(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gray, const u32 *cl, const u32 *cr, const u16 *p2lut, int p1,
+                     const void *vol_e, const void *vol_n3, const void *vol_s3, float *disp_l, float *disp_r, u32 fu)
+{
+    if (D != 192 || Hp % 16 != 0 || Wp % 16 != 0 || Wp < 16 || (size_t)Hp * Wp * D >= ((size_t)1 << 32)) {
+        vppx_set_error("rsgm_launch_wsum: shape not supported");
+        return VPPX_E_UNSUPPORTED;
+    }
+    WsumArgs a;
+    a.gray = gray; a.cl = cl; a.cr = cr; a.p2lut = p2lut;
+    a.vol[0] = (const u8 *)vol_e; a.vol[1] = (const u8 *)vol_n3; a.vol[2] = (const u8 *)vol_s3;
+    a.disp_l = disp_l; a.disp_r = disp_r;
+    a.Hp = Hp; a.Wp = Wp; a.B = B;
+    a.p1 = p1 < 0 ? 0 : (p1 > 231 ? 231 : p1); // exact for P1 >= P2max (rsgm_launch_paths)
+    a.factor_uniq = fu;
+    // ---- the last layer of waves, cut into pieces: the model of launch_we12 ("wsum_cut=K": K pieces on every line)
+    const int nunits = B * (Hp / 4), ngroups = (Wp + 11) / 12;
+    a.hand = nullptr; a.n_whole = nunits; a.pieces = 1; a.piece_groups = ngroups; a.serial = 0; a.timeout_ticks = 0;
+    a.ntail = 0; a.tail_base = nunits; a.tail_pitch = 8; a.lead = 0;
+    {
+        const int nsimd_dev = rsgm_device_simds(ctx);
+        const int nsimd = ctx->knobs.we_layer > 0 ? ctx->knobs.we_layer : nsimd_dev;
+        int tail = nunits % nsimd, pieces = 1;
+        const bool can_cut = ctx->knobs.we_split && !ctx->capturing && ctx->vert3_probed && ctx->v3.ok;
+        if (can_cut && ctx->knobs.wsum_cut > 1) {
+            tail = nunits;
+            pieces = ctx->knobs.wsum_cut < 8 ? ctx->knobs.wsum_cut : 8;
+            pieces = pieces <= ngroups ? pieces : ngroups;
+        } else if (can_cut && nunits > nsimd && tail > 0) {
+            double best = 0.9;
+            for (int c = 2; c <= 8 && c <= ngroups; c++) {
+                const double load = (double)(((long long)tail * c + nsimd - 1) / nsimd) / c;
+                if (load < best - 1e-9) { best = load; pieces = c; }
+            }
+        }
+        if (pieces > 1 && tail <= WSUM_FLAG_CAP) {
+            const size_t dwords = WSUM_FLAG_CAP + (size_t)tail * (pieces - 1) * (64 * WSUM_REC);
+            u32 *hand;
+            int rc = ws_get(ctx, WS_WSUM_HAND, dwords, &hand);
+            if (rc) return rc;
+            if (ctx->wsum_hand_seen != (void *)hand || ctx->wsum_hand_cap != ctx->ws[WS_WSUM_HAND].cap) {
+                // fresh memory may hold anything; from here on only this context's serials live in the flag region, and the
+                // records lie behind it whatever the geometry: no payload can ever be read as a flag
+                VPPX_HIP(hipMemsetAsync(hand, 0, WSUM_FLAG_CAP * sizeof(u32), ctx->stream));
+                ctx->wsum_hand_seen = (void *)hand;
+                ctx->wsum_hand_cap = ctx->ws[WS_WSUM_HAND].cap;
+            }
+            a.hand = hand; a.n_whole = nunits - tail; a.pieces = pieces; a.piece_groups = ngroups / pieces;
+            a.ntail = tail; a.tail_base = (a.n_whole + 7) & ~7; a.tail_pitch = (tail + 7) & ~7;
+            a.lead = ctx->knobs.we_layer > 0 ? 8 : nsimd_dev / 4; // one per CU (sgm_we12_kernel)
+            a.serial = (++ctx->we_serial) & 0x0FFFFFFFu;
+            if (a.serial == 0) a.serial = (++ctx->we_serial) & 0x0FFFFFFFu;
+            a.timeout_ticks = 20LL * 100000LL; // 20 ms of the 100 MHz wall clock
+            if (ctx->knobs.we_mute) { // tests: no piece passes its state on, every later piece gives up after 0.2 ms
+                a.timeout_ticks = 20000LL;
+                a.serial |= 0x10000000u;
+            }
+        }
+    }
+    const dim3 grid((unsigned)(a.pieces > 1 ? a.lead + a.tail_base + a.pieces * a.tail_pitch : nunits));
+    sgm_wsum12_kernel<<<grid, 64, 0, ctx->stream>>>(a);
+    VPPX_CHECK_LAUNCH();
+    route_note(ctx, "wsum<12>");
+    ctx->wsum_last_pieces = a.pieces;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -238,6 +238,12 @@ extern "C" int vppx_create(vppx_ctx **out, int device)
                 const size_t wl = v.find("we_layer=");
                 if (wl != std::string::npos) ctx->knobs.we_layer = atoi(v.c_str() + wl + 9);
             }
+            if (has("wsum")) ctx->knobs.wsum = 1;
+            if (has("nowsum")) ctx->knobs.wsum = 0;
+            {
+                const size_t wc = v.find("wsum_cut=");
+                if (wc != std::string::npos) ctx->knobs.wsum_cut = atoi(v.c_str() + wc + 9);
+            }
             if (has("we_lq0")) ctx->knobs.we_lq = 0;
             if (has("we_lq1")) ctx->knobs.we_lq = 1;
 #ifdef VPPX_EXPERIMENT
@@ -729,6 +735,7 @@ static int run_aggregation(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeo
     const size_t npp = (size_t)g.B * g.Hp * g.Wp;
     const size_t ncell = npp * g.D;
     int nvol;
+    ctx->wsum_route = false;
     if ((rc = lockstep_check(ctx))) return rc; // an earlier fused launch lost its lock step: say so before queueing more
     if (hints && validhints) {
         // --guided (rsgm.py:265-268): the hint pixels' re-weighted cost rows are written out compactly, every other
@@ -770,6 +777,9 @@ static int run_aggregation(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeo
         // them -- 16 or 8 rows per wave, the right-image census window kept in registers and shifted by one word per step:
         // 19 instead of 26 instructions per pixel, bit-exact -- and measured 1.88-2.10 ms (16 rows, 168 VGPRs: 2-3 waves per
         // SIMD cannot cover the walk's dependent chain) and 2.6 ms (8 rows: 96 VGPRs only with spills) against 1.94-2.00.)
+        // W folded into the sum / WTA pass (sgm_wsum12_kernel): this launch then makes the E lines only
+        ctx->wsum_route = vert3 && elem_bytes == 1 && rsgm_wsum_eligible(ctx, g.B, g.Hp, g.Wp, g.D, maxp2, rsgm_device_simds(ctx));
+        const int we_dirs = ctx->wsum_route ? 0x10 : 0x11;
         bool we_launched = false; // (launch_vert has run W/E next to its under-filled launch)
         auto launch_we = [&]() -> int {
             // event pairs around this launch too: inside a step it follows a run of small kernels (or the previous step's
@@ -782,7 +792,7 @@ static int run_aggregation(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeo
             if (exp_env("VPPX_EXP_TWICE") && (rc = rsgm_launch_paths(ctx, g.B, g.Hp, g.Wp, g.D, gl, cl, cr, nullptr, lut_d, p.p1, paths, 1, 0x11))) return rc;
 #endif
             if (timed) VPPX_HIP(hipEventRecord(ctx->we_ev[0][slot], ctx->stream));
-            const int r = rsgm_launch_paths(ctx, g.B, g.Hp, g.Wp, g.D, gl, cl, cr, nullptr, lut_d, p.p1, paths, 1, 0x11);
+            const int r = rsgm_launch_paths(ctx, g.B, g.Hp, g.Wp, g.D, gl, cl, cr, nullptr, lut_d, p.p1, paths, 1, we_dirs);
             if (timed) {
                 VPPX_HIP(hipEventRecord(ctx->we_ev[1][slot], ctx->stream));
                 ctx->we_calls++;
@@ -1085,8 +1095,11 @@ static int rsgm_core(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeom &g, 
     if ((rc = ws_get(ctx, WS_DISP_R1, npp, &dr1))) return rc;
     const u32 fu = uniq_factor(p.uniqueness);
     // rsgm.py:141-142: matchWTA_SSE + subPixelRefine(.., 0) are always applied to the left map
-    rc = rsgm_launch_sum_wta_lr(ctx, g.B, g.Hp, g.Wp, g.D, vols, nvol, elem_bytes, dl0, dr0, fu, 1,
-                                (hints && validhints) ? 0 : 24 + maxp2);
+    if (ctx->wsum_route) // W is made, summed and decided in one pass; vols[0] (W) holds nothing of this call
+        rc = rsgm_launch_wsum(ctx, g.B, g.Hp, g.Wp, g.D, gl, cl, cr, lut_d, p.p1, vols[1], vols[2], vols[3], dl0, dr0, fu);
+    else
+        rc = rsgm_launch_sum_wta_lr(ctx, g.B, g.Hp, g.Wp, g.D, vols, nvol, elem_bytes, dl0, dr0, fu, 1,
+                                    (hints && validhints) ? 0 : 24 + maxp2);
     if (rc < 0) return rc;
     if (rc == 0) {
         stage_mark(ctx, ST_SUM_WTA);
@@ -2106,6 +2119,11 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
 
 extern "C" int vppx_last_call_parts(vppx_ctx *ctx) { return ctx ? ctx->last_parts : 0; }
 extern "C" int vppx_we_last_pieces(vppx_ctx *ctx) { return ctx ? ctx->we_last_pieces : 0; }
+extern "C" int vppx_wsum_last_pieces(vppx_ctx *ctx) { return ctx ? ctx->wsum_last_pieces : 0; }
+extern "C" int vppx_wsum_default_route(int B, int Hp, int Wp, int dmax, int p2max, int nsimd)
+{
+    return rsgm_wsum_default(B, Hp, Wp, dmax, p2max, nsimd) ? 1 : 0;
+}
 
 // The parts of a call and, for an evaluating call whose map is complete with them, its metrics: once, over the whole batch,
 // behind the last part -- and inside the capture when the call is being captured.

@@ -93,6 +93,7 @@ enum WsSlot {
     WS_V3ERR,        // device-side copy of the fused kernel's error word (void_if_lost_kernel)
     WS_WE_TRACE,     // experiment builds: per-block wall-clock trace of the W/E kernel
     WS_WE_HAND,      // W/E kernel: path states handed from piece to piece of the split tail lines + a flag per line (We12Args)
+    WS_WSUM_HAND,    // W + sum + WTA kernel: a fixed flag region, then the records handed from piece to piece of its tail lines (WsumArgs)
     WS_DSI,          // materialised cost volume (stage API), or the hint pixels' cost rows of a guided call
     WS_GUIDED_MAP,   // guided call: row index of every padded pixel (+ the row counter behind it)
     WS_DISP_L0,
@@ -175,6 +176,8 @@ struct vppx_ctx {
         int fs_fail_submit = 0; // "fs_fail_submit=K" (tests): the K-th batch submit of a frame stream fails before it enqueues anything
         int fs_fail_from = 0;   // "fs_fail_from=K" (tests): ... and every submit from the K-th on
         int we_lq = -1;       // "we_lq0" / "we_lq1": the W/E kernel's left-view operand loads (per step / per quad of steps); default by launch
+        int wsum = -1;        // "wsum": the W + sum + WTA kernel for every fused D = 192 launch of 3 frames or more; "nowsum": never; default by shape
+        int wsum_cut = 0;     // "wsum_cut=K" (tests): that kernel cuts EVERY line into K pieces
         int sum_blocks = 0;   // (experiment builds) "sum_blocks=N": forced number of blocks of the sum / WTA kernel
         unsigned long long guided_part_bytes = 48ull << 30; // VPPX_GUIDED_PART_MB: volume budget of one part of a guided batch
     } knobs;
@@ -198,6 +201,10 @@ struct vppx_ctx {
     size_t we_hand_cap = 0;
     int we_hand_geom[3] = {0, 0, 0}; // (ntail, pieces, DPL) of the last cut W/E launch: where its flags lie (We12Args)
     int we_last_pieces = 1;        // pieces per tail line of the last W/E launch (vppx_we_last_pieces)
+    void *wsum_hand_seen = nullptr; // the W + sum + WTA kernel's hand-off buffer as its flag region was last cleared (rsgm_launch_wsum)
+    size_t wsum_hand_cap = 0;
+    int wsum_last_pieces = 1;      // pieces per tail line of its last launch
+    bool wsum_route = false;       // the running call's aggregation leaves W to that kernel (run_aggregation)
     bool we_beside_vert = false;   // the W/E launch being queued runs next to a lock-step launch (run_aggregation)
     unsigned long long *draws_dst = nullptr; // device [B]: where the fused call leaves every frame's draw count (set per call by a frame stream)
     int last_sum_nvol = 0;         // volumes the last fused sum / WTA launch added (4: fused layout, 8: eight paths) and its
@@ -415,6 +422,11 @@ int rsgm_paths_elem_bytes(int D, int maxp2);
 // fused sum + left/right WTA; returns 1 (not an error) when the shape is not covered
 // max_path_value: upper bound of one path value (Cmax + P2max); 0 = unknown
 size_t rsgm_sum_lds_bytes(const vppx_ctx *ctx, int D, int nvol);
+bool rsgm_wsum_default(int B, int Hp, int Wp, int D, int maxp2, int nsimd);
+bool rsgm_wsum_eligible(const vppx_ctx *ctx, int B, int Hp, int Wp, int D, int maxp2, int nsimd);
+int rsgm_device_simds(vppx_ctx *ctx);
+int rsgm_launch_wsum(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u8 *gray, const u32 *cl, const u32 *cr, const u16 *p2lut, int p1,
+                     const void *vol_e, const void *vol_n3, const void *vol_s3, float *disp_l, float *disp_r, u32 fu);
 int rsgm_launch_sum_wta_lr(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const void *const *vols, int nvol, int elem_bytes,
                            float *disp_l, float *disp_r, u32 factor_uniq, int do_subpixel, int max_path_value);
 int rsgm_launch_wta_left(vppx_ctx *ctx, int B, int Hp, int Wp, int D, const u16 *S, float *disp, u32 factor_uniq);

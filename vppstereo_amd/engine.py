@@ -637,6 +637,10 @@ class Engine:
         """Pieces per line of the last layer of waves in the last W/E launch of the fused layout (1: no line was cut)."""
         return int(self.lib.vppx_we_last_pieces(self.ctx.handle))
 
+    def wsum_last_pieces(self):
+        """The same for the last launch of the W + sum + WTA kernel (route "wsum<12>")."""
+        return int(self.lib.vppx_wsum_last_pieces(self.ctx.handle))
+
     def last_routes(self):
         """The kernel instantiations the last rSGM-bearing call launched, in launch order, each once (vppx_last_routes),
         e.g. ["paths<4,16,exact,census,u8,dirs=ff>", "sum_lr<4,u8,8,64,spare,sw4,fast,16,fullw>"]."""
