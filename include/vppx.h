@@ -19,6 +19,7 @@
  *   occlusion_heuristic()               filter.py:246-292           vppx_occlusion_heuristic_host/_dev
  *   test.py:158-225 (VPP -> rSGM per frame)                         vppx_vpp_rsgm_dev (fused, batched)
  *   guided_metrics()                    losses.py:13-24             vppx_guided_metrics_host / _dev, vppx_occ_vpp_rsgm_eval_dev
+ *   sample_hints()                      losses.py:5-10              vppx_sample_hints_host / _dev, vppx_occ_vpp_rsgm_sampled_dev
  *   color_error_image_kitti()           utils.py:17-36              vppx_error_colors_host / _dev
  *   guided_visualize()                  utils.py:39-79              vppx_guided_visualize_host / _dev
  *   test.py:318, :325-326, :343 (max_val, applyColorMap)            vppx_finite_max_dev, vppx_colorize_host / _dev
@@ -391,6 +392,46 @@ int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op, const Vpp
                                const float *validgt, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
                                float *disp_small, VppxMetrics *metrics_out, float *errormap);
 
+/* ---- hint sampling (losses.py:5-10 sample_hints; test.py:125-129) ---------------------------------------------------------
+ * What test.py does first for every dataset without raw hints: hints = src * (rand_like(src) < probability) * (validsrc > 0)
+ * with torch's CPU generator.  Reproduced bit for bit: frame f of a call equals torch.manual_seed(seed + f (mod 2^32)) followed
+ * by sample_hints(src, validsrc > 0, probability) on the CPU.  torch draws one tempered MT19937 word y per pixel in row-major
+ * order -- valid or not -- and keeps k = y & 0xFFFFFF (rand = k * 2^-24); rand < probability compares in float32, which is
+ * k < T with T = clamp(ceil((double)(float)probability * 2^24), 0, 2^24) (vppx_sample_threshold; NaN gives 0).  Then, with
+ * sel = validsrc > 0 && k < T: hints = sel ? src : +0.0f (src unchanged, NaN / inf included; anything at an unselected pixel
+ * gives 0), validhints = sel ? 1.0f : 0.0f.  Any probability is legal.  A frame's stream starts with its own seed (the
+ * reference's one generator running on through all frames is a serial dependency between frames, as with the colours). */
+typedef struct VppxSampleParams {
+    double probability;  /* [0.05]  --guideperc */
+    uint32_t seed;       /* [1]     frame f samples with seed + f */
+    uint32_t reserved0;
+    uint64_t reserved1;
+} VppxSampleParams;
+void vppx_sample_params_default(VppxSampleParams *p);
+uint32_t vppx_sample_threshold(double probability);
+/* src, validsrc, hints_out, validhints_out (may be NULL): float32 [B,H,W].  Device pointers, stream-ordered, no synchronisation;
+ * one workgroup per frame walks the generator, so frames of a batch run in parallel.  VPPX_E_INVALID_ARG with nothing launched:
+ * a NULL required pointer, B / H / W <= 0, H * W > 2^31. */
+int vppx_sample_hints_dev(vppx_ctx *ctx, const VppxSampleParams *smp, int B, int H, int W, const float *src, const float *validsrc,
+                          float *hints_out, float *validhints_out);
+/* The same on host pointers, synchronous. */
+int vppx_sample_hints_host(vppx_ctx *ctx, const VppxSampleParams *smp, int B, int H, int W, const float *src, const float *validsrc,
+                           float *hints_out, float *validhints_out);
+/* vppx_occ_vpp_rsgm_eval_dev on hints sampled on the way: test.py:125-252 in one call.  In place of g / validhints: smp, the
+ * source pair src / validsrc (float32 [B,H,W]; both NULL = sample from gt / validgt, which are then required) and `guided`
+ * (!= 0: --guided, the sampled mask is the validhints, test.py:207-208).  The sampled maps live in the context's workspace and
+ * enter the path where a caller's would: at full size, in front of the --iscale decimation.  ep, gt, validgt and metrics_out may
+ * all be NULL: sampled, not evaluated (errormap then NULL as well).  hints_out / validhints_out (float32 [B,H,W], may be NULL)
+ * receive the sampled maps in launch-stream order.  With vppx_set_pipeline the sampling is the first kernel of the front stage
+ * (two sets of maps alternate); with vppx_set_graph_mode it is launched in front of the replayed graph, so a new seed does not
+ * re-capture; a call that runs in parts samples once, frame f with smp->seed + f. */
+int vppx_occ_vpp_rsgm_sampled_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                  const VppxScaleParams *sp, const VppxEvalParams *ep, const VppxSampleParams *smp, int B, int H, int W,
+                                  int C, const uint8_t *left, const uint8_t *right, const float *src, const float *validsrc, int guided,
+                                  const uint8_t *g_occ, const float *gt, const float *validgt, uint8_t *conf_out, uint8_t *l_vpp,
+                                  uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out, float *errormap,
+                                  float *hints_out, float *validhints_out);
+
 /* ---- pictures (utils.py:17-79; test.py:318-343) --------------------------------------------------------------------------
  * What test.py --outdir renders per frame, for a batch: inputs float32 [B,H,W], pictures uint8 [B,H,W,3].  Every call takes a
  * `dilation` d >= 0, applied to the coloured picture as the reference does with cv2.dilate(img, np.ones((d, d))): per channel
@@ -461,6 +502,7 @@ int vppx_finite_max_dev(vppx_ctx *ctx, int B, int H, int W, const float *x, floa
 #define VPPX_FS_GUIDED 8
 #define VPPX_FS_METRICS 16  /* every push brings gt + validgt (vppx_fstream_push_eval); pop can return the frame's VppxMetrics */
 #define VPPX_FS_NO_DISP 32  /* needs VPPX_FS_METRICS: disparities are not copied out; pop's disp_out must be NULL */
+#define VPPX_FS_SAMPLE 64   /* the hints are sampled on the device (vppx_fstream_create_sampled, vppx_fstream_push_sampled) */
 typedef struct vppx_fstream vppx_fstream;
 int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int batch,
                         int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out);
@@ -507,6 +549,21 @@ int vppx_fstream_push_eval(vppx_fstream *fs, const uint8_t *left, const uint8_t 
  * be NULL here, and must be on a VPPX_FS_NO_DISP stream (VPPX_E_INVALID_ARG otherwise, also from vppx_fstream_pop). */
 int vppx_fstream_pop_eval(vppx_fstream *fs, float *disp_out, uint8_t *l_vpp_out, uint8_t *r_vpp_out, uint8_t *conf_out,
                           uint64_t *draws_out, VppxMetrics *metrics_out, int *got);
+/* A sampling stream (flags must hold VPPX_FS_SAMPLE, smp is required): no push brings hints, every batch runs through
+ * vppx_occ_vpp_rsgm_sampled_dev; frame f of the stream (counted from its creation) samples with smp->seed + f, as it draws its
+ * colours from srand(vp->seed + f).  ep != NULL makes it an evaluating stream as well (flags must then hold VPPX_FS_METRICS, and
+ * must not otherwise); VPPX_FS_GUIDED feeds the sampled mask as validhints.  A batch re-run after a lost lock step samples again:
+ * the same bytes. */
+int vppx_fstream_create_sampled(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                const VppxScaleParams *sp, const VppxEvalParams *ep, const VppxSampleParams *smp, int batch, int depth,
+                                int H, int W, int C, int flags, int copy_threads, vppx_fstream **out);
+/* One frame in.  src / validsrc (float32 [H,W], together or both NULL) are what the hints are sampled from; the ring keeps one
+ * byte per pixel of validsrc > 0.  On a VPPX_FS_METRICS stream gt / validgt are required and src may be NULL: the ring then
+ * holds no hints plane at all for the frame and the gt already there is the source.  (A frame whose kind of source differs
+ * from the batch being filled starts a new batch.)  The other push calls fail with VPPX_E_INVALID_ARG on a sampling stream,
+ * this one on any other stream. */
+int vppx_fstream_push_sampled(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const uint8_t *g_occ, const float *src,
+                              const float *validsrc, const float *gt, const float *validgt);
 /* Frames pushed since creation, frames of the batch being filled, frames submitted and not yet popped, batches re-run
  * after a lost lock step (any pointer may be NULL). */
 int vppx_fstream_counts(vppx_fstream *fs, int64_t *pushed, int64_t *filling, int64_t *unpopped, int64_t *reruns);

@@ -38,9 +38,12 @@ EXPORTS = [
     "vppx_rsgm_front_dev", "vppx_rsgm_guided_rows_dev", "vppx_rsgm_mid_dev",
     "vppx_error_colors_dev", "vppx_error_colors_host", "vppx_guided_visualize_dev", "vppx_guided_visualize_host",
     "vppx_colorize_dev", "vppx_colorize_host", "vppx_finite_max_dev",
+    "vppx_sample_params_default", "vppx_sample_threshold", "vppx_sample_hints_dev", "vppx_sample_hints_host", "vppx_occ_vpp_rsgm_sampled_dev",
+    "vppx_fstream_create_sampled", "vppx_fstream_push_sampled",
 ]
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 FS_METRICS, FS_NO_DISP = 16, 32
+FS_SAMPLE = 64
 VIZ_KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')  # utils.guided_visualize's dict keys (utils.py:79), VPPX_VIZ_* bit order
 VIZ_ALL = 63
 VIZ_MAX_DILATION = 31
@@ -76,6 +79,10 @@ class VppxScaleParams(C.Structure):
 
 class VppxEvalParams(C.Structure):
     _fields_ = [("gt_scale", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class VppxSampleParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("seed", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_uint64)]
 
 
 class VppxMetrics(C.Structure):
@@ -234,6 +241,17 @@ def load():
             getattr(lib, "vppx_guided_visualize_" + sfx).argtypes = [vp, i, i, i, vp, vp, vp, d, i, u, vp]
             getattr(lib, "vppx_colorize_" + sfx).argtypes = [vp, i, i, i, vp, vp, vp, i, vp]
         lib.vppx_finite_max_dev.argtypes = [vp, i, i, i, vp, vp]
+        pm = C.POINTER(VppxSampleParams)
+        lib.vppx_sample_params_default.argtypes = [pm]
+        lib.vppx_sample_params_default.restype = None
+        lib.vppx_sample_threshold.argtypes = [d]
+        lib.vppx_sample_threshold.restype = C.c_uint32
+        lib.vppx_sample_hints_dev.argtypes = [vp, pm, i, i, i, vp, vp, vp, vp]
+        lib.vppx_sample_hints_host.argtypes = [vp, pm, i, i, i, vp, vp, vp, vp]
+        lib.vppx_occ_vpp_rsgm_sampled_dev.argtypes = [vp, po, pv, pr, ps, pe, pm, i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                      vp, vp, vp, vp]
+        lib.vppx_fstream_create_sampled.argtypes = [vp, po, pv, pr, ps, pe, pm, i, i, i, i, i, i, i, C.POINTER(vp)]
+        lib.vppx_fstream_push_sampled.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = lib
         return lib
 
@@ -397,6 +415,24 @@ def eval_params(**kw):
     p = VppxEvalParams()
     load().vppx_eval_params_default(C.byref(p))
     return _fill(p, kw)
+
+
+def sample_params(**kw):
+    """VppxSampleParams: probability = --guideperc (default 0.05), seed (default 1)."""
+    p = VppxSampleParams()
+    load().vppx_sample_params_default(C.byref(p))
+    return _fill(p, kw)
+
+
+def sample_threshold(p):
+    """T of the sampling rule (include/vppx.h): torch's ``rand < p`` on float32 rand = k * 2**-24 is exactly ``k < T`` with
+    T = clamp(ceil(float64(float32(p)) * 2**24), 0, 2**24); NaN selects nothing.  Host arithmetic, no library call."""
+    pf = float(np.float32(p))
+    if not pf > 0.0:
+        return 0
+    if pf >= 1.0:
+        return 1 << 24
+    return min(int(np.ceil(pf * 16777216.0)), 1 << 24)
 
 
 def check_gt_shape(Hg, Wg, gt_scale, Ho, Wo, what="gt"):

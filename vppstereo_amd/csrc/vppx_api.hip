@@ -303,6 +303,7 @@ extern "C" void vppx_destroy(vppx_ctx *ctx)
     if (ctx->ev_occ_done) (void)hipEventDestroy(ctx->ev_occ_done);
     if (ctx->ev_inputs_auto) (void)hipEventDestroy(ctx->ev_inputs_auto);
     if (ctx->ev_scaled) (void)hipEventDestroy(ctx->ev_scaled);
+    if (ctx->ev_sampled) (void)hipEventDestroy(ctx->ev_sampled);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -2022,6 +2023,150 @@ extern "C" int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op
     VPPX_PIPE_KEEP(ctx);
     return vppx_eval_call_internal(ctx, op, vp, rp, sp, ep, B, H, W, C, left, right, g, g_occ, validhints, gt, validgt, 0, conf_out, l_vpp, r_vpp,
                                    disp_out, disp_small, metrics_out, errormap);
+}
+
+// ---------------------------------------------------------------------------------------
+// hint sampling (losses.py:5-10 sample_hints; test.py:125-129) on torch's CPU random stream
+// ---------------------------------------------------------------------------------------
+extern "C" void vppx_sample_params_default(VppxSampleParams *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->probability = 0.05;
+    p->seed = 1;
+}
+
+extern "C" uint32_t vppx_sample_threshold(double probability) { return sample_threshold(probability); }
+
+static int check_sample_args(const char *name, const VppxSampleParams *smp, int B, int H, int W)
+{
+    if (!smp) { vppx_set_error("%s: NULL argument", name); return VPPX_E_INVALID_ARG; }
+    if (B < 1 || H < 1 || W < 1 || (size_t)H * W > ((size_t)1 << 31)) {
+        vppx_set_error("%s: bad shape (B %d, %d x %d)", name, B, H, W);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vppx_sample_hints_dev(vppx_ctx *ctx, const VppxSampleParams *smp, int B, int H, int W, const float *src, const float *validsrc,
+                                     float *hints_out, float *validhints_out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx); // (no workspace)
+    int rc;
+    if (!smp || !src || !validsrc || !hints_out) { vppx_set_error("vppx_sample_hints_dev: NULL argument"); return VPPX_E_INVALID_ARG; }
+    if ((rc = check_sample_args("vppx_sample_hints_dev", smp, B, H, W))) return rc;
+    return sample_launch(ctx, B, (size_t)H * W, src, validsrc, 0, hints_out, validhints_out, nullptr, smp->seed, sample_threshold(smp->probability));
+}
+
+extern "C" int vppx_sample_hints_host(vppx_ctx *ctx, const VppxSampleParams *smp, int B, int H, int W, const float *src, const float *validsrc,
+                                      float *hints_out, float *validhints_out)
+{
+    VPPX_ENTER(ctx);
+    int rc;
+    if (!smp || !src || !validsrc || !hints_out) { vppx_set_error("vppx_sample_hints_host: NULL argument"); return VPPX_E_INVALID_ARG; }
+    if ((rc = check_sample_args("vppx_sample_hints_host", smp, B, H, W))) return rc;
+    const size_t bytes = (size_t)B * H * W * sizeof(float);
+    void *ds, *dv, *dh, *dvh = nullptr;
+    if ((rc = upload(ctx, WS_STAGE_A, src, bytes, &ds))) return rc;
+    if ((rc = upload(ctx, WS_STAGE_B, validsrc, bytes, &dv))) return rc;
+    if ((rc = ws_reserve(ctx, WS_STAGE_C, bytes, &dh))) return rc;
+    if (validhints_out && (rc = ws_reserve(ctx, WS_STAGE_E, bytes, &dvh))) return rc;
+    if ((rc = sample_launch(ctx, B, (size_t)H * W, (const float *)ds, dv, 0, (float *)dh, (float *)dvh, nullptr, smp->seed,
+                            sample_threshold(smp->probability))))
+        return rc;
+    if ((rc = download(ctx, hints_out, dh, bytes))) return rc;
+    if (dvh && (rc = download(ctx, validhints_out, dvh, bytes))) return rc;
+    VPPX_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// The sampled call: the hints (and, guided, their mask) of the batch are sampled into the workspace in front of the scaled /
+// evaluating call, which then takes them exactly where a caller's maps would enter.  With vppx_set_pipeline the sampling is the
+// first kernel of the front stage, as the resize of a scaled call is: it waits for what every front stage waits for and writes
+// the set of maps the previous call did not use.  src == NULL: gt / validgt are the source.  validsrc / validgt: float32, or one
+// byte per pixel (a frame stream's ring).
+int vppx_sampled_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
+                               const VppxEvalParams *ep, const VppxSampleParams *smp, int B, int H, int W, int C, const uint8_t *left,
+                               const uint8_t *right, const float *src, const void *validsrc, int vsrc_is_u8, int guided, const uint8_t *g_occ,
+                               const float *gt, const void *validgt, int vgt_is_u8, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
+                               float *disp_small, VppxMetrics *metrics_out, float *errormap, float *hints_out, float *validhints_out)
+{
+    int rc;
+    const char *const name = "vppx_occ_vpp_rsgm_sampled";
+    if (!vp || !rp || !smp || !left || !right || !disp_out) { vppx_set_error("%s: NULL argument", name); return VPPX_E_INVALID_ARG; }
+    const bool eval = gt || validgt || metrics_out;
+    if (eval && (!gt || !validgt || !metrics_out)) { vppx_set_error("%s: gt, validgt and metrics_out go together", name); return VPPX_E_INVALID_ARG; }
+    if (!eval && (ep || errormap)) { vppx_set_error("%s: ep / errormap without gt, validgt and metrics_out", name); return VPPX_E_INVALID_ARG; }
+    if ((src != nullptr) != (validsrc != nullptr)) { vppx_set_error("%s: src and validsrc go together", name); return VPPX_E_INVALID_ARG; }
+    if (!src) {
+        if (!gt) { vppx_set_error("%s: src is NULL and there is no gt to sample from", name); return VPPX_E_INVALID_ARG; }
+        src = gt;
+        validsrc = validgt;
+        vsrc_is_u8 = vgt_is_u8;
+    }
+    if ((rc = check_sample_args(name, smp, B, H, W))) return rc;
+    VppxScaleParams one = {1, 1};
+    if (!sp) sp = &one;
+    {   // everything the call itself would refuse is refused before the sampling is queued
+        int h, w, Ho, Wo, s = 1;
+        if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
+        if ((rc = check_frames(B, H, W, C))) return rc;
+        if ((rc = check_frames(B, h, w, C))) return rc;
+        if ((rc = check_vpp_params(*vp))) return rc;
+        if ((rc = check_rsgm_params(*rp))) return rc;
+        if (eval && (rc = check_metrics_args(name, ep, B, Ho, Wo, H, W, &s))) return rc;
+    }
+    if ((rc = lockstep_check(ctx))) return rc;
+    const bool piped = pipeline_applies(ctx);
+    const int set = piped ? ctx->sample_parity : 0;
+    const size_t np = (size_t)B * H * W;
+    float *gs, *vs = nullptr;
+    if ((rc = ws_get(ctx, set ? WS_SAMPLE_G1 : WS_SAMPLE_G0, np, &gs))) return rc;
+    if ((guided || validhints_out) && (rc = ws_get(ctx, set ? WS_SAMPLE_V1 : WS_SAMPLE_V0, np, &vs))) return rc;
+    const u32 T = sample_threshold(smp->probability);
+    if (piped) {
+        if (!ctx->ev_sampled) VPPX_HIP(hipEventCreateWithFlags(&ctx->ev_sampled, hipEventDisableTiming));
+        if ((rc = front_begin(ctx))) return rc;
+        rc = sample_launch(ctx, B, (size_t)H * W, src, validsrc, vsrc_is_u8, gs, vs, nullptr, smp->seed, T);
+        const hipError_t e = rc ? hipSuccess : hipEventRecord(ctx->ev_sampled, ctx->stream);
+        ctx->stream = ctx->main_saved;
+        ctx->front_active = false;
+        if (rc) return rc;
+        if (e != hipSuccess) { vppx_set_error("hipEventRecord failed: %s", hipGetErrorString(e)); return VPPX_E_HIP; }
+        ctx->sample_parity ^= 1;
+        ctx->inputs_ev = (void *)ctx->ev_sampled;
+    } else {
+        if (ctx->inputs_ev) {
+            VPPX_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->inputs_ev, 0));
+            ctx->inputs_ev = nullptr;
+        }
+        if ((rc = sample_launch(ctx, B, (size_t)H * W, src, validsrc, vsrc_is_u8, gs, vs, nullptr, smp->seed, T))) return rc;
+    }
+    if (eval)
+        rc = vppx_eval_call_internal(ctx, op, vp, rp, sp, ep, B, H, W, C, left, right, gs, g_occ, guided ? vs : nullptr, gt, validgt, vgt_is_u8,
+                                     conf_out, l_vpp, r_vpp, disp_out, disp_small, metrics_out, errormap);
+    else
+        rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, left, right, gs, g_occ, guided ? vs : nullptr, conf_out, l_vpp, r_vpp, disp_out, disp_small);
+    ctx->inputs_ev = nullptr; // one-shot, whatever happened
+    if (rc) return rc;
+    // the caller's copies of the maps, in launch-stream order (the launch stream has waited for the front stage by now)
+    if (hints_out) VPPX_HIP(hipMemcpyAsync(hints_out, gs, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (validhints_out) VPPX_HIP(hipMemcpyAsync(validhints_out, vs, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+extern "C" int vppx_occ_vpp_rsgm_sampled_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                             const VppxScaleParams *sp, const VppxEvalParams *ep, const VppxSampleParams *smp, int B, int H, int W,
+                                             int C, const uint8_t *left, const uint8_t *right, const float *src, const float *validsrc, int guided,
+                                             const uint8_t *g_occ, const float *gt, const float *validgt, uint8_t *conf_out, uint8_t *l_vpp,
+                                             uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out, float *errormap,
+                                             float *hints_out, float *validhints_out)
+{
+    VPPX_ENTER(ctx);
+    VPPX_PIPE_KEEP(ctx);
+    return vppx_sampled_call_internal(ctx, op, vp, rp, sp, ep, smp, B, H, W, C, left, right, src, validsrc, 0, guided, g_occ, gt, validgt, 0, conf_out,
+                                      l_vpp, r_vpp, disp_out, disp_small, metrics_out, errormap, hints_out, validhints_out);
 }
 
 // Batches larger than one round of the lock-step kernel are run as consecutive parts of one round each ("batch quantum":

@@ -36,6 +36,11 @@ int vppx_eval_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVp
                             const uint8_t *g_occ, const float *validhints, const float *gt, const void *validgt, int valid_is_u8,
                             uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out,
                             float *errormap); // vppx_api.hip
+int vppx_sampled_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
+                               const VppxEvalParams *ep, const VppxSampleParams *smp, int B, int H, int W, int C, const uint8_t *left,
+                               const uint8_t *right, const float *src, const void *validsrc, int vsrc_is_u8, int guided, const uint8_t *g_occ,
+                               const float *gt, const void *validgt, int vgt_is_u8, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
+                               float *disp_small, VppxMetrics *metrics_out, float *errormap, float *hints_out, float *validhints_out); // vppx_api.hip
 
 namespace {
 
@@ -53,6 +58,7 @@ struct Slot {
     bool submitted = false, verified = false;
     bool out_pending = false; // the batch's kernels are enqueued, its copy-out is not yet (see fs_submit)
     bool out_method_rnd = false;
+    bool has_src = false;  // VPPX_FS_SAMPLE: the batch's frames brought src / validsrc (else its gt / validgt planes are the source)
 };
 
 } // namespace
@@ -79,6 +85,8 @@ struct vppx_fstream {
     size_t in_bytes = 0, out_bytes = 0;
     size_t out_host_bytes = 0;              // the host ring's part of the output area: with VPPX_FS_NO_DISP the map, laid out last, stays on the device
     VppxEvalParams ep = {1, 0};
+    VppxSampleParams smp = {0.05, 1, 0, 0}; // VPPX_FS_SAMPLE: frame f of the stream samples with smp.seed + f
+    size_t o_vsrc = 0;                      // VPPX_FS_SAMPLE: ONE BYTE of validsrc > 0 per pixel (o_hint holds src)
     std::vector<Slot> slots;
     hipStream_t s_in = nullptr, s_out = nullptr;
     CopyPool *pool = nullptr;
@@ -123,7 +131,7 @@ static int fs_free(vppx_fstream *fs)
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                     const VppxEvalParams *ep, bool eval, int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
+                     const VppxEvalParams *ep, bool eval, const VppxSampleParams *smp, int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
 {
     if (!ctx) { vppx_set_error("context is NULL (vppx_create failed? there is no CPU fallback)"); return VPPX_E_NO_DEVICE; }
     if (!out || !vp || !rp) { vppx_set_error("vppx_fstream_create: NULL argument"); return VPPX_E_INVALID_ARG; }
@@ -136,6 +144,10 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     if ((flags & VPPX_FS_MASK) && !op) { vppx_set_error("vppx_fstream_create: VPPX_FS_MASK returns the mask of the occlusion heuristic (op is NULL)"); return VPPX_E_INVALID_ARG; }
     if (eval != ((flags & VPPX_FS_METRICS) != 0)) {
         vppx_set_error("vppx_fstream_create: VPPX_FS_METRICS streams are created with vppx_fstream_create_eval, and only they");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((smp != nullptr) != ((flags & VPPX_FS_SAMPLE) != 0)) {
+        vppx_set_error("vppx_fstream_create: VPPX_FS_SAMPLE streams are created with vppx_fstream_create_sampled (smp not NULL), and only they");
         return VPPX_E_INVALID_ARG;
     }
     if ((flags & VPPX_FS_NO_DISP) && !(flags & VPPX_FS_METRICS)) { vppx_set_error("vppx_fstream_create: VPPX_FS_NO_DISP needs VPPX_FS_METRICS"); return VPPX_E_INVALID_ARG; }
@@ -180,6 +192,7 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     fs->scaled = sp != nullptr;
     if (sp) fs->sp = *sp;
     if (eval && ep) fs->ep = *ep;
+    if (smp) fs->smp = *smp;
     fs->px_s = (size_t)hs * ws;
     fs->img_s = fs->px_s * C;
     fs->px_o = (size_t)Ho * Wo;
@@ -189,7 +202,8 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
     fs->o_right = o; o += up256(fs->img * batch);
     fs->o_hint = o;  o += up256(fs->px * 4 * batch);
     fs->o_gocc = o;  if (flags & VPPX_FS_GOCC) o += up256(fs->px_s * batch);
-    fs->o_valid = o; if (flags & VPPX_FS_GUIDED) o += up256(fs->px * 4 * batch);
+    fs->o_valid = o; if ((flags & VPPX_FS_GUIDED) && !smp) o += up256(fs->px * 4 * batch);
+    fs->o_vsrc = o;  if (smp) o += up256(fs->px * batch);
     fs->o_gt = o;    if (flags & VPPX_FS_METRICS) o += up256(fs->px * 4 * batch);
     fs->o_vgt = o;   if (flags & VPPX_FS_METRICS) o += up256(fs->px * batch);
     fs->in_bytes = o;
@@ -248,7 +262,7 @@ static int fs_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams
 extern "C" int vppx_fstream_create(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
                                    int batch, int depth, int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
 {
-    return fs_create(ctx, op, vp, rp, nullptr, nullptr, false, batch, depth, H, W, C, flags, copy_threads, out);
+    return fs_create(ctx, op, vp, rp, nullptr, nullptr, false, nullptr, batch, depth, H, W, C, flags, copy_threads, out);
 }
 
 extern "C" int vppx_fstream_create_scaled(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
@@ -256,7 +270,7 @@ extern "C" int vppx_fstream_create_scaled(vppx_ctx *ctx, const VppxOccParams *op
                                           vppx_fstream **out)
 {
     const bool unscaled = !sp || (sp->iscale == 1 && sp->oscale == 1);
-    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, nullptr, false, batch, depth, H, W, C, flags, copy_threads, out);
+    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, nullptr, false, nullptr, batch, depth, H, W, C, flags, copy_threads, out);
 }
 
 extern "C" int vppx_fstream_create_eval(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
@@ -264,7 +278,16 @@ extern "C" int vppx_fstream_create_eval(vppx_ctx *ctx, const VppxOccParams *op, 
                                         int copy_threads, vppx_fstream **out)
 {
     const bool unscaled = !sp || (sp->iscale == 1 && sp->oscale == 1);
-    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, ep, true, batch, depth, H, W, C, flags, copy_threads, out);
+    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, ep, true, nullptr, batch, depth, H, W, C, flags, copy_threads, out);
+}
+
+extern "C" int vppx_fstream_create_sampled(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
+                                           const VppxScaleParams *sp, const VppxEvalParams *ep, const VppxSampleParams *smp, int batch, int depth,
+                                           int H, int W, int C, int flags, int copy_threads, vppx_fstream **out)
+{
+    if (!smp) { vppx_set_error("vppx_fstream_create_sampled: smp is NULL"); return VPPX_E_INVALID_ARG; }
+    const bool unscaled = !sp || (sp->iscale == 1 && sp->oscale == 1);
+    return fs_create(ctx, op, vp, rp, unscaled ? nullptr : sp, ep, ep != nullptr, smp, batch, depth, H, W, C, flags, copy_threads, out);
 }
 
 extern "C" void vppx_fstream_destroy(vppx_fstream *fs) { fs_free(fs); }
@@ -345,10 +368,15 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         if (s.submitted) VPPX_HIP(hipStreamWaitEvent(fs->s_in, s.ev_out, 0));
         VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_left, s.h_in + fs->o_left, fs->img * nb, hipMemcpyHostToDevice, fs->s_in));
         VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_right, s.h_in + fs->o_right, fs->img * nb, hipMemcpyHostToDevice, fs->s_in));
-        VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_hint, s.h_in + fs->o_hint, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
+        if (!(fs->flags & VPPX_FS_SAMPLE))
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_hint, s.h_in + fs->o_hint, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
+        else if (s.has_src) { // (a batch sampled from its gt brings no hints plane at all)
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_hint, s.h_in + fs->o_hint, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
+            VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_vsrc, s.h_in + fs->o_vsrc, fs->px * nb, hipMemcpyHostToDevice, fs->s_in));
+        }
         if (fs->flags & VPPX_FS_GOCC)
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gocc, s.h_in + fs->o_gocc, fs->px_s * nb, hipMemcpyHostToDevice, fs->s_in));
-        if (fs->flags & VPPX_FS_GUIDED)
+        if ((fs->flags & VPPX_FS_GUIDED) && !(fs->flags & VPPX_FS_SAMPLE))
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_valid, s.h_in + fs->o_valid, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
         if (fs->flags & VPPX_FS_METRICS) {
             VPPX_HIP(hipMemcpyAsync(s.d_in + fs->o_gt, s.h_in + fs->o_gt, fs->px * 4 * nb, hipMemcpyHostToDevice, fs->s_in));
@@ -369,7 +397,20 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         rc = vppx_inputs_ready_event(ctx, (void *)s.ev_in);
         if (rc) return rc;
         ctx->draws_dst = (vp.method == VPPX_METHOD_RND) ? (unsigned long long *)(s.d_out + fs->o_draws) : nullptr;
-        if (fs->flags & VPPX_FS_METRICS) {
+        if (fs->flags & VPPX_FS_SAMPLE) {
+            // the hints are sampled on the device in front of the batch (a re-run samples again: the same bytes), from the ring's
+            // src and one-byte validity planes or, without them, from its gt planes; frame f of the stream samples with smp.seed + f
+            const bool ev = (fs->flags & VPPX_FS_METRICS) != 0;
+            VppxSampleParams smp = fs->smp;
+            smp.seed = fs->smp.seed + (s.seed - fs->vp.seed);
+            rc = vppx_sampled_call_internal(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, fs->scaled ? &fs->sp : nullptr, ev ? &fs->ep : nullptr,
+                                            &smp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right,
+                                            s.has_src ? (const float *)(s.d_in + fs->o_hint) : nullptr, s.has_src ? s.d_in + fs->o_vsrc : nullptr, 1,
+                                            (fs->flags & VPPX_FS_GUIDED) ? 1 : 0, (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
+                                            ev ? (const float *)(s.d_in + fs->o_gt) : nullptr, ev ? s.d_in + fs->o_vgt : nullptr, 1,
+                                            (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp), nullptr,
+                                            ev ? (VppxMetrics *)(s.d_out + fs->o_metrics) : nullptr, nullptr, nullptr, nullptr);
+        } else if (fs->flags & VPPX_FS_METRICS) {
             // the batch and, behind its post stage on the launch stream, its metrics (a re-run queues them again with the batch):
             // they read the ring's gt and one-byte validity planes, which the inputs event covers like the other inputs
             rc = vppx_eval_call_internal(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, fs->scaled ? &fs->sp : nullptr, &fs->ep, nb, fs->H, fs->W,
@@ -444,18 +485,25 @@ static int fs_close_batch(vppx_fstream *fs)
 }
 
 static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ,
-                   const float *validhints, const float *gt, const float *validgt, const char *name)
+                   const float *validhints, const float *gt, const float *validgt, const char *name, const float *validsrc = nullptr)
 {
-    if (!left || !right || !hints || (((fs->flags & VPPX_FS_GOCC) != 0) != (g_occ != nullptr))) {
+    const bool sampling = (fs->flags & VPPX_FS_SAMPLE) != 0; // hints is the frame's src then (NULL: its gt is the source)
+    if (!left || !right || (!hints && !sampling) || (((fs->flags & VPPX_FS_GOCC) != 0) != (g_occ != nullptr))) {
         vppx_set_error("%s: left, right, hints%s", name, (fs->flags & VPPX_FS_GOCC) ? " and g_occ (VPPX_FS_GOCC)" : "; g_occ only with VPPX_FS_GOCC");
         return VPPX_E_INVALID_ARG;
     }
-    if ((fs->flags & VPPX_FS_GUIDED) && !validhints) { vppx_set_error("%s: validhints is NULL", name); return VPPX_E_INVALID_ARG; }
+    if ((fs->flags & VPPX_FS_GUIDED) && !validhints && !sampling) { vppx_set_error("%s: validhints is NULL", name); return VPPX_E_INVALID_ARG; }
     if ((fs->flags & VPPX_FS_METRICS) && (!gt || !validgt)) { vppx_set_error("%s: gt and validgt are required", name); return VPPX_E_INVALID_ARG; }
     DevGuard g(fs->ctx->device);
     if (fs->fill_count >= fs->batch) {
         // the push that filled this batch could not submit it (its error was returned): submit it now, or take nothing -- a
         // frame `batch` of the slot would lie past its planes, the last one past the pinned block
+        const int rc = fs_close_batch(fs);
+        if (rc) return rc;
+    }
+    if (sampling && fs->fill_count > 0 && fs->slots[fs->fill_batch % fs->depth].has_src != (hints != nullptr)) {
+        // a batch samples from one kind of source: a frame of the other kind starts a new one (results do not depend on where a
+        // batch boundary falls)
         const int rc = fs_close_batch(fs);
         if (rc) return rc;
     }
@@ -466,14 +514,17 @@ static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, 
         return VPPX_E_INVALID_ARG;
     }
     const int i = fs->fill_count;
-    CopyJob jobs[7] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
+    if (i == 0) s.has_src = sampling && hints != nullptr;
+    CopyJob jobs[8] = {{s.h_in + fs->o_left + fs->img * i, left, fs->img},
                        {s.h_in + fs->o_right + fs->img * i, right, fs->img},
                        {s.h_in + fs->o_hint + fs->px * 4 * i, hints, fs->px * 4},
                        {g_occ ? s.h_in + fs->o_gocc + fs->px_s * i : nullptr, g_occ, fs->px_s},
                        {validhints ? s.h_in + fs->o_valid + fs->px * 4 * i : nullptr, validhints, fs->px * 4},
                        {gt ? s.h_in + fs->o_gt + fs->px * 4 * i : nullptr, gt, fs->px * 4},
-                       {validgt ? s.h_in + fs->o_vgt + fs->px * i : nullptr, validgt, fs->px, 1}}; // validgt > 0 as one byte
-    fs->pool->copy(jobs, 7);
+                       {validgt ? s.h_in + fs->o_vgt + fs->px * i : nullptr, validgt, fs->px, 1}, // validgt > 0 as one byte
+                       {validsrc ? s.h_in + fs->o_vsrc + fs->px * i : nullptr, validsrc, fs->px, 1}};
+    if (!hints) jobs[2].dst = nullptr;
+    fs->pool->copy(jobs, 8);
     fs->fill_count++;
     fs->pushed++;
     if (fs->fill_count == fs->batch) return fs_close_batch(fs);
@@ -483,6 +534,10 @@ static int fs_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, 
 extern "C" int vppx_fstream_push(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const float *hints, const uint8_t *g_occ)
 {
     if (!fs) { vppx_set_error("vppx_fstream_push: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_SAMPLE) {
+        vppx_set_error("vppx_fstream_push: the stream was created with VPPX_FS_SAMPLE; push frames with vppx_fstream_push_sampled");
+        return VPPX_E_INVALID_ARG;
+    }
     if (fs->flags & VPPX_FS_METRICS) {
         vppx_set_error("vppx_fstream_push: the stream was created with VPPX_FS_METRICS; push frames with vppx_fstream_push_eval");
         return VPPX_E_INVALID_ARG;
@@ -498,6 +553,10 @@ extern "C" int vppx_fstream_push_guided(vppx_fstream *fs, const uint8_t *left, c
                                         const uint8_t *g_occ, const float *validhints)
 {
     if (!fs) { vppx_set_error("vppx_fstream_push_guided: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_SAMPLE) {
+        vppx_set_error("vppx_fstream_push_guided: the stream was created with VPPX_FS_SAMPLE; push frames with vppx_fstream_push_sampled");
+        return VPPX_E_INVALID_ARG;
+    }
     if (fs->flags & VPPX_FS_METRICS) {
         vppx_set_error("vppx_fstream_push_guided: the stream was created with VPPX_FS_METRICS; push frames with vppx_fstream_push_eval");
         return VPPX_E_INVALID_ARG;
@@ -513,6 +572,10 @@ extern "C" int vppx_fstream_push_eval(vppx_fstream *fs, const uint8_t *left, con
                                       const float *validhints, const float *gt, const float *validgt)
 {
     if (!fs) { vppx_set_error("vppx_fstream_push_eval: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (fs->flags & VPPX_FS_SAMPLE) {
+        vppx_set_error("vppx_fstream_push_eval: the stream was created with VPPX_FS_SAMPLE; push frames with vppx_fstream_push_sampled");
+        return VPPX_E_INVALID_ARG;
+    }
     if (!(fs->flags & VPPX_FS_METRICS)) {
         vppx_set_error("vppx_fstream_push_eval: the stream was created without VPPX_FS_METRICS; push frames with vppx_fstream_push / _push_guided");
         return VPPX_E_INVALID_ARG;
@@ -522,6 +585,21 @@ extern "C" int vppx_fstream_push_eval(vppx_fstream *fs, const uint8_t *left, con
         return VPPX_E_INVALID_ARG;
     }
     return fs_push(fs, left, right, hints, g_occ, validhints, gt, validgt, "vppx_fstream_push_eval");
+}
+
+extern "C" int vppx_fstream_push_sampled(vppx_fstream *fs, const uint8_t *left, const uint8_t *right, const uint8_t *g_occ, const float *src,
+                                         const float *validsrc, const float *gt, const float *validgt)
+{
+    if (!fs) { vppx_set_error("vppx_fstream_push_sampled: stream is NULL"); return VPPX_E_INVALID_ARG; }
+    if (!(fs->flags & VPPX_FS_SAMPLE)) {
+        vppx_set_error("vppx_fstream_push_sampled: the stream was created without VPPX_FS_SAMPLE; push frames with the hints they bring");
+        return VPPX_E_INVALID_ARG;
+    }
+    const bool ev = (fs->flags & VPPX_FS_METRICS) != 0;
+    if (!ev && (gt || validgt)) { vppx_set_error("vppx_fstream_push_sampled: gt / validgt only with VPPX_FS_METRICS"); return VPPX_E_INVALID_ARG; }
+    if ((src != nullptr) != (validsrc != nullptr)) { vppx_set_error("vppx_fstream_push_sampled: src and validsrc go together"); return VPPX_E_INVALID_ARG; }
+    if (!src && !ev) { vppx_set_error("vppx_fstream_push_sampled: src is NULL and the stream has no gt to sample from (VPPX_FS_METRICS)"); return VPPX_E_INVALID_ARG; }
+    return fs_push(fs, left, right, src, g_occ, nullptr, gt, validgt, "vppx_fstream_push_sampled", validsrc);
 }
 
 extern "C" int vppx_fstream_flush(vppx_fstream *fs)

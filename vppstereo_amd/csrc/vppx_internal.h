@@ -138,6 +138,10 @@ enum WsSlot {
     WS_VIZ_PART,     // vppx_finite_max_dev: one partial maximum per (frame, block) (viz_kernels.hip)
     WS_VIZ_OUT,      // the _host renderers: device copy of the pictures
     WS_VIZ_AUX,      // vppx_colorize_host: device copies of max_val and the colour table
+    WS_SAMPLE_G0,    // sampled hints and mask of a sampling call (sample_kernels.hip; two sets: pipelined calls alternate)
+    WS_SAMPLE_V0,
+    WS_SAMPLE_G1,
+    WS_SAMPLE_V1,
     WS_NUM
 };
 
@@ -316,6 +320,9 @@ struct vppx_ctx {
     const void *scale_tab_at = nullptr;
     int scale_parity = 0;
     hipEvent_t ev_scaled = nullptr;
+    // hint sampling in front of a fused call (vppx_occ_vpp_rsgm_sampled_dev): which set of sampled maps the next pipelined call writes
+    int sample_parity = 0;
+    hipEvent_t ev_sampled = nullptr;
     // guided_metrics behind the running fused call (vppx_occ_vpp_rsgm_eval_dev, an evaluating frame stream): queued on the launch
     // stream once the whole batch's map is complete -- behind the last part, inside a graph capture, behind the restore
     struct EvalReq {
@@ -486,6 +493,13 @@ int metrics_blocks_per_frame(size_t npx); // a function of the frame's shape onl
 // (valid_is_u8); partials: B * metrics_blocks_per_frame(Ho * Wo) records of METRICS_PARTIAL_BYTES; errormap may be null
 int metrics_launch(vppx_ctx *ctx, int B, int Ho, int Wo, const float *disp, int Hg, int Wg, int gt_scale, const float *gt,
                    const void *valid, int valid_is_u8, void *partials, VppxMetrics *out, float *errormap);
+
+// sample_kernels.hip (losses.sample_hints, losses.py:5-10, on torch's CPU random stream)
+// src / hints: float32 [B][npx]; vsrc: float32, or one byte per pixel (vsrc_is_u8); vhints may be null.  Frame f samples with
+// seeds_dev[f], or with seed + f when seeds_dev is null; T = sample_threshold(probability)
+int sample_launch(vppx_ctx *ctx, int B, size_t npx, const float *src, const void *vsrc, int vsrc_is_u8, float *hints, float *vhints,
+                  const u32 *seeds_dev, u32 seed, u32 T);
+u32 sample_threshold(double p);
 
 // viz_kernels.hip (utils.py:17-79, test.py:318-343): pictures uint8 [B,H,W,3], dilation fused (0 and 1: none)
 #define VIZ_MAX_DILATION VPPX_VIZ_MAX_DILATION

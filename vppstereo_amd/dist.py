@@ -22,6 +22,14 @@ def frame_seed(base_seed, global_frame_index):
     return (int(base_seed) + int(global_frame_index)) & 0xFFFFFFFF
 
 
+def shard_sample(sample, lo):
+    """The `sample=` dict of `Engine.vpp_rsgm` for the shard that starts at global frame `lo`: its frames sample their hints
+    with the GLOBAL frame index (seed + lo + f), as they draw their colours, so the sharding does not change the hints."""
+    s = dict(sample)
+    s["seed"] = frame_seed(s.get("seed", 1), lo)
+    return s
+
+
 class GatherHandle:
     """A gather of one step's disparity shards in flight.  `wait()` makes the caller's stream (CUDA) or
     thread (CPU) wait for it; `result()` waits and returns [n_frames,H,W] on the root, None elsewhere."""

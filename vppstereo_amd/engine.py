@@ -158,9 +158,9 @@ class Engine:
         _lib.check(self.lib.vppx_rsgm_mid_dev(self.ctx.handle, B, Hp, Wp, _ptr(disp_l), _ptr(disp_r), _ptr(out_l), _ptr(out_r)))
         return out_l, out_r
 
-    def vpp_rsgm(self, left, right, hints, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
+    def vpp_rsgm(self, left, right, hints=None, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
                  rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None, iscale=1, oscale=1, disp_small=None,
-                 gt=None, validgt=None, metrics_out=None, errormap=None):
+                 gt=None, validgt=None, metrics_out=None, errormap=None, sample=None):
         """The whole hot path for a batch: one call, no host round trips, no synchronisation.
 
         g_occ: None, a uint8 [B,H,W] mask tensor, or -- test.py:154 with --maskocc in the same call --
@@ -179,8 +179,23 @@ class Engine:
         its result on the device, behind the post stage on the same stream (vppx_occ_vpp_rsgm_eval_dev: test.py:136-252 in one
         call), with gt_scale = oscale (test.py:150-152), and returns ``(out, metrics)``: metrics is a float64 [B,8] tensor, a
         view of the VppxMetrics records (`guided_metrics`); metrics_out: such a tensor to write into; errormap: float32
-        [B,Ho,Wo] or None, receives the reference's error map.  Without gt the call is today's, and returns `out`."""
+        [B,Ho,Wo] or None, receives the reference's error map.  Without gt the call is today's, and returns `out`.
+        sample: None, or a dict(probability=0.05, seed=1, src=None, validsrc=None, guided=False, hints_out=None,
+        validhints_out=None): the hints are sampled on the device on the way (vppx_occ_vpp_rsgm_sampled_dev; `sample_hints`
+        describes the stream), frame f with sampling seed `seed + f`, from src / validsrc (float32 [B,H,W]) or, without them,
+        from gt / validgt.  `hints` and `validhints` must then be None; guided=True is --guided with the sampled mask
+        (test.py:207-208); hints_out / validhints_out: float32 [B,H,W] tensors that receive the sampled maps."""
         torch = self.torch
+        if sample is not None:
+            if hints is not None or validhints is not None:
+                raise ValueError("sample: the hints are sampled on the device; pass hints=None and validhints=None")
+            heuristic = isinstance(g_occ, (str, dict))
+            if isinstance(g_occ, str) and g_occ != "occlusion_heuristic":
+                raise ValueError("g_occ: expected a mask tensor, None, 'occlusion_heuristic' or a dict of its parameters")
+            return self._vpp_rsgm_sampled(left, right, dict(sample), g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out,
+                                          inputs_ready, int(iscale), int(oscale), disp_small, gt, validgt, metrics_out, errormap)
+        if hints is None:
+            raise ValueError("hints: a float32 [B,H,W] tensor (or sample=dict(...) to sample them on the device)")
         heuristic = isinstance(g_occ, (str, dict))
         if isinstance(g_occ, str) and g_occ != "occlusion_heuristic":
             raise ValueError("g_occ: expected a mask tensor, None, 'occlusion_heuristic' or a dict of its parameters")
@@ -428,6 +443,88 @@ class Engine:
                                                        _ptr(occ_out), _ptr(l_vpp), _ptr(r_vpp), _ptr(out), _ptr(disp_small), _ptr(m),
                                                        _ptr(errormap)))
         return out, m
+
+    SAMPLE_KEYS = ("probability", "seed", "src", "validsrc", "guided", "hints_out", "validhints_out")
+
+    def sample_hints(self, src, validsrc, probability=0.05, seed=1, out=None, valid_out=None):
+        """losses.sample_hints (losses.py:5-10) for a batch on the device, on torch's CPU random stream (vppx_sample_hints_dev):
+        frame f equals ``torch.manual_seed(seed + f); sample_hints(src[f], validsrc[f] > 0, probability)`` on the CPU, bit for
+        bit.  src, validsrc: float32 [B,H,W].  Returns (hints, validhints), float32 [B,H,W]; no synchronisation."""
+        torch = self.torch
+        self._chk(src, torch.float32, 3, "src")
+        B, H, W = src.shape
+        self._chk(validsrc, torch.float32, 3, "validsrc", (B, H, W))
+        if out is None:
+            out = torch.empty_like(src)
+        if valid_out is None:
+            valid_out = torch.empty_like(src)
+        self._chk(out, torch.float32, 3, "out", (B, H, W))
+        self._chk(valid_out, torch.float32, 3, "valid_out", (B, H, W))
+        smp = _lib.sample_params(probability=float(probability), seed=int(seed) & 0xFFFFFFFF)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_sample_hints_dev(self.ctx.handle, C.byref(smp), B, H, W, _ptr(src), _ptr(validsrc), _ptr(out), _ptr(valid_out)))
+        return out, valid_out
+
+    def _vpp_rsgm_sampled(self, left, right, sample, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
+                          iscale, oscale, disp_small, gt, validgt, metrics_out, errormap):
+        torch = self.torch
+        unknown = set(sample) - set(self.SAMPLE_KEYS)
+        if unknown:
+            raise TypeError(f"sample: unknown keys {sorted(unknown)} (keys: {list(self.SAMPLE_KEYS)})")
+        src, validsrc = sample.get("src"), sample.get("validsrc")
+        if (src is None) != (validsrc is None):
+            raise ValueError("sample: src and validsrc go together")
+        evaluating = gt is not None or validgt is not None
+        if evaluating and (gt is None or validgt is None):
+            raise ValueError("gt and validgt go together")
+        if src is None and not evaluating:
+            raise ValueError("sample: without src / validsrc the hints are sampled from gt / validgt: pass them")
+        if not evaluating and (metrics_out is not None or errormap is not None):
+            raise ValueError("metrics_out / errormap are outputs of the evaluating call: pass gt and validgt")
+        self._chk(left, torch.uint8, 4, "left")
+        B, H, W, Cc = left.shape
+        if Cc not in (1, 3):
+            raise ValueError("left: channels must be 1 or 3")
+        self._chk(right, torch.uint8, 4, "right", left.shape)
+        sp = _lib.scale_params(iscale=iscale, oscale=oscale)
+        h, w, Ho, Wo = _lib.scaled_shape(H, W, iscale, oscale)
+        for t, n in ((src, "src"), (validsrc, "validsrc"), (gt, "gt"), (validgt, "validgt"), (sample.get("hints_out"), "hints_out"),
+                     (sample.get("validhints_out"), "validhints_out")):
+            if t is not None:
+                self._chk(t, torch.float32, 3, n, (B, H, W))
+        if evaluating:
+            _lib.check_gt_shape(H, W, oscale, Ho, Wo)
+        if g_occ is not None and not heuristic:
+            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
+        if out is None:
+            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
+        if disp_small is not None:
+            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
+        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
+            if t is not None:
+                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
+        if occ_out is not None:
+            if not heuristic:
+                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
+            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
+        if errormap is not None:
+            self._chk(errormap, torch.float32, 3, "errormap", (B, Ho, Wo))
+        m = self._metrics_tensor(B, metrics_out) if evaluating else None
+        self._bind_stream()
+        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
+        rp = _lib.rsgm_params(**(rsgm_kw or {}))
+        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
+        ep = _lib.eval_params(gt_scale=oscale) if evaluating else None
+        smp = _lib.sample_params(probability=float(sample.get("probability", 0.05)), seed=int(sample.get("seed", 1)) & 0xFFFFFFFF)
+        if inputs_ready is not None:
+            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        _lib.check(self.lib.vppx_occ_vpp_rsgm_sampled_dev(
+            self.ctx.handle, C.byref(op) if heuristic else None, C.byref(vp), C.byref(rp), C.byref(sp), C.byref(ep) if evaluating else None,
+            C.byref(smp), B, H, W, Cc, _ptr(left), _ptr(right), _ptr(src), _ptr(validsrc), 1 if sample.get("guided") else 0,
+            None if heuristic else _ptr(g_occ), _ptr(gt), _ptr(validgt), _ptr(occ_out), _ptr(l_vpp), _ptr(r_vpp), _ptr(out), _ptr(disp_small),
+            _ptr(m), _ptr(errormap), _ptr(sample.get("hints_out")), _ptr(sample.get("validhints_out"))))
+        return (out, m) if evaluating else out
 
     def occlusion_heuristic(self, hints, rx=9, ry=7, l=2, g=0.4375, th_conf=1, th_filter=0.1, out=None):
         torch = self.torch

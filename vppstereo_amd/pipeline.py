@@ -44,8 +44,43 @@ def _scaled_hints(gt, iscale):
     return gt[::iscale, ::iscale][:h, :w] / np.float32(iscale)
 
 
-def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw=None, rsgm_kw=None, return_patterns=False,
-              validhints=None, iscale=1, oscale=1, gt=None, validgt=None, return_errormap=False):
+def sample_hints(src, validsrc, probability=0.05, seed=1, return_valid=True):
+    """losses.sample_hints (losses.py:5-10) of one frame or a batch of host arrays on the device (vppx_sample_hints_host): frame f
+    equals ``torch.manual_seed(seed + f); sample_hints(src[f], validsrc[f] > 0, probability)`` on the CPU, bit for bit.  src,
+    validsrc: float [H,W] or [B,H,W].  Returns (hints, validhints) float32, or hints alone with return_valid=False."""
+    src = np.ascontiguousarray(np.asarray(src, dtype=np.float32))
+    validsrc = np.ascontiguousarray(np.asarray(validsrc, dtype=np.float32))
+    if src.ndim not in (2, 3) or validsrc.shape != src.shape:
+        raise ValueError("src, validsrc: float arrays of one shape, [H,W] or [B,H,W]")
+    B = 1 if src.ndim == 2 else src.shape[0]
+    H, W = src.shape[-2:]
+    hints = np.empty_like(src)
+    valid = np.empty_like(src) if return_valid else None
+    smp = _lib.sample_params(probability=float(probability), seed=int(seed) & 0xFFFFFFFF)
+    lib, ctx = _lib.load(), _lib.default_context()
+    _lib.check(lib.vppx_sample_hints_host(ctx.handle, C.byref(smp), B, H, W, _lib.np_ptr(src), _lib.np_ptr(validsrc), _lib.np_ptr(hints),
+                                          _lib.np_ptr(valid)))
+    return (hints, valid) if return_valid else hints
+
+
+SAMPLE_KEYS = ("probability", "seed", "src", "validsrc", "guided")
+
+
+def check_sampled_push(sampling, metrics, hints=None, validhints=None, src=None, validsrc=None):
+    """What a push on a FrameStream refuses about sampling, before anything touches the device."""
+    if sampling:
+        if hints is not None or validhints is not None:
+            raise ValueError("the stream was created with sample=: the hints are sampled on the device, no push brings any (push_sampled)")
+        if (src is None) != (validsrc is None):
+            raise ValueError("src and validsrc go together")
+        if src is None and not metrics:
+            raise ValueError("src=None samples from the frame's gt: the stream needs metrics=True (or push src and validsrc)")
+    elif src is not None or validsrc is not None:
+        raise ValueError("src / validsrc given but the stream was created without sample=")
+
+
+def run_frame(left, right, hints=None, maskocc=False, g_occ=None, occ_kw=None, vpp_kw=None, rsgm_kw=None, return_patterns=False,
+              validhints=None, iscale=1, oscale=1, gt=None, validgt=None, return_errormap=False, sample=None):
     """left, right: uint8 [H,W,3] or [H,W]; hints: float [H,W] (0 = none).  maskocc: compute g_occ with the occlusion heuristic
     (test.py:154) -- else `g_occ` (uint8 [H,W] or None) is used as given.  vpp_kw: keywords of `vpp_standalone.vpp`
     (wsize, blending, c_occ, ...); rsgm_kw: keywords of `rsgm.compute_rsgm` (dmax, p1, ...).  validhints: float [H,W] or None;
@@ -57,7 +92,29 @@ def run_frame(left, right, hints, maskocc=False, g_occ=None, occ_kw=None, vpp_kw
     gt / validgt: float [H,W] (the full frame shape) or None.  Given, the frame's evaluation metrics (losses.guided_metrics,
     test.py:251-252, with the --oscale decimation of the ground truth, test.py:150-152) are computed on the device and the call
     returns ``(result_as_above, metrics)``: a dict with the reference's keys 'bad 1.0' ... 'bad 4.0', 'avgerr', 'rms' (floats),
-    plus 'errormap' (float32 [Ho,Wo]) with return_errormap."""
+    plus 'errormap' (float32 [Ho,Wo]) with return_errormap.
+    sample: None, or dict(probability=0.05, seed=1, src=None, validsrc=None, guided=False): the hints are sampled on the device
+    first (`sample_hints`; test.py:125-129) from src / validsrc or, without them, from gt / validgt; `hints` and `validhints` must
+    then be None, and guided=True feeds the sampled mask as validhints (test.py:207-208)."""
+    if sample is not None:
+        sample = dict(sample)
+        unknown = set(sample) - set(SAMPLE_KEYS)
+        if unknown:
+            raise TypeError(f"sample: unknown keys {sorted(unknown)} (keys: {list(SAMPLE_KEYS)})")
+        if hints is not None or validhints is not None:
+            raise ValueError("sample: the hints are sampled on the device; pass hints=None and validhints=None")
+        s_src, s_valid = sample.get("src"), sample.get("validsrc")
+        if (s_src is None) != (s_valid is None):
+            raise ValueError("sample: src and validsrc go together")
+        if s_src is None:
+            if gt is None or validgt is None:
+                raise ValueError("sample: without src / validsrc the hints are sampled from gt / validgt: pass them")
+            s_src, s_valid = gt, validgt
+        hints, s_mask = sample_hints(s_src, s_valid, sample.get("probability", 0.05), sample.get("seed", 1))
+        if sample.get("guided"):
+            validhints = s_mask
+    elif hints is None:
+        raise ValueError("hints: a float [H,W] array (or sample=dict(...) to sample them on the device)")
     vk = dict(vpp_kw or {})
     method = vk.pop("method", "rnd")
     assert method in ["rnd", "maxDistance"]
@@ -179,11 +236,15 @@ class FrameStream:
     truth, ``gt=`` and ``validgt=`` (float [H,W], the full frame shape; > 0 is valid), the metrics of every batch are computed on the device behind its kernels
     (with the --oscale decimation of test.py:150-152) and each result becomes ``(result_as_above, metrics)`` -- metrics: the
     dict of `run_frame`, without an error map; `last_metrics_record` holds the popped frame's eight doubles (VppxMetrics).
-    return_disp=False (needs metrics=True): the disparity maps stay on the device and each result is the metrics dict alone."""
+    return_disp=False (needs metrics=True): the disparity maps stay on the device and each result is the metrics dict alone.
+    sample=probability: the hints are sampled on the device (test.py:125-129, `sample_hints`): frames go in through
+    ``push_sampled``, frame f samples with seed sample_seed + f (sample_seed=None: the stream's `seed`) and equals
+    `run_frame(..., sample=dict(probability=, seed=sample_seed + f, ...))` with init_rand(seed + f)."""
 
     def __init__(self, height, width, channels=3, batch=None, depth=3, seed=1, maskocc=False, with_g_occ=False, occ_kw=None,
                  vpp_kw=None, rsgm_kw=None, return_patterns=False, copy_threads=-1, device=-1, guided=False, iscale=1, oscale=1,
-                 metrics=False, return_disp=True):
+                 metrics=False, return_disp=True, sample=None, sample_seed=None):
+        self._sample = sample is not None
         if not return_disp and not metrics:
             raise ValueError("return_disp=False needs metrics=True (a stream that returns nothing)")
         if not return_disp and return_patterns:
@@ -226,10 +287,19 @@ class FrameStream:
         flags = (_lib.FS_PATTERNS if self._patterns else 0) | (_lib.FS_MASK if self._mask else 0) | (_lib.FS_GOCC if self._gocc else 0)
         flags |= _lib.FS_GUIDED if self._guided else 0
         flags |= (_lib.FS_METRICS if self._metrics else 0) | (0 if self._return_disp else _lib.FS_NO_DISP)
+        flags |= _lib.FS_SAMPLE if self._sample else 0
+        self._fill_has_src = False
         self._h = C.c_void_p()
         self.last_metrics_record = None
         try:
-            if self._metrics:
+            if self._sample:
+                ep = _lib.eval_params(gt_scale=self.oscale) if self._metrics else None
+                smp = _lib.sample_params(probability=float(sample), seed=int(seed if sample_seed is None else sample_seed) & 0xFFFFFFFF)
+                _lib.check(self._lib.vppx_fstream_create_sampled(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p),
+                                                                 C.byref(rp), C.byref(sp) if self._scaled else None,
+                                                                 C.byref(ep) if ep is not None else None, C.byref(smp), self.batch, self.depth,
+                                                                 self.h, self.w, self.ch, flags, int(copy_threads), C.byref(self._h)))
+            elif self._metrics:
                 ep = _lib.eval_params(gt_scale=self.oscale)
                 _lib.check(self._lib.vppx_fstream_create_eval(self._ctx.handle, C.byref(op) if op is not None else None, C.byref(p),
                                                               C.byref(rp), C.byref(sp) if self._scaled else None, C.byref(ep), self.batch,
@@ -282,7 +352,8 @@ class FrameStream:
         """One frame in (copied before the call returns).  The frame that completes a batch submits it; if that submit fails
         the push raises but HAS taken the frame, and the next push or `flush()` submits the batch again.  validhints: float
         [H,W], required on a guided stream and refused on any other.  A metrics=True stream takes its frames through
-        `push_eval`."""
+        `push_eval`, a sample= stream through `push_sampled`."""
+        check_sampled_push(self._sample, self._metrics, hints, validhints)
         if self._metrics:
             raise ValueError("the stream was created with metrics=True: every push brings gt and validgt (push_eval)")
         self._push(left, right, hints, g_occ, validhints, None, None)
@@ -290,16 +361,37 @@ class FrameStream:
     def push_eval(self, left, right, hints, g_occ=None, validhints=None, gt=None, validgt=None):
         """`push` on a metrics=True stream (vppx_fstream_push_eval): the frame and its ground truth, gt and validgt, float [H,W]
         at the full frame shape (validgt > 0 is valid).  Refused on any other stream."""
+        check_sampled_push(self._sample, self._metrics, hints, validhints)
         if not self._metrics:
             raise ValueError("gt / validgt given but the stream was created without metrics=True")
         if gt is None or validgt is None:
             raise ValueError("the stream was created with metrics=True: every push brings gt and validgt")
         self._push(left, right, hints, g_occ, validhints, gt, validgt)
 
+    def push_sampled(self, left, right, g_occ=None, src=None, validsrc=None, gt=None, validgt=None):
+        """One frame into a sample= stream (vppx_fstream_push_sampled): its hints are sampled on the device with probability
+        `sample`, frame f of the stream with sampling seed sample_seed + f, from src / validsrc (float [H,W]) or -- src=None, on a
+        metrics=True stream -- from the gt / validgt the push brings anyway (nothing else goes up for the hints then).  A guided=True
+        stream feeds the sampled mask as validhints.  Refused on any other stream."""
+        check_sampled_push(self._sample, self._metrics, None, None, src, validsrc)
+        if not self._sample:
+            raise ValueError("the stream was created without sample=: every push brings its hints (push / push_eval)")
+        if self._metrics and (gt is None or validgt is None):
+            raise ValueError("the stream was created with metrics=True: every push brings gt and validgt")
+        if not self._metrics and (gt is not None or validgt is not None):
+            raise ValueError("gt / validgt given but the stream was created without metrics=True")
+        if src is not None:
+            src = self._arr(src, np.float32, (self.h, self.w), "src")
+            validsrc = self._arr(validsrc, np.float32, (self.h, self.w), "validsrc")
+        if self._fill and self._fill_has_src != (src is not None):
+            self.flush()   # a batch samples from one kind of source
+        self._push(left, right, src, g_occ, validsrc, gt, validgt)
+
     def _push(self, left, right, hints, g_occ, validhints, gt, validgt):
         left = self._arr(left, np.uint8, self._shape, "left")
         right = self._arr(right, np.uint8, self._shape, "right")
-        hints = self._arr(hints, np.float32, (self.h, self.w), "hints")
+        if not self._sample:
+            hints = self._arr(hints, np.float32, (self.h, self.w), "hints")
         occ = None
         if self._gocc:
             if g_occ is None:
@@ -310,7 +402,9 @@ class FrameStream:
         elif g_occ is not None:
             raise ValueError("g_occ given but the stream was created without with_g_occ=True")
         vh = None
-        if self._guided:
+        if self._sample:
+            vh = validhints   # (the frame's validsrc, checked by push_sampled)
+        elif self._guided:
             if validhints is None:
                 raise ValueError("the stream was created with guided=True: every push brings validhints")
             vh = self._arr(validhints, np.float32, (self.h, self.w), "validhints")
@@ -329,7 +423,15 @@ class FrameStream:
                 self._early.append(self._pop_native())
         try:
             occ_p = occ.ctypes.data if occ is not None else None
-            if self._metrics:
+            if self._sample:
+                if self._fill == 0:
+                    self._fill_has_src = hints is not None
+                _lib.check(self._lib.vppx_fstream_push_sampled(self._h, left.ctypes.data, right.ctypes.data, occ_p,
+                                                               hints.ctypes.data if hints is not None else None,
+                                                               vh.ctypes.data if vh is not None else None,
+                                                               gt.ctypes.data if gt is not None else None,
+                                                               validgt.ctypes.data if validgt is not None else None))
+            elif self._metrics:
                 _lib.check(self._lib.vppx_fstream_push_eval(self._h, left.ctypes.data, right.ctypes.data, hints.ctypes.data, occ_p,
                                                             vh.ctypes.data if vh is not None else None, gt.ctypes.data,
                                                             validgt.ctypes.data))
@@ -420,9 +522,10 @@ class FrameStream:
     def run(self, frames):
         """Generator: results for an iterable of (left, right, hints[, g_occ]) in input order -- on a guided stream
         (left, right, hints, g_occ or None, validhints); on a metrics=True stream the two extra entries gt, validgt come at
-        the end: (left, right, hints, g_occ or None, validhints or None, gt, validgt) -- keeps about `depth` batches in flight."""
+        the end: (left, right, hints, g_occ or None, validhints or None, gt, validgt); on a sample= stream the arguments of
+        `push_sampled`: (left, right[, g_occ, src, validsrc, gt, validgt]) -- keeps about `depth` batches in flight."""
         for fr in frames:
-            (self.push_eval if self._metrics else self.push)(*fr)
+            (self.push_sampled if self._sample else self.push_eval if self._metrics else self.push)(*fr)
             # whole batches that must be complete by now: everything but the last depth - 1 submitted ones
             while self._early:
                 yield self.pop()
