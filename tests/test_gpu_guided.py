@@ -151,7 +151,7 @@ def test_guided_batch_forced_into_parts_equals_the_whole_batch(tmp_path):
     dst = str(tmp_path / "parts.npy")
     r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, dst], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert int(r.stdout.split("parts")[-1]) >= 2, r.stdout   # (5 + 3: a remainder below 8 frames rides on a full part)
+    assert int(r.stdout.split("parts")[-1]) >= 2, r.stdout   # (2 + 3 + 3: a guided call's remainder is a part of its own)
     assert np.array_equal(np.load(dst), whole)
 
 

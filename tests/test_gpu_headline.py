@@ -511,3 +511,68 @@ def test_parts_of_a_split_batch_equal_the_unsplit_call(B, chunk, parts):
     lo, ro = oracle.vpp(b["left"][f], b["right"][f], b["hints"][f], g_occ=conf)
     assert np.array_equal(lo, ref[2][f].cpu().numpy()) and np.array_equal(ro, ref[3][f].cpu().numpy())
     assert np.array_equal(oracle.compute_rsgm(b["left"][f], lo, ro, dmax=D, subpixel=True), ref[0][f].cpu().numpy())
+
+
+# ---- the slices of a split call: every per-frame plane of a guided, evaluating / scaled call (HotCall::frames) ----
+_SLICE_B, _SLICE_H, _SLICE_W, _SLICE_D, _SLICE_SEED = 7, 40, 96, 64, 21
+_SLICE_OUTS = {"A": ("out", "occ_out", "l_vpp", "r_vpp", "errormap", "metrics"), "B": ("out", "disp_small", "l_vpp", "r_vpp")}
+_slice_cache = {}
+
+
+def _slice_call(eng, d, which, lo, hi):
+    """Call A or B of the test below on frames lo .. hi of the data, frame lo with the call's seed + lo.  Returns its outputs."""
+    import torch
+    n, H, W = hi - lo, _SLICE_H, _SLICE_W
+    t = {k: _dev(eng, v[lo:hi]) for k, v in d.items()}
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=eng.device)
+    kw = dict(validhints=t["validhints"], seed=_SLICE_SEED + lo, rsgm_kw=dict(dmax=_SLICE_D))
+    if which == "A":    # the heuristic's mask and the patterns out, metrics and error map behind the batch
+        o = dict(occ_out=new((n, H, W), torch.uint8), l_vpp=new((n, H, W, 3), torch.uint8), r_vpp=new((n, H, W, 3), torch.uint8),
+                 errormap=new((n, H, W), torch.float32), metrics=new((n, 8), torch.float64))
+        o["out"], _ = eng.vpp_rsgm(t["left"], t["right"], t["hints"], g_occ="occlusion_heuristic", occ_out=o["occ_out"], l_vpp=o["l_vpp"],
+                                   r_vpp=o["r_vpp"], gt=t["gt"], validgt=t["validgt"], errormap=o["errormap"], metrics_out=o["metrics"], **kw)
+    else:               # a caller's mask at the scaled shape, resize in front, restore behind
+        h, w = H // 2, W // 2
+        o = dict(disp_small=new((n, h, w), torch.float32), l_vpp=new((n, h, w, 3), torch.uint8), r_vpp=new((n, h, w, 3), torch.uint8))
+        o["out"] = eng.vpp_rsgm(t["left"], t["right"], t["hints"], g_occ=t["mask"], l_vpp=o["l_vpp"], r_vpp=o["r_vpp"], iscale=2, oscale=1,
+                                disp_small=o["disp_small"], **kw)
+    eng.synchronize()
+    return {k: v.cpu().numpy() for k, v in o.items()}
+
+
+def _slice_case():
+    """The data and, computed once on a default context, the one-frame calls every split is compared with."""
+    if not _slice_cache:
+        B, H, W = _SLICE_B, _SLICE_H, _SLICE_W
+        d = synth.make_batch(B, H, W, _SLICE_D, 0.04, seed=311)
+        d["validhints"] = (d["hints"] > 0).astype(np.float32)   # frame f's from its own hints
+        d["validgt"] = (d["gt"] > 0).astype(np.float32)
+        d["mask"] = np.random.default_rng(312).integers(0, 2, (B, H // 2, W // 2)).astype(np.uint8)
+        for k in ("left", "right", "hints", "validhints", "mask"):
+            assert len({d[k][f].tobytes() for f in range(B)}) == B, k   # pairwise distinct frames: a slice off by a frame shows
+        eng = _engine()
+        _slice_cache["data"] = d
+        _slice_cache["ref"] = {w: [_slice_call(eng, d, w, f, f + 1) for f in range(B)] for w in ("A", "B")}
+    return _slice_cache["data"], _slice_cache["ref"]
+
+
+@pytest.mark.parametrize("env", [{}, dict(VPPX_CHUNK=3), dict(VPPX_SUBSTREAMS=2)], ids=["default", "chunk3", "substreams2"])
+def test_every_plane_of_a_split_guided_call_is_sliced_per_frame(env):
+    """7 distinct frames of 40 x 96 x 3, D = 64, guided (validhints), on a default context, as parts (VPPX_CHUNK=3) and over two
+    sub-streams (VPPX_SUBSTREAMS=2: the one path that slices validhints for a child context).  Call A: the heuristic's mask, the
+    patterns, the metrics and the error map; call B: a caller's mask per frame, iscale 2 / oscale 1 with disp_small, i.e. planes of
+    the scaled shape (20 x 48).  Every output of frame f -- out, disp_small, occ_out, l_vpp, r_vpp, errormap and the eight
+    metrics -- is bit-equal to the one-frame call with seed + f on a default context.  Under VPPX_CHUNK=3 the call must really
+    have been split: a guided call's remainder is a part of its own (vpp_rsgm_parts), 7 = 1 + 3 + 3."""
+    d, ref = _slice_case()
+    eng = _engine(**env)
+    parts = {}
+    for which in ("A", "B"):
+        got = _slice_call(eng, d, which, 0, _SLICE_B)
+        parts[which] = eng.last_call_parts()
+        for f in range(_SLICE_B):
+            for k in _SLICE_OUTS[which]:
+                assert got[k][f].tobytes() == ref[which][f][k][0].tobytes(), (which, k, f)
+    print("last_call_parts", env, parts)
+    if "VPPX_CHUNK" in env:
+        assert parts == {"A": 3, "B": 3}, parts

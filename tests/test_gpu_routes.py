@@ -366,9 +366,9 @@ np.save(sys.argv[3], out.cpu().numpy())
 
 def test_guided_budget_parts_equal_one_part(eng, tmp_path):
     """With a 20 MiB budget 8 frames run as parts of 3: vpp_rsgm_parts makes 2 + 3 + 3 (the remainder is a part of its own,
-    in front -- unlike VPPX_CHUNK=3, which merges a remainder below 8 frames into a full part: 5 + 3), and vppx_rsgm_dev's
-    loop 3 + 3 + 2.  Parts below 8 frames take <16,12> where the whole batch takes <8,24>: the routes show the split.  Both
-    must equal the batch in one part bit for bit."""
+    in front, as in every guided call -- an unguided call under VPPX_CHUNK=3 merges a remainder below 8 frames into a full
+    part: 5 + 3), and vppx_rsgm_dev's loop 3 + 3 + 2.  Parts below 8 frames take <16,12> where the whole batch takes <8,24>:
+    the routes show the split.  Both must equal the batch in one part bit for bit."""
     import torch
     b = synth.make_batch(_PB, _PH, _PW, _PD, 0.05, seed=61)
     vh_np = _valid(b["hints"])

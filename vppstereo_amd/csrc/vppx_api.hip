@@ -1437,11 +1437,16 @@ extern "C" int vppx_rand_stream(vppx_ctx *ctx, uint32_t seed, uint64_t offset, i
 // ---------------------------------------------------------------------------------------
 // fused hot path (test.py:158-225): VPP -> rSGM, batched, device resident
 // ---------------------------------------------------------------------------------------
-static int vpp_rsgm_one(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
-                        int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                        const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+static int vpp_rsgm_one(vppx_ctx *ctx, const HotCall &c)
 {
     int rc;
+    const VppxOccParams *const op = c.op;
+    const VppxVppParams *const vp = &c.vp;
+    const VppxRsgmParams *const rp = c.rp;
+    const int B = c.B, H = c.H, W = c.W, C = c.C;
+    const u8 *const left = c.left, *const right = c.right, *g_occ = c.g_occ;
+    const float *const g = c.g;
+    u8 *l_vpp = c.l_vpp, *r_vpp = c.r_vpp, *const conf_out = c.conf_out;
     const size_t nb = (size_t)B * H * W * C, np = (size_t)B * H * W;
     const bool piped = pipeline_applies(ctx);
     // A pipelined front stage writes library-owned buffers only; the caller's copies are made on the launch stream
@@ -1506,12 +1511,39 @@ static int vpp_rsgm_one(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPar
     RsgmGeom rg;
     make_geom(B, H, W, C, rp->dmax, rg);
     // --guided: the VPP hints re-weight the costs too (test.py:207 passes data['hints'] to both)
-    return rsgm_core(ctx, *rp, rg, left, l_vpp, r_vpp, disp_out, validhints ? g : nullptr, validhints);
+    return rsgm_core(ctx, *rp, rg, left, l_vpp, r_vpp, c.disp_out, c.validhints ? g : nullptr, c.validhints);
 }
 
-static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
-                          int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                          const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out);
+static int vpp_rsgm_entry(vppx_ctx *ctx, const HotCall &c);
+static int scaled_call(vppx_ctx *ctx, const HotCall &c);
+static int eval_call(vppx_ctx *ctx, const HotCall &c);
+static int sampled_call(vppx_ctx *ctx, const HotCall &c);
+
+// The common part of every entry point's descriptor
+static HotCall hot_call(HotCall::Layer layer, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H, int W,
+                        int C, const uint8_t *left, const uint8_t *right)
+{
+    HotCall c;
+    c.layer = layer;
+    c.op = op;
+    if (vp) c.vp = *vp;
+    c.vp_null = !vp;
+    c.rp = rp;
+    c.B = B; c.H = H; c.W = W; c.C = C;
+    c.left = left; c.right = right;
+    return c;
+}
+
+// The call, entered at its layer; the caller's inputs-ready event is one-shot, whatever happened
+int vppx_hot_call_internal(vppx_ctx *ctx, const HotCall &c)
+{
+    const int rc = c.layer == HotCall::SAMPLED ? sampled_call(ctx, c)
+                 : c.layer == HotCall::EVAL    ? eval_call(ctx, c)
+                 : c.layer == HotCall::SCALED  ? scaled_call(ctx, c)
+                                               : vpp_rsgm_entry(ctx, c);
+    ctx->inputs_ev = nullptr;
+    return rc;
+}
 
 extern "C" int vppx_inputs_ready_event(vppx_ctx *ctx, void *hip_event)
 {
@@ -1527,9 +1559,10 @@ extern "C" int vppx_vpp_rsgm_dev(vppx_ctx *ctx, const VppxVppParams *vp, const V
 {
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
-    const int rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, left, right, g, g_occ, nullptr, nullptr, l_vpp, r_vpp, disp_out);
-    ctx->inputs_ev = nullptr; // one-shot, whatever happened
-    return rc;
+    HotCall c = hot_call(HotCall::PLAIN, nullptr, vp, rp, B, H, W, C, left, right);
+    c.g = g; c.g_occ = g_occ;
+    c.l_vpp = l_vpp; c.r_vpp = r_vpp; c.disp_out = disp_out;
+    return vppx_hot_call_internal(ctx, c);
 }
 
 extern "C" int vppx_occ_vpp_rsgm_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
@@ -1539,9 +1572,10 @@ extern "C" int vppx_occ_vpp_rsgm_dev(vppx_ctx *ctx, const VppxOccParams *op, con
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
     if (!op) { vppx_set_error("vppx_occ_vpp_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
-    const int rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, nullptr, nullptr, conf_out, l_vpp, r_vpp, disp_out);
-    ctx->inputs_ev = nullptr;
-    return rc;
+    HotCall c = hot_call(HotCall::PLAIN, op, vp, rp, B, H, W, C, left, right);
+    c.g = g;
+    c.conf_out = conf_out; c.l_vpp = l_vpp; c.r_vpp = r_vpp; c.disp_out = disp_out;
+    return vppx_hot_call_internal(ctx, c);
 }
 
 // test.py:207-223 (--guided --stereomodel rsgm): the VPP hints g re-weight the matching costs as well (_guided_dsi).
@@ -1553,11 +1587,44 @@ extern "C" int vppx_occ_vpp_rsgm_guided_dev(vppx_ctx *ctx, const VppxOccParams *
 {
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
+    if (!validhints) { vppx_set_error("vppx_occ_vpp_rsgm_guided: validhints is NULL"); ctx->inputs_ev = nullptr; return VPPX_E_INVALID_ARG; }
+    HotCall c = hot_call(HotCall::PLAIN, op, vp, rp, B, H, W, C, left, right);
+    c.g = g; c.g_occ = op ? nullptr : g_occ; c.validhints = validhints;
+    c.conf_out = conf_out; c.l_vpp = l_vpp; c.r_vpp = r_vpp; c.disp_out = disp_out;
+    return vppx_hot_call_internal(ctx, c);
+}
+
+// The tail of a host call: `call` queues the hot path on the staged inputs; its results come down (entries without a device
+// buffer are skipped), with them the rand() draws each frame consumed (draws_out, may be NULL), and the stream is waited for.
+// Like vppx_rsgm_host: a lost lock step of THIS call is repeated once, on the line-parallel kernel, an earlier call's is reported.
+struct HostCopy { void *host; const void *dev; size_t bytes; };
+template <typename Call>
+static int host_call_tail(vppx_ctx *ctx, const VppxVppParams *vp, int B, Call call, std::initializer_list<HostCopy> copies, uint64_t *draws_out)
+{
     int rc;
-    if (!validhints) { vppx_set_error("vppx_occ_vpp_rsgm_guided: validhints is NULL"); rc = VPPX_E_INVALID_ARG; }
-    else rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, op ? nullptr : g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
-    ctx->inputs_ev = nullptr;
-    return rc;
+    for (int attempt = 0;; attempt++) {
+        const unsigned serial_before = ctx->v3.serial;
+        rc = call();
+        ctx->inputs_ev = nullptr;
+        if (rc) return rc;
+        for (const HostCopy &k : copies)
+            if (k.dev && (rc = download(ctx, k.host, k.dev, k.bytes))) return rc;
+        std::vector<unsigned long long> tot;
+        // the totals of THIS context's single part only: parts overwrite each other's, sub-stream children keep their own
+        if (draws_out && vp->method == VPPX_METHOD_RND && ctx->ws[WS_FRAME_TOT].p && ctx->last_parts == 1 &&
+            ctx->ws[WS_FRAME_TOT].cap >= (size_t)B * 16) {
+            tot.resize((size_t)B * 2);
+            VPPX_HIP(hipMemcpyAsync(tot.data(), ctx->ws[WS_FRAME_TOT].p, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VPPX_HIP(hipStreamSynchronize(ctx->stream));
+        if (draws_out)
+            for (int f = 0; f < B; f++) draws_out[f] = tot.empty() ? 0 : tot[2 * f];
+        if ((rc = lockstep_check(ctx)) == 0) break;
+        const unsigned s = ctx->lockstep_last_serial;
+        const bool mine = (unsigned)(s - serial_before - 1u) < (unsigned)(ctx->v3.serial - serial_before);
+        if (!mine || attempt > 0) return rc;
+    }
+    return 0;
 }
 
 // test.py:154-225 for host arrays in ONE call: the pair, the hints (and a caller's mask) go up once, the disparities (and, on
@@ -1594,34 +1661,15 @@ static int occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxV
     if (l_vpp_out && (rc = ws_reserve(ctx, WS_STAGE_E, nb, &dlv))) return rc;
     if (r_vpp_out && (rc = ws_reserve(ctx, WS_STAGE_F, nb, &drv))) return rc;
     if ((rc = ws_reserve(ctx, WS_HANDOFF_H, np * sizeof(float), &dout))) return rc;
-    for (int attempt = 0;; attempt++) {
-        const unsigned serial_before = ctx->v3.serial;
+    HotCall c = hot_call(HotCall::PLAIN, nullptr, vp, rp, B, H, W, C, (const u8 *)dl, (const u8 *)dr);
+    c.g = (const float *)dg; c.g_occ = (const u8 *)docc; c.validhints = (const float *)dvh;
+    c.l_vpp = (u8 *)dlv; c.r_vpp = (u8 *)drv; c.disp_out = (float *)dout;
+    auto call = [&]() {
         ctx->front_routes_keep = op != nullptr; // (vppx_last_front_routes: the heuristic above belongs to this call)
-        rc = vpp_rsgm_entry(ctx, nullptr, vp, rp, B, H, W, C, (const u8 *)dl, (const u8 *)dr, (const float *)dg, (const u8 *)docc,
-                            (const float *)dvh, nullptr, (u8 *)dlv, (u8 *)drv, (float *)dout);
-        ctx->inputs_ev = nullptr;
-        if (rc) return rc;
-        if ((rc = download(ctx, disp_out, dout, np * sizeof(float)))) return rc;
-        if (dconf && (rc = download(ctx, conf_out, dconf, np))) return rc;
-        if (dlv && (rc = download(ctx, l_vpp_out, dlv, nb))) return rc;
-        if (drv && (rc = download(ctx, r_vpp_out, drv, nb))) return rc;
-        std::vector<unsigned long long> tot;
-        // the totals of THIS context's single part only: parts overwrite each other's, sub-stream children keep their own
-        if (draws_out && vp->method == VPPX_METHOD_RND && ctx->ws[WS_FRAME_TOT].p && ctx->last_parts == 1 &&
-            ctx->ws[WS_FRAME_TOT].cap >= (size_t)B * 16) {
-            tot.resize((size_t)B * 2);
-            VPPX_HIP(hipMemcpyAsync(tot.data(), ctx->ws[WS_FRAME_TOT].p, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        VPPX_HIP(hipStreamSynchronize(ctx->stream));
-        if (draws_out)
-            for (int f = 0; f < B; f++) draws_out[f] = tot.empty() ? 0 : tot[2 * f];
-        // like vppx_rsgm_host: a lost lock step of THIS call is repeated on the line-parallel kernel, an earlier call's is reported
-        if ((rc = lockstep_check(ctx)) == 0) break;
-        const unsigned s = ctx->lockstep_last_serial;
-        const bool mine = (unsigned)(s - serial_before - 1u) < (unsigned)(ctx->v3.serial - serial_before);
-        if (!mine || attempt > 0) return rc;
-    }
-    return 0;
+        return vpp_rsgm_entry(ctx, c);
+    };
+    return host_call_tail(ctx, vp, B, call,
+                          {{disp_out, dout, np * sizeof(float)}, {conf_out, dconf, np}, {l_vpp_out, dlv, nb}, {r_vpp_out, drv, nb}}, draws_out);
 }
 
 extern "C" int vppx_occ_vpp_rsgm_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
@@ -1744,25 +1792,53 @@ static int scale_tables(vppx_ctx *ctx, int H, int W, const VppxScaleParams &sp, 
     return 0;
 }
 
-// guided_metrics of a finished map on the launch stream (ctx->eval: vppx_occ_vpp_rsgm_eval_dev).  The partial records have their
-// own workspace slot: a pipelined next call's front stage runs next to this and shares nothing with it.
-static int eval_launch(vppx_ctx *ctx, int B, int Ho, int Wo, const float *disp)
+// guided_metrics of a finished map on the launch stream (the evaluation request of c: vppx_occ_vpp_rsgm_eval_dev).  The partial
+// records have their own workspace slot: a pipelined next call's front stage runs next to this and shares nothing with it.
+static int eval_launch(vppx_ctx *ctx, const HotCall &c, int Ho, int Wo, const float *disp)
 {
-    const vppx_ctx::EvalReq &e = ctx->eval;
     void *part = nullptr;
-    int rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part);
+    int rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)c.B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part);
     if (rc) return rc;
-    return metrics_launch(ctx, B, Ho, Wo, disp, e.Hg, e.Wg, e.gt_scale, e.gt, e.valid, e.valid_is_u8, part, e.out, e.errormap);
+    return metrics_launch(ctx, c.B, Ho, Wo, disp, c.Hg, c.Wg, c.gt_scale, c.gt, c.validgt, c.valid_is_u8, part, c.metrics_out, c.errormap);
+}
+
+// One kernel in front of the front stage (the resize of a scaled call, the sampling of a sampled one).  With vppx_set_pipeline
+// it is the first kernel of the front stage: it waits for what every front stage waits for (the previous
+// call's aggregation event and this call's inputs) and writes the set of buffers the previous call did NOT use -- the caller
+// picks it by *parity, flipped here; the front stage proper then starts on the kernel's event.  Otherwise the kernel goes on the
+// launch stream, behind the caller's inputs event.  The context is back on the launch stream before any return.
+template <typename Launch>
+static int pre_front(vppx_ctx *ctx, hipEvent_t *ev, int *parity, Launch launch)
+{
+    int rc;
+    if (!pipeline_applies(ctx)) {
+        if (ctx->inputs_ev) {
+            VPPX_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->inputs_ev, 0));
+            ctx->inputs_ev = nullptr;
+        }
+        return launch();
+    }
+    if (!*ev) VPPX_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    if ((rc = front_begin(ctx))) return rc;
+    rc = launch();
+    const hipError_t e = rc ? hipSuccess : hipEventRecord(*ev, ctx->stream);
+    ctx->stream = ctx->main_saved;
+    ctx->front_active = false;
+    if (rc) return rc;
+    if (e != hipSuccess) { vppx_set_error("hipEventRecord failed: %s", hipGetErrorString(e)); return VPPX_E_HIP; }
+    *parity ^= 1;
+    ctx->inputs_ev = (void *)*ev;
+    return 0;
 }
 
 // The scaled call on device pointers: resize + decimation (scale_front_kernel), the unchanged hot path at (h, w) on the
 // library-owned scaled buffers, then the restore (scale_restore_kernel) on the launch stream.
-static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                       int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                       const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small)
+static int scaled_call(vppx_ctx *ctx, const HotCall &c)
 {
     int rc;
-    if (!vp || !rp || !sp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_scaled: NULL argument"); return VPPX_E_INVALID_ARG; }
+    const VppxScaleParams *const sp = c.sp;
+    const int B = c.B, H = c.H, W = c.W, C = c.C;
+    if (c.vp_null || !c.rp || !sp || !c.left || !c.right || !c.g || !c.disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_scaled: NULL argument"); return VPPX_E_INVALID_ARG; }
     int h, w, Ho, Wo;
     if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
     if ((rc = check_frames(B, H, W, C))) return rc;
@@ -1772,62 +1848,48 @@ static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPara
         vppx_set_error("vppx_occ_vpp_rsgm_scaled: iscale %d turns %dx%d frames into %dx%d: %s", sp->iscale, H, W, h, w, msg);
         return rc;
     }
-    if ((rc = check_vpp_params(*vp))) return rc;
-    if ((rc = check_rsgm_params(*rp))) return rc;
+    if ((rc = check_vpp_params(c.vp))) return rc;
+    if ((rc = check_rsgm_params(*c.rp))) return rc;
+    HotCall run = c; // the call at the shape it runs at
+    run.sp = nullptr;
+    run.g_occ = c.op ? nullptr : c.g_occ;
+    run.conf_out = c.op ? c.conf_out : nullptr;
+    run.disp_small = nullptr;
     if (sp->iscale == 1) { // nothing to resize, nothing to restore: the unscaled call
-        rc = vpp_rsgm_entry(ctx, op, vp, rp, B, H, W, C, left, right, g, op ? nullptr : g_occ, validhints, op ? conf_out : nullptr, l_vpp,
-                            r_vpp, disp_out);
-        if (rc == 0 && disp_small)
-            VPPX_HIP(hipMemcpyAsync(disp_small, disp_out, (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        rc = vpp_rsgm_entry(ctx, run);
+        if (rc == 0 && c.disp_small)
+            VPPX_HIP(hipMemcpyAsync(c.disp_small, c.disp_out, (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         return rc;
     }
     if ((rc = lockstep_check(ctx))) return rc; // (before anything is queued, as the hot path itself does)
     const int *tab = nullptr;
     if ((rc = scale_tables(ctx, H, W, *sp, h, w, Ho, Wo, &tab))) return rc;
-    const bool piped = pipeline_applies(ctx);
-    const int set = piped ? ctx->scale_parity : 0;
+    const int set = pipeline_applies(ctx) ? ctx->scale_parity : 0;
     const size_t np = (size_t)B * h * w, nb = np * C;
     u8 *ls, *rs;
     float *gs, *vhs = nullptr;
     if ((rc = ws_get(ctx, set ? WS_SCALE_L1 : WS_SCALE_L0, nb, &ls))) return rc;
     if ((rc = ws_get(ctx, set ? WS_SCALE_R1 : WS_SCALE_R0, nb, &rs))) return rc;
     if ((rc = ws_get(ctx, set ? WS_SCALE_G1 : WS_SCALE_G0, np, &gs))) return rc;
-    if (validhints && (rc = ws_get(ctx, set ? WS_SCALE_V1 : WS_SCALE_V0, np, &vhs))) return rc;
+    if (c.validhints && (rc = ws_get(ctx, set ? WS_SCALE_V1 : WS_SCALE_V0, np, &vhs))) return rc;
     const bool restore = scale_restores(*sp);
-    if (ctx->eval.active) ctx->eval.after_restore = restore; // (the metrics read the restored map: queued below, not by the hot path)
-    float *dsmall = restore ? disp_small : disp_out;
+    float *dsmall = restore ? c.disp_small : c.disp_out;
     if (restore && !dsmall && (rc = ws_get(ctx, WS_SCALE_DSMALL, np, &dsmall))) return rc;
     ScaleFrontArgs a;
-    a.l = left; a.r = right; a.g = g; a.vh = validhints;
+    a.l = c.left; a.r = c.right; a.g = c.g; a.vh = c.validhints;
     a.ls = ls; a.rs = rs; a.gs = gs; a.vhs = vhs;
     a.ytab = (const int4 *)tab;
     a.xtab = (const int4 *)(tab + 4 * h);
     a.B = B; a.H = H; a.W = W; a.C = C; a.h = h; a.w = w; a.s = sp->iscale;
     a.fs = (float)sp->iscale;
     a.n_img_threads = 0;
-    if (piped) {
-        // the resize is the first kernel of the front stage.  It waits for what every front stage waits for (the
-        // previous call's aggregation event and this call's inputs) and writes the set of scaled buffers the previous call did NOT
-        // use; the front stage proper then starts on the resize's event.
-        if (!ctx->ev_scaled) VPPX_HIP(hipEventCreateWithFlags(&ctx->ev_scaled, hipEventDisableTiming));
-        if ((rc = front_begin(ctx))) return rc;
-        rc = scale_launch_front(ctx, a);
-        const hipError_t e = rc ? hipSuccess : hipEventRecord(ctx->ev_scaled, ctx->stream);
-        ctx->stream = ctx->main_saved;
-        ctx->front_active = false;
-        if (rc) return rc;
-        if (e != hipSuccess) { vppx_set_error("hipEventRecord failed: %s", hipGetErrorString(e)); return VPPX_E_HIP; }
-        ctx->scale_parity ^= 1;
-        ctx->inputs_ev = (void *)ctx->ev_scaled;
-    } else {
-        if (ctx->inputs_ev) {
-            VPPX_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->inputs_ev, 0));
-            ctx->inputs_ev = nullptr;
-        }
-        if ((rc = scale_launch_front(ctx, a))) return rc;
-    }
-    rc = vpp_rsgm_entry(ctx, op, vp, rp, B, h, w, C, ls, rs, gs, op ? nullptr : g_occ, vhs, op ? conf_out : nullptr, l_vpp, r_vpp, dsmall);
-    if (rc) return rc;
+    if ((rc = pre_front(ctx, &ctx->ev_scaled, &ctx->scale_parity, [&]() { return scale_launch_front(ctx, a); }))) return rc;
+    run.H = h; run.W = w;
+    run.left = ls; run.right = rs; run.g = gs; run.validhints = vhs;
+    run.disp_out = dsmall;
+    // the metrics read the restored map: with a restore they are queued below, behind it, and the hot path has no request
+    if (restore) run.metrics_out = nullptr;
+    if ((rc = vpp_rsgm_entry(ctx, run))) return rc;
     {   // vppx_last_routes: the resize first, the restore last
         char buf[32];
         snprintf(buf, sizeof(buf), "scale_front<%d>", C);
@@ -1835,11 +1897,11 @@ static int scaled_call(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppPara
     }
     if (restore) {
         const int *ry = tab + 4 * h + 4 * w, *rx = ry + Ho;
-        if ((rc = scale_launch_restore(ctx, B, h, w, Ho, Wo, dsmall, disp_out, ry, rx, sp->iscale, sp->oscale))) return rc;
+        if ((rc = scale_launch_restore(ctx, B, h, w, Ho, Wo, dsmall, c.disp_out, ry, rx, sp->iscale, sp->oscale))) return rc;
         route_note(ctx, "scale_restore");
-        if (ctx->eval.active && (rc = eval_launch(ctx, B, Ho, Wo, disp_out))) return rc;
-    } else if (disp_small) {
-        VPPX_HIP(hipMemcpyAsync(disp_small, disp_out, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        if (c.metrics_out && (rc = eval_launch(ctx, c, Ho, Wo, c.disp_out))) return rc;
+    } else if (c.disp_small) {
+        VPPX_HIP(hipMemcpyAsync(c.disp_small, c.disp_out, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     }
     return 0;
 }
@@ -1851,9 +1913,11 @@ extern "C" int vppx_occ_vpp_rsgm_scaled_dev(vppx_ctx *ctx, const VppxOccParams *
 {
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
-    const int rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out, disp_small);
-    ctx->inputs_ev = nullptr; // one-shot, whatever happened
-    return rc;
+    HotCall c = hot_call(HotCall::SCALED, op, vp, rp, B, H, W, C, left, right);
+    c.sp = sp;
+    c.g = g; c.g_occ = g_occ; c.validhints = validhints;
+    c.conf_out = conf_out; c.l_vpp = l_vpp; c.r_vpp = r_vpp; c.disp_out = disp_out; c.disp_small = disp_small;
+    return vppx_hot_call_internal(ctx, c);
 }
 
 extern "C" int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
@@ -1886,32 +1950,14 @@ extern "C" int vppx_occ_vpp_rsgm_scaled_host(vppx_ctx *ctx, const VppxOccParams 
     if (r_vpp_out && (rc = ws_reserve(ctx, WS_STAGE_F, nbs, &drv))) return rc;
     if ((rc = ws_reserve(ctx, WS_HANDOFF_H, npo * sizeof(float), &dout))) return rc;
     if (disp_small && (rc = ws_reserve(ctx, WS_SCALE_HOST_D, nps * sizeof(float), &dsm))) return rc;
-    for (int attempt = 0;; attempt++) {
-        const unsigned serial_before = ctx->v3.serial;
-        rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, (const u8 *)dl, (const u8 *)dr, (const float *)dg, (const u8 *)docc,
-                         (const float *)dvh, (u8 *)dconf, (u8 *)dlv, (u8 *)drv, (float *)dout, (float *)dsm);
-        ctx->inputs_ev = nullptr;
-        if (rc) return rc;
-        if ((rc = download(ctx, disp_out, dout, npo * sizeof(float)))) return rc;
-        if (dsm && (rc = download(ctx, disp_small, dsm, nps * sizeof(float)))) return rc;
-        if (dconf && (rc = download(ctx, conf_out, dconf, nps))) return rc;
-        if (dlv && (rc = download(ctx, l_vpp_out, dlv, nbs))) return rc;
-        if (drv && (rc = download(ctx, r_vpp_out, drv, nbs))) return rc;
-        std::vector<unsigned long long> tot;
-        if (draws_out && vp->method == VPPX_METHOD_RND && ctx->ws[WS_FRAME_TOT].p && ctx->last_parts == 1 &&
-            ctx->ws[WS_FRAME_TOT].cap >= (size_t)B * 16) {
-            tot.resize((size_t)B * 2);
-            VPPX_HIP(hipMemcpyAsync(tot.data(), ctx->ws[WS_FRAME_TOT].p, tot.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        VPPX_HIP(hipStreamSynchronize(ctx->stream));
-        if (draws_out)
-            for (int f = 0; f < B; f++) draws_out[f] = tot.empty() ? 0 : tot[2 * f];
-        if ((rc = lockstep_check(ctx)) == 0) break;
-        const unsigned s = ctx->lockstep_last_serial;
-        const bool mine = (unsigned)(s - serial_before - 1u) < (unsigned)(ctx->v3.serial - serial_before);
-        if (!mine || attempt > 0) return rc;
-    }
-    return 0;
+    HotCall c = hot_call(HotCall::SCALED, op, vp, rp, B, H, W, C, (const u8 *)dl, (const u8 *)dr);
+    c.sp = sp;
+    c.g = (const float *)dg; c.g_occ = (const u8 *)docc; c.validhints = (const float *)dvh;
+    c.conf_out = (u8 *)dconf; c.l_vpp = (u8 *)dlv; c.r_vpp = (u8 *)drv; c.disp_out = (float *)dout; c.disp_small = (float *)dsm;
+    return host_call_tail(ctx, vp, B, [&]() { return scaled_call(ctx, c); },
+                          {{disp_out, dout, npo * sizeof(float)}, {disp_small, dsm, nps * sizeof(float)}, {conf_out, dconf, nps},
+                           {l_vpp_out, dlv, nbs}, {r_vpp_out, drv, nbs}},
+                          draws_out);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1982,35 +2028,24 @@ extern "C" int vppx_guided_metrics_host(vppx_ctx *ctx, const VppxEvalParams *ep,
     return 0;
 }
 
-// The scaled call with ctx->eval set for its duration: the hot path (or scaled_call, behind a restore) queues the metrics.
-// validgt: float32, or one byte per pixel (an evaluating frame stream's ring).
-int vppx_eval_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                            const VppxEvalParams *ep, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g,
-                            const uint8_t *g_occ, const float *validhints, const float *gt, const void *validgt, int valid_is_u8,
-                            uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out,
-                            float *errormap)
+// The evaluating call: the scaled call with the evaluation request resolved; the hot path (or scaled_call, behind a restore)
+// queues the metrics.  validgt: float32, or one byte per pixel (an evaluating frame stream's ring).
+static int eval_call(vppx_ctx *ctx, const HotCall &c)
 {
     int rc, s = 1;
-    if (!gt || !validgt || !metrics_out || !disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_eval: NULL argument"); return VPPX_E_INVALID_ARG; }
-    VppxScaleParams one = {1, 1};
-    if (!sp) sp = &one;
+    if (!c.gt || !c.validgt || !c.metrics_out || !c.disp_out) { vppx_set_error("vppx_occ_vpp_rsgm_eval: NULL argument"); return VPPX_E_INVALID_ARG; }
+    const VppxScaleParams one = {1, 1};
+    HotCall e = c;
+    if (!e.sp) e.sp = &one;
     int h, w, Ho, Wo;
-    if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
-    if ((rc = check_metrics_args("vppx_occ_vpp_rsgm_eval", ep, B, Ho, Wo, H, W, &s))) return rc;
+    if ((rc = vppx_scaled_shape(c.H, c.W, e.sp, &h, &w, &Ho, &Wo))) return rc;
+    if ((rc = check_metrics_args("vppx_occ_vpp_rsgm_eval", c.ep, c.B, Ho, Wo, c.H, c.W, &s))) return rc;
     {   // the records' slot is sized before anything is queued (and before a capture could begin)
         void *part = nullptr;
-        if ((rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part))) return rc;
+        if ((rc = ws_reserve(ctx, WS_METRICS_PART, (size_t)c.B * metrics_blocks_per_frame((size_t)Ho * Wo) * METRICS_PARTIAL_BYTES, &part))) return rc;
     }
-    vppx_ctx::EvalReq &e = ctx->eval;
-    e.active = true;
-    e.after_restore = false;
-    e.gt = gt; e.valid = validgt; e.valid_is_u8 = valid_is_u8;
-    e.gt_scale = s; e.Hg = H; e.Wg = W;
-    e.out = metrics_out; e.errormap = errormap;
-    rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out, disp_small);
-    ctx->eval = vppx_ctx::EvalReq();
-    ctx->inputs_ev = nullptr; // one-shot, whatever happened
-    return rc;
+    e.gt_scale = s; e.Hg = c.H; e.Wg = c.W;
+    return scaled_call(ctx, e);
 }
 
 extern "C" int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
@@ -2021,8 +2056,12 @@ extern "C" int vppx_occ_vpp_rsgm_eval_dev(vppx_ctx *ctx, const VppxOccParams *op
 {
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
-    return vppx_eval_call_internal(ctx, op, vp, rp, sp, ep, B, H, W, C, left, right, g, g_occ, validhints, gt, validgt, 0, conf_out, l_vpp, r_vpp,
-                                   disp_out, disp_small, metrics_out, errormap);
+    HotCall c = hot_call(HotCall::EVAL, op, vp, rp, B, H, W, C, left, right);
+    c.sp = sp; c.ep = ep;
+    c.g = g; c.g_occ = g_occ; c.validhints = validhints;
+    c.conf_out = conf_out; c.l_vpp = l_vpp; c.r_vpp = r_vpp; c.disp_out = disp_out; c.disp_small = disp_small;
+    c.gt = gt; c.validgt = validgt; c.metrics_out = metrics_out; c.errormap = errormap;
+    return vppx_hot_call_internal(ctx, c);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2086,73 +2125,55 @@ extern "C" int vppx_sample_hints_host(vppx_ctx *ctx, const VppxSampleParams *smp
 // first kernel of the front stage, as the resize of a scaled call is: it waits for what every front stage waits for and writes
 // the set of maps the previous call did not use.  src == NULL: gt / validgt are the source.  validsrc / validgt: float32, or one
 // byte per pixel (a frame stream's ring).
-int vppx_sampled_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                               const VppxEvalParams *ep, const VppxSampleParams *smp, int B, int H, int W, int C, const uint8_t *left,
-                               const uint8_t *right, const float *src, const void *validsrc, int vsrc_is_u8, int guided, const uint8_t *g_occ,
-                               const float *gt, const void *validgt, int vgt_is_u8, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
-                               float *disp_small, VppxMetrics *metrics_out, float *errormap, float *hints_out, float *validhints_out)
+static int sampled_call(vppx_ctx *ctx, const HotCall &c)
 {
     int rc;
     const char *const name = "vppx_occ_vpp_rsgm_sampled";
-    if (!vp || !rp || !smp || !left || !right || !disp_out) { vppx_set_error("%s: NULL argument", name); return VPPX_E_INVALID_ARG; }
-    const bool eval = gt || validgt || metrics_out;
-    if (eval && (!gt || !validgt || !metrics_out)) { vppx_set_error("%s: gt, validgt and metrics_out go together", name); return VPPX_E_INVALID_ARG; }
-    if (!eval && (ep || errormap)) { vppx_set_error("%s: ep / errormap without gt, validgt and metrics_out", name); return VPPX_E_INVALID_ARG; }
-    if ((src != nullptr) != (validsrc != nullptr)) { vppx_set_error("%s: src and validsrc go together", name); return VPPX_E_INVALID_ARG; }
+    const VppxSampleParams *const smp = c.smp;
+    const int B = c.B, H = c.H, W = c.W;
+    if (c.vp_null || !c.rp || !smp || !c.left || !c.right || !c.disp_out) { vppx_set_error("%s: NULL argument", name); return VPPX_E_INVALID_ARG; }
+    const bool eval = c.gt || c.validgt || c.metrics_out;
+    if (eval && (!c.gt || !c.validgt || !c.metrics_out)) { vppx_set_error("%s: gt, validgt and metrics_out go together", name); return VPPX_E_INVALID_ARG; }
+    if (!eval && (c.ep || c.errormap)) { vppx_set_error("%s: ep / errormap without gt, validgt and metrics_out", name); return VPPX_E_INVALID_ARG; }
+    if ((c.src != nullptr) != (c.validsrc != nullptr)) { vppx_set_error("%s: src and validsrc go together", name); return VPPX_E_INVALID_ARG; }
+    const float *src = c.src;
+    const void *validsrc = c.validsrc;
+    int vsrc_is_u8 = c.vsrc_is_u8;
     if (!src) {
-        if (!gt) { vppx_set_error("%s: src is NULL and there is no gt to sample from", name); return VPPX_E_INVALID_ARG; }
-        src = gt;
-        validsrc = validgt;
-        vsrc_is_u8 = vgt_is_u8;
+        if (!c.gt) { vppx_set_error("%s: src is NULL and there is no gt to sample from", name); return VPPX_E_INVALID_ARG; }
+        src = c.gt;
+        validsrc = c.validgt;
+        vsrc_is_u8 = c.valid_is_u8;
     }
     if ((rc = check_sample_args(name, smp, B, H, W))) return rc;
-    VppxScaleParams one = {1, 1};
-    if (!sp) sp = &one;
+    const VppxScaleParams one = {1, 1};
+    HotCall run = c; // the scaled / evaluating call behind the sampling
+    if (!run.sp) run.sp = &one;
     {   // everything the call itself would refuse is refused before the sampling is queued
         int h, w, Ho, Wo, s = 1;
-        if ((rc = vppx_scaled_shape(H, W, sp, &h, &w, &Ho, &Wo))) return rc;
-        if ((rc = check_frames(B, H, W, C))) return rc;
-        if ((rc = check_frames(B, h, w, C))) return rc;
-        if ((rc = check_vpp_params(*vp))) return rc;
-        if ((rc = check_rsgm_params(*rp))) return rc;
-        if (eval && (rc = check_metrics_args(name, ep, B, Ho, Wo, H, W, &s))) return rc;
+        if ((rc = vppx_scaled_shape(H, W, run.sp, &h, &w, &Ho, &Wo))) return rc;
+        if ((rc = check_frames(B, H, W, c.C))) return rc;
+        if ((rc = check_frames(B, h, w, c.C))) return rc;
+        if ((rc = check_vpp_params(c.vp))) return rc;
+        if ((rc = check_rsgm_params(*c.rp))) return rc;
+        if (eval && (rc = check_metrics_args(name, c.ep, B, Ho, Wo, H, W, &s))) return rc;
     }
     if ((rc = lockstep_check(ctx))) return rc;
-    const bool piped = pipeline_applies(ctx);
-    const int set = piped ? ctx->sample_parity : 0;
+    const int set = pipeline_applies(ctx) ? ctx->sample_parity : 0;
     const size_t np = (size_t)B * H * W;
     float *gs, *vs = nullptr;
     if ((rc = ws_get(ctx, set ? WS_SAMPLE_G1 : WS_SAMPLE_G0, np, &gs))) return rc;
-    if ((guided || validhints_out) && (rc = ws_get(ctx, set ? WS_SAMPLE_V1 : WS_SAMPLE_V0, np, &vs))) return rc;
+    if ((c.guided || c.validhints_out) && (rc = ws_get(ctx, set ? WS_SAMPLE_V1 : WS_SAMPLE_V0, np, &vs))) return rc;
     const u32 T = sample_threshold(smp->probability);
-    if (piped) {
-        if (!ctx->ev_sampled) VPPX_HIP(hipEventCreateWithFlags(&ctx->ev_sampled, hipEventDisableTiming));
-        if ((rc = front_begin(ctx))) return rc;
-        rc = sample_launch(ctx, B, (size_t)H * W, src, validsrc, vsrc_is_u8, gs, vs, nullptr, smp->seed, T);
-        const hipError_t e = rc ? hipSuccess : hipEventRecord(ctx->ev_sampled, ctx->stream);
-        ctx->stream = ctx->main_saved;
-        ctx->front_active = false;
-        if (rc) return rc;
-        if (e != hipSuccess) { vppx_set_error("hipEventRecord failed: %s", hipGetErrorString(e)); return VPPX_E_HIP; }
-        ctx->sample_parity ^= 1;
-        ctx->inputs_ev = (void *)ctx->ev_sampled;
-    } else {
-        if (ctx->inputs_ev) {
-            VPPX_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->inputs_ev, 0));
-            ctx->inputs_ev = nullptr;
-        }
-        if ((rc = sample_launch(ctx, B, (size_t)H * W, src, validsrc, vsrc_is_u8, gs, vs, nullptr, smp->seed, T))) return rc;
-    }
-    if (eval)
-        rc = vppx_eval_call_internal(ctx, op, vp, rp, sp, ep, B, H, W, C, left, right, gs, g_occ, guided ? vs : nullptr, gt, validgt, vgt_is_u8,
-                                     conf_out, l_vpp, r_vpp, disp_out, disp_small, metrics_out, errormap);
-    else
-        rc = scaled_call(ctx, op, vp, rp, sp, B, H, W, C, left, right, gs, g_occ, guided ? vs : nullptr, conf_out, l_vpp, r_vpp, disp_out, disp_small);
-    ctx->inputs_ev = nullptr; // one-shot, whatever happened
-    if (rc) return rc;
+    if ((rc = pre_front(ctx, &ctx->ev_sampled, &ctx->sample_parity,
+                        [&]() { return sample_launch(ctx, B, (size_t)H * W, src, validsrc, vsrc_is_u8, gs, vs, nullptr, smp->seed, T); })))
+        return rc;
+    run.g = gs;
+    run.validhints = c.guided ? vs : nullptr;
+    if ((rc = eval ? eval_call(ctx, run) : scaled_call(ctx, run))) return rc;
     // the caller's copies of the maps, in launch-stream order (the launch stream has waited for the front stage by now)
-    if (hints_out) VPPX_HIP(hipMemcpyAsync(hints_out, gs, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (validhints_out) VPPX_HIP(hipMemcpyAsync(validhints_out, vs, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (c.hints_out) VPPX_HIP(hipMemcpyAsync(c.hints_out, gs, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (c.validhints_out) VPPX_HIP(hipMemcpyAsync(c.validhints_out, vs, np * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
 }
 
@@ -2165,8 +2186,13 @@ extern "C" int vppx_occ_vpp_rsgm_sampled_dev(vppx_ctx *ctx, const VppxOccParams 
 {
     VPPX_ENTER(ctx);
     VPPX_PIPE_KEEP(ctx);
-    return vppx_sampled_call_internal(ctx, op, vp, rp, sp, ep, smp, B, H, W, C, left, right, src, validsrc, 0, guided, g_occ, gt, validgt, 0, conf_out,
-                                      l_vpp, r_vpp, disp_out, disp_small, metrics_out, errormap, hints_out, validhints_out);
+    HotCall c = hot_call(HotCall::SAMPLED, op, vp, rp, B, H, W, C, left, right);
+    c.sp = sp; c.ep = ep; c.smp = smp;
+    c.g_occ = g_occ;
+    c.conf_out = conf_out; c.l_vpp = l_vpp; c.r_vpp = r_vpp; c.disp_out = disp_out; c.disp_small = disp_small;
+    c.gt = gt; c.validgt = validgt; c.metrics_out = metrics_out; c.errormap = errormap;
+    c.src = src; c.validsrc = validsrc; c.guided = guided; c.hints_out = hints_out; c.validhints_out = validhints_out;
+    return vppx_hot_call_internal(ctx, c);
 }
 
 // Batches larger than one round of the lock-step kernel are run as consecutive parts of one round each ("batch quantum":
@@ -2179,11 +2205,12 @@ extern "C" int vppx_occ_vpp_rsgm_sampled_dev(vppx_ctx *ctx, const VppxOccParams 
 // the first full part) so that the last part -- the one the timing helpers re-launch -- is a whole round.  With
 // vppx_set_pipeline the front stage of a part runs under the previous part's sum / WTA and post kernels, as between calls.
 // VPPX_CHUNK=0 keeps whole batches, VPPX_CHUNK=n forces parts of n frames.
-static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
-                          int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                          const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+static int vpp_rsgm_parts(vppx_ctx *ctx, const HotCall &c)
 {
     int rc;
+    const VppxRsgmParams *const rp = c.rp;
+    const int B = c.B, H = c.H, W = c.W, C = c.C;
+    const bool validhints = c.validhints != nullptr;
     const int chunk_env = ctx->knobs.chunk;
     int q = 0;
     if (chunk_env > 0) {
@@ -2204,21 +2231,17 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             if (fused) q = fpr;
         }
     }
-    bool budget = false; // guided: parts of the memory budget (a remainder is a part of its own, never merged into a full one)
+    // guided: parts of at most the memory budget; a remainder is a part of its own, never merged into a full one (a forced part
+    // of as many frames as the budget holds, plus the remainder, would be past it)
     if (validhints) {
         const int fb = guided_frames_per_part(ctx, H, W, C, rp->dmax);
-        if (fb < B && (q <= 0 || q > fb)) {
-            q = fb;
-            budget = true;
-        }
+        if (fb < B && (q <= 0 || q > fb)) q = fb;
     }
     ctx->last_parts = 1;
-    if (q <= 0 || q >= B)
-        return vpp_rsgm_one(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+    if (q <= 0 || q >= B) return vpp_rsgm_one(ctx, c);
     ctx->last_parts = 0;
-    const size_t fpx = (size_t)H * W;
     void *const inputs_ev = ctx->inputs_ev; // one-shot per CALL: every part's front stage may start on it
-    // The plan.  Forced part sizes (VPPX_CHUNK=n): the remainder first, riding on the first full part below 8 frames.  Default
+    // The plan.  Forced part sizes (VPPX_CHUNK=n): the remainder first, riding on the first full part below 8 frames (unguided).  Default
     // (q = one round of the lock-step kernel): whole rounds; a remainder is spread over them when that adds at most a third
     // of a round to each -- such a part runs its whole round, then the extra frames as an under-filled lock-step launch next
     // to its W/E launch (rsgm_vert3_plan), which costs less than a part of its own with its exposed front / post tail
@@ -2226,14 +2249,14 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
     std::vector<int> plan;
     {
         const int k = B / q, r = B % q;
-        if (chunk_env < 0 && !budget && r > 0 && k >= 1 && 3 * ((r + k - 1) / k) <= q) {
+        if (chunk_env < 0 && !validhints && r > 0 && k >= 1 && 3 * ((r + k - 1) / k) <= q) {
             for (int i = 0; i < k; i++) plan.push_back(q + r / k + (i < r % k ? 1 : 0));
         } else {
             int left_over = B;
             while (left_over > 0) {
                 int nb = left_over % q;
                 if (nb == 0) nb = q;
-                else if (nb < 8 && left_over > q && !budget) nb += q; // a few frames do not make a launch of their own
+                else if (nb < 8 && left_over > q && !validhints) nb += q; // a few frames do not make a launch of their own
                 plan.push_back(nb);
                 left_over -= nb;
             }
@@ -2244,16 +2267,10 @@ static int vpp_rsgm_parts(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
     struct DrawsRestore { vppx_ctx *c; unsigned long long *p; ~DrawsRestore() { c->draws_dst = p; } } draws_restore{ctx, draws_base};
     for (size_t pi = 0; pi < plan.size(); pi++) {
         const int nb = plan[pi];
-        VppxVppParams v2 = *vp;
-        v2.seed = vp->seed + (uint32_t)lo; // frame f keeps srand(seed + f) whatever the split
         ctx->inputs_ev = inputs_ev;
         ctx->stage_append = lo > 0;
         ctx->draws_dst = draws_base ? draws_base + lo : nullptr;
-        rc = vpp_rsgm_one(ctx, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C,
-                          g + (size_t)lo * fpx, g_occ ? g_occ + (size_t)lo * fpx : nullptr,
-                          validhints ? validhints + (size_t)lo * fpx : nullptr, conf_out ? conf_out + (size_t)lo * fpx : nullptr,
-                          l_vpp ? l_vpp + (size_t)lo * fpx * C : nullptr, r_vpp ? r_vpp + (size_t)lo * fpx * C : nullptr,
-                          disp_out + (size_t)lo * fpx);
+        rc = vpp_rsgm_one(ctx, c.frames(lo, nb));
         ctx->stage_append = false;
         if (rc) return rc;
         ctx->last_parts++;
@@ -2272,18 +2289,14 @@ extern "C" int vppx_wsum_default_route(int B, int Hp, int Wp, int dmax, int p2ma
 
 // The parts of a call and, for an evaluating call whose map is complete with them, its metrics: once, over the whole batch,
 // behind the last part -- and inside the capture when the call is being captured.
-static int vpp_rsgm_parts_eval(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
-                               int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                               const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+static int vpp_rsgm_parts_eval(vppx_ctx *ctx, const HotCall &c)
 {
-    const int rc = vpp_rsgm_parts(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
-    if (rc || !ctx->eval.active || ctx->eval.after_restore) return rc;
-    return eval_launch(ctx, B, H, W, disp_out);
+    const int rc = vpp_rsgm_parts(ctx, c);
+    if (rc || !c.metrics_out) return rc;
+    return eval_launch(ctx, c, c.H, c.W, c.disp_out);
 }
 
-static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H,
-                          int W, int C, const uint8_t *left, const uint8_t *right, const float *g, const uint8_t *g_occ,
-                          const float *validhints, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out)
+static int vpp_rsgm_entry(vppx_ctx *ctx, const HotCall &c)
 {
     int rc;
     routes_reset(ctx); // (sub-stream children record into their own lists: not merged here)
@@ -2291,9 +2304,11 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
     ctx->front_routes_keep = false;
     const size_t front_base = ctx->front_routes.size(); // (what a host wrapper queued before this: not part of a captured graph)
     if ((rc = lockstep_check(ctx))) return rc;
-    if (!vp || !rp || !left || !right || !g || !disp_out) { vppx_set_error("vppx_vpp_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
-    if ((rc = check_frames(B, H, W, C))) return rc;
-    if ((rc = check_vpp_params(*vp))) return rc;
+    if (c.vp_null || !c.rp || !c.left || !c.right || !c.g || !c.disp_out) { vppx_set_error("vppx_vpp_rsgm: NULL argument"); return VPPX_E_INVALID_ARG; }
+    const VppxRsgmParams *const rp = c.rp;
+    const int B = c.B;
+    if ((rc = check_frames(B, c.H, c.W, c.C))) return rc;
+    if ((rc = check_vpp_params(c.vp))) return rc;
     if ((rc = check_rsgm_params(*rp))) return rc;
     if (ctx->inputs_ev && !pipeline_applies(ctx)) { // not pipelined: the inputs event is simply waited for on the launch stream
         VPPX_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->inputs_ev, 0));
@@ -2304,16 +2319,15 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         // hipGraph replay: launch-bound small batches pay ~40 kernel launches per call otherwise
         vppx_ctx::GraphKey key;
         memset(&key, 0, sizeof(key));
-        key.B = B; key.H = H; key.W = W; key.C = C; key.vp = *vp; key.rp = *rp;
-        key.ptr[0] = left; key.ptr[1] = right; key.ptr[2] = g; key.ptr[3] = g_occ; key.ptr[4] = l_vpp; key.ptr[5] = r_vpp;
-        key.ptr[6] = disp_out; key.ptr[7] = conf_out; key.ptr[8] = validhints;
-        key.has_op = op ? 1 : 0;
-        if (op) key.op = *op;
+        key.B = B; key.H = c.H; key.W = c.W; key.C = c.C; key.vp = c.vp; key.rp = *rp;
+        key.ptr[0] = c.left; key.ptr[1] = c.right; key.ptr[2] = c.g; key.ptr[3] = c.g_occ; key.ptr[4] = c.l_vpp; key.ptr[5] = c.r_vpp;
+        key.ptr[6] = c.disp_out; key.ptr[7] = c.conf_out; key.ptr[8] = c.validhints;
+        key.has_op = c.op ? 1 : 0;
+        if (c.op) key.op = *c.op;
         key.stream = (void *)ctx->stream;
-        if (ctx->eval.active && !ctx->eval.after_restore) {
-            const vppx_ctx::EvalReq &e = ctx->eval;
-            key.eval_ptr[0] = e.gt; key.eval_ptr[1] = e.valid; key.eval_ptr[2] = e.out; key.eval_ptr[3] = e.errormap;
-            key.eval_scale[0] = e.gt_scale; key.eval_scale[1] = e.Hg; key.eval_scale[2] = e.Wg; key.eval_scale[3] = e.valid_is_u8;
+        if (c.metrics_out) { // (the metrics this call queues itself: they are part of the captured graph)
+            key.eval_ptr[0] = c.gt; key.eval_ptr[1] = c.validgt; key.eval_ptr[2] = c.metrics_out; key.eval_ptr[3] = c.errormap;
+            key.eval_scale[0] = c.gt_scale; key.eval_scale[1] = c.Hg; key.eval_scale[2] = c.Wg; key.eval_scale[3] = c.valid_is_u8;
         }
         key.ws_gen = ctx->ws_gen;
         // the graph does not contain the penalty-table upload: it must still be the table of these parameters
@@ -2331,7 +2345,7 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
                 ctx->capturing = true;
-                rc = vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+                rc = vpp_rsgm_parts_eval(ctx, c);
                 ctx->capturing = false;
                 hipGraph_t graph = nullptr;
                 e = hipStreamEndCapture(ctx->stream, &graph);
@@ -2362,15 +2376,15 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
             // capture is not possible here (e.g. the legacy default stream): stay on the eager path
             (void)hipGetLastError();
             ctx->graph_mode = false;
-            return vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+            return vpp_rsgm_parts_eval(ctx, c);
         }
-        rc = vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+        rc = vpp_rsgm_parts_eval(ctx, c);
         key.ws_gen = ctx->ws_gen; // the workspace as this call left it
         ctx->lastkey = key;
         ctx->have_lastkey = (rc == 0);
         return rc;
     }
-    if (nsub <= 1) return vpp_rsgm_parts_eval(ctx, op, vp, rp, B, H, W, C, left, right, g, g_occ, validhints, conf_out, l_vpp, r_vpp, disp_out);
+    if (nsub <= 1) return vpp_rsgm_parts_eval(ctx, c);
     // Frames are independent: split the batch over child contexts (own stream + arena).  The
     // latency-bound stages of one part (VPP replay, post-processing) then overlap the
     // bandwidth-bound stages of another (aggregation stores, sum/WTA loads).
@@ -2386,30 +2400,19 @@ static int vpp_rsgm_entry(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppP
         }
     }
     VPPX_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-    const size_t fpx = (size_t)H * W;
     int lo = 0;
     for (int i = 0; i < nsub; i++) {
         const int nb = B / nsub + (i < B % nsub ? 1 : 0);
-        vppx_ctx *c = ctx->sub[i];
-        VPPX_HIP(hipStreamWaitEvent(c->stream, ctx->ev_fork, 0));
-        VppxVppParams v2 = *vp;
-        v2.seed = vp->seed + (uint32_t)lo; // frame f keeps srand(seed + f) whatever the split
+        vppx_ctx *sub = ctx->sub[i];
+        VPPX_HIP(hipStreamWaitEvent(sub->stream, ctx->ev_fork, 0));
         // (a guided part goes through the parts of its own context: the memory budget holds for it as well)
-        const uint8_t *const occ_i = g_occ ? g_occ + (size_t)lo * fpx : nullptr;
-        uint8_t *const conf_i = conf_out ? conf_out + (size_t)lo * fpx : nullptr;
-        uint8_t *const lv_i = l_vpp ? l_vpp + (size_t)lo * fpx * C : nullptr, *const rv_i = r_vpp ? r_vpp + (size_t)lo * fpx * C : nullptr;
-        if (validhints)
-            rc = vpp_rsgm_parts(c, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C, g + (size_t)lo * fpx,
-                                occ_i, validhints + (size_t)lo * fpx, conf_i, lv_i, rv_i, disp_out + (size_t)lo * fpx);
-        else
-            rc = vpp_rsgm_one(c, op, &v2, rp, nb, H, W, C, left + (size_t)lo * fpx * C, right + (size_t)lo * fpx * C,
-                              g + (size_t)lo * fpx, occ_i, nullptr, conf_i, lv_i, rv_i, disp_out + (size_t)lo * fpx);
-        if (rc) return rc;
-        VPPX_HIP(hipEventRecord(ctx->sub_done[i], c->stream));
+        const HotCall part = c.frames(lo, nb);
+        if ((rc = c.validhints ? vpp_rsgm_parts(sub, part) : vpp_rsgm_one(sub, part))) return rc;
+        VPPX_HIP(hipEventRecord(ctx->sub_done[i], sub->stream));
         VPPX_HIP(hipStreamWaitEvent(ctx->stream, ctx->sub_done[i], 0));
         lo += nb;
     }
-    if (ctx->eval.active && !ctx->eval.after_restore && (rc = eval_launch(ctx, B, H, W, disp_out))) return rc;
+    if (c.metrics_out && (rc = eval_launch(ctx, c, c.H, c.W, c.disp_out))) return rc;
     // timing helpers look at the last geometry of the first child
     ctx->have_last = false;
     ctx->last_parts = 0; // the children's arenas hold the per-frame draw totals, not this context's (vppx_occ_vpp_rsgm_host reports 0)

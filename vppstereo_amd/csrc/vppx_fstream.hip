@@ -25,23 +25,6 @@
 #include <string.h>
 #include <thread>
 
-int vppx_lockstep_check_internal(vppx_ctx *ctx); // vppx_api.hip
-int vppx_check_hot_path_args_internal(const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H, int W, int C);
-extern "C" int vppx_occ_vpp_rsgm_scaled_dev(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp,
-                                            const VppxScaleParams *sp, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right,
-                                            const float *g, const uint8_t *g_occ, const float *validhints, uint8_t *conf_out, uint8_t *l_vpp,
-                                            uint8_t *r_vpp, float *disp_out, float *disp_small);
-int vppx_eval_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                            const VppxEvalParams *ep, int B, int H, int W, int C, const uint8_t *left, const uint8_t *right, const float *g,
-                            const uint8_t *g_occ, const float *validhints, const float *gt, const void *validgt, int valid_is_u8,
-                            uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out, float *disp_small, VppxMetrics *metrics_out,
-                            float *errormap); // vppx_api.hip
-int vppx_sampled_call_internal(vppx_ctx *ctx, const VppxOccParams *op, const VppxVppParams *vp, const VppxRsgmParams *rp, const VppxScaleParams *sp,
-                               const VppxEvalParams *ep, const VppxSampleParams *smp, int B, int H, int W, int C, const uint8_t *left,
-                               const uint8_t *right, const float *src, const void *validsrc, int vsrc_is_u8, int guided, const uint8_t *g_occ,
-                               const float *gt, const void *validgt, int vgt_is_u8, uint8_t *conf_out, uint8_t *l_vpp, uint8_t *r_vpp, float *disp_out,
-                               float *disp_small, VppxMetrics *metrics_out, float *errormap, float *hints_out, float *validhints_out); // vppx_api.hip
-
 namespace {
 
 using vppx_host::CopyJob;
@@ -384,62 +367,62 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
         }
         VPPX_HIP(hipEventRecord(s.ev_in, fs->s_in));
     }
-    VppxVppParams vp = fs->vp;
-    vp.seed = s.seed;
     // the hot path reports an earlier call's lost lock step instead of running (its caller could not tell otherwise): a stream
     // looks first, keeps going -- the context now rests on the line-parallel layout -- and re-runs what was in flight at the next pop
     if (vppx_lockstep_check_internal(ctx) != 0) fs->lost_pending = true;
-    u8 *lv = (fs->flags & VPPX_FS_PATTERNS) ? s.d_out + fs->o_lv : nullptr;
-    u8 *rv = (fs->flags & VPPX_FS_PATTERNS) ? s.d_out + fs->o_rv : nullptr;
+    // The batch as one call.  VPPX_FS_SAMPLE: the hints are sampled on the device in front of the batch (a re-run samples again:
+    // the same bytes), from the ring's src and one-byte validity planes or, without them, from its gt planes; frame f of the stream
+    // samples with smp.seed + f.  VPPX_FS_METRICS: behind the batch's post stage on the launch stream, its metrics (a re-run
+    // queues them again with the batch): they read the ring's gt and one-byte validity planes, which the inputs event covers like
+    // the other inputs.  A guided batch never takes the lock-step kernel: no re-run.
+    const int flags = fs->flags;
+    const bool sampling = (flags & VPPX_FS_SAMPLE) != 0, ev = (flags & VPPX_FS_METRICS) != 0, guided = (flags & VPPX_FS_GUIDED) != 0;
+    VppxSampleParams smp = fs->smp;
+    smp.seed = fs->smp.seed + (s.seed - fs->vp.seed);
+    HotCall c;
+    c.layer = sampling ? HotCall::SAMPLED : ev ? HotCall::EVAL : fs->scaled ? HotCall::SCALED : HotCall::PLAIN;
+    c.op = fs->have_op ? &fs->op : nullptr;
+    c.vp = fs->vp;
+    c.vp.seed = s.seed;
+    c.rp = &fs->rp;
+    c.sp = fs->scaled ? &fs->sp : nullptr;
+    c.ep = ev ? &fs->ep : nullptr;
+    c.B = nb; c.H = fs->H; c.W = fs->W; c.C = fs->C;
+    c.left = s.d_in + fs->o_left;
+    c.right = s.d_in + fs->o_right;
+    if (sampling) {
+        c.smp = &smp;
+        if (s.has_src) {
+            c.src = (const float *)(s.d_in + fs->o_hint);
+            c.validsrc = s.d_in + fs->o_vsrc;
+        }
+        c.vsrc_is_u8 = 1;
+        c.guided = guided;
+    } else {
+        c.g = (const float *)(s.d_in + fs->o_hint);
+        if (guided) c.validhints = (const float *)(s.d_in + fs->o_valid);
+    }
+    if (flags & VPPX_FS_GOCC) c.g_occ = s.d_in + fs->o_gocc;
+    if (ev) {
+        c.gt = (const float *)(s.d_in + fs->o_gt);
+        c.validgt = s.d_in + fs->o_vgt;
+        c.metrics_out = (VppxMetrics *)(s.d_out + fs->o_metrics);
+    }
+    c.valid_is_u8 = 1;
+    if (flags & VPPX_FS_MASK) c.conf_out = s.d_out + fs->o_conf;
+    if (flags & VPPX_FS_PATTERNS) {
+        c.l_vpp = s.d_out + fs->o_lv;
+        c.r_vpp = s.d_out + fs->o_rv;
+    }
+    c.disp_out = (float *)(s.d_out + fs->o_disp);
+    const bool method_rnd = c.vp.method == VPPX_METHOD_RND;
     int rc = 0;
     for (int attempt = 0;; attempt++) {
         const long lost_before = ctx->lockstep_failures;
         rc = vppx_inputs_ready_event(ctx, (void *)s.ev_in);
         if (rc) return rc;
-        ctx->draws_dst = (vp.method == VPPX_METHOD_RND) ? (unsigned long long *)(s.d_out + fs->o_draws) : nullptr;
-        if (fs->flags & VPPX_FS_SAMPLE) {
-            // the hints are sampled on the device in front of the batch (a re-run samples again: the same bytes), from the ring's
-            // src and one-byte validity planes or, without them, from its gt planes; frame f of the stream samples with smp.seed + f
-            const bool ev = (fs->flags & VPPX_FS_METRICS) != 0;
-            VppxSampleParams smp = fs->smp;
-            smp.seed = fs->smp.seed + (s.seed - fs->vp.seed);
-            rc = vppx_sampled_call_internal(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, fs->scaled ? &fs->sp : nullptr, ev ? &fs->ep : nullptr,
-                                            &smp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right,
-                                            s.has_src ? (const float *)(s.d_in + fs->o_hint) : nullptr, s.has_src ? s.d_in + fs->o_vsrc : nullptr, 1,
-                                            (fs->flags & VPPX_FS_GUIDED) ? 1 : 0, (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
-                                            ev ? (const float *)(s.d_in + fs->o_gt) : nullptr, ev ? s.d_in + fs->o_vgt : nullptr, 1,
-                                            (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp), nullptr,
-                                            ev ? (VppxMetrics *)(s.d_out + fs->o_metrics) : nullptr, nullptr, nullptr, nullptr);
-        } else if (fs->flags & VPPX_FS_METRICS) {
-            // the batch and, behind its post stage on the launch stream, its metrics (a re-run queues them again with the batch):
-            // they read the ring's gt and one-byte validity planes, which the inputs event covers like the other inputs
-            rc = vppx_eval_call_internal(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, fs->scaled ? &fs->sp : nullptr, &fs->ep, nb, fs->H, fs->W,
-                                         fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
-                                         (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
-                                         (fs->flags & VPPX_FS_GUIDED) ? (const float *)(s.d_in + fs->o_valid) : nullptr,
-                                         (const float *)(s.d_in + fs->o_gt), s.d_in + fs->o_vgt, 1,
-                                         (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp), nullptr,
-                                         (VppxMetrics *)(s.d_out + fs->o_metrics), nullptr);
-        } else if (fs->scaled)
-            rc = vppx_occ_vpp_rsgm_scaled_dev(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, &fs->sp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left,
-                                              s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
-                                              (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr,
-                                              (fs->flags & VPPX_FS_GUIDED) ? (const float *)(s.d_in + fs->o_valid) : nullptr,
-                                              (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp),
-                                              nullptr);
-        else if (fs->flags & VPPX_FS_GUIDED) // (never the lock-step kernel: no re-run)
-            rc = vppx_occ_vpp_rsgm_guided_dev(ctx, fs->have_op ? &fs->op : nullptr, &vp, &fs->rp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left,
-                                              s.d_in + fs->o_right, (const float *)(s.d_in + fs->o_hint),
-                                              (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr, (const float *)(s.d_in + fs->o_valid),
-                                              (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv, (float *)(s.d_out + fs->o_disp));
-        else if (fs->have_op)
-            rc = vppx_occ_vpp_rsgm_dev(ctx, &fs->op, &vp, &fs->rp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right,
-                                       (const float *)(s.d_in + fs->o_hint), (fs->flags & VPPX_FS_MASK) ? s.d_out + fs->o_conf : nullptr, lv, rv,
-                                       (float *)(s.d_out + fs->o_disp));
-        else
-            rc = vppx_vpp_rsgm_dev(ctx, &vp, &fs->rp, nb, fs->H, fs->W, fs->C, s.d_in + fs->o_left, s.d_in + fs->o_right,
-                                   (const float *)(s.d_in + fs->o_hint), (fs->flags & VPPX_FS_GOCC) ? s.d_in + fs->o_gocc : nullptr, lv, rv,
-                                   (float *)(s.d_out + fs->o_disp));
+        ctx->draws_dst = method_rnd ? (unsigned long long *)(s.d_out + fs->o_draws) : nullptr;
+        rc = vppx_hot_call_internal(ctx, c);
         ctx->draws_dst = nullptr;
         // A launch still in flight can lose its lock step between the look above and the hot path's own look, just before it queues
         // the aggregation (the deeper the ring, the more launches are in flight): the call then reports that instead of running.
@@ -452,7 +435,7 @@ static int fs_submit(vppx_fstream *fs, Slot &s, bool upload)
     }
     if (rc) return rc;
     VPPX_HIP(hipEventRecord(s.ev_done, ctx->stream));
-    s.out_method_rnd = vp.method == VPPX_METHOD_RND;
+    s.out_method_rnd = method_rnd;
     s.out_pending = true;
     // Copy-outs ride in the NEXT batch, behind its aggregation: the lock-step launch goes at the pace of its slowest CU, and a CU
     // that also hosts copy-out waves (stores over PCIe back up its memory pipeline) is slow -- next to the copy-out the launch took

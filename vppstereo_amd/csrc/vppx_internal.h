@@ -323,19 +323,80 @@ struct vppx_ctx {
     // hint sampling in front of a fused call (vppx_occ_vpp_rsgm_sampled_dev): which set of sampled maps the next pipelined call writes
     int sample_parity = 0;
     hipEvent_t ev_sampled = nullptr;
-    // guided_metrics behind the running fused call (vppx_occ_vpp_rsgm_eval_dev, an evaluating frame stream): queued on the launch
-    // stream once the whole batch's map is complete -- behind the last part, inside a graph capture, behind the restore
-    struct EvalReq {
-        bool active = false;
-        bool after_restore = false; // the map the metrics read is the restored one: scaled_call queues them, not the hot path
-        const float *gt = nullptr;
-        const void *valid = nullptr;
-        int valid_is_u8 = 0;
-        int gt_scale = 1, Hg = 0, Wg = 0;
-        VppxMetrics *out = nullptr;
-        float *errormap = nullptr;
-    } eval;
 };
+
+// ---------------------------------------------------------------------------------------
+// One fused hot-path call (VPP -> rSGM; scaled, evaluated, sampled on request) as every layer between an entry point and the
+// kernels takes it.  The entry points and a frame stream fill one and hand it down; no layer spells the bundle out again.
+// ---------------------------------------------------------------------------------------
+struct HotCall {
+    enum Layer { PLAIN, SCALED, EVAL, SAMPLED };
+    Layer layer = PLAIN;                   // where the call enters: that layer's checks and messages come first
+    // parameter blocks
+    const VppxOccParams *op = nullptr;     // NULL: no occlusion heuristic on the way; g_occ (may be NULL) is the caller's mask
+    VppxVppParams vp = {};                 // (by value: frames() moves the seed)
+    bool vp_null = false;                  // the caller passed none: refused together with the layer's other NULL arguments
+    const VppxRsgmParams *rp = nullptr;
+    const VppxScaleParams *sp = nullptr;   // NULL: unscaled.  Below the scaled layer always NULL: the call at the shape it runs at
+    const VppxEvalParams *ep = nullptr;    // NULL: gt_scale 1
+    const VppxSampleParams *smp = nullptr;
+    int B = 0, H = 0, W = 0, C = 0;
+    // inputs
+    const u8 *left = nullptr, *right = nullptr;
+    const float *g = nullptr;              // the hints (a sampled call: NULL, they are sampled on the way)
+    const u8 *g_occ = nullptr;
+    const float *validhints = nullptr;     // not NULL: --guided
+    // outputs
+    u8 *conf_out = nullptr, *l_vpp = nullptr, *r_vpp = nullptr;
+    float *disp_out = nullptr, *disp_small = nullptr;
+    // evaluation request (metrics_out != NULL below the evaluating layer: guided_metrics of the result, queued behind it)
+    const float *gt = nullptr;
+    const void *validgt = nullptr;         // float32, or one byte per pixel (valid_is_u8: an evaluating frame stream's ring)
+    int valid_is_u8 = 0;
+    VppxMetrics *metrics_out = nullptr;
+    float *errormap = nullptr;
+    int gt_scale = 1, Hg = 0, Wg = 0;      // (resolved by the evaluating layer: ep's scale and the shape of gt / validgt)
+    // sampling request
+    const float *src = nullptr;            // NULL: gt / validgt are the source
+    const void *validsrc = nullptr;        // float32, or one byte per pixel (vsrc_is_u8: a sampling frame stream's ring)
+    int vsrc_is_u8 = 0, guided = 0;
+    float *hints_out = nullptr, *validhints_out = nullptr;
+
+    // Frames lo .. lo + nb of a call at its run shape (sp == NULL: every plane but gt / validgt has the frame shape H x W): the one
+    // place that knows which planes are per frame and what their strides are.  NULL stays NULL; frame f keeps srand(seed + f).
+    HotCall frames(int lo, int nb) const
+    {
+        HotCall p = *this;
+        const size_t px = (size_t)lo * H * W, gpx = (size_t)lo * Hg * Wg;
+        auto at = [](auto *ptr, size_t n) { return ptr ? ptr + n : nullptr; };
+        p.B = nb;
+        p.vp.seed = vp.seed + (uint32_t)lo;
+        p.left = at(left, px * C);
+        p.right = at(right, px * C);
+        p.g = at(g, px);
+        p.g_occ = at(g_occ, px);
+        p.validhints = at(validhints, px);
+        p.conf_out = at(conf_out, px);
+        p.l_vpp = at(l_vpp, px * C);
+        p.r_vpp = at(r_vpp, px * C);
+        p.disp_out = at(disp_out, px);
+        p.disp_small = at(disp_small, px);
+        p.gt = at(gt, gpx);
+        p.validgt = at((const u8 *)validgt, gpx * (valid_is_u8 ? 1 : sizeof(float)));
+        p.metrics_out = at(metrics_out, (size_t)lo);
+        p.errormap = at(errormap, px);
+        p.src = at(src, px);
+        p.validsrc = at((const u8 *)validsrc, px * (vsrc_is_u8 ? 1 : sizeof(float)));
+        p.hints_out = at(hints_out, px);
+        p.validhints_out = at(validhints_out, px);
+        return p;
+    }
+};
+// vppx_api.hip, for vppx_fstream.hip: the call (every entry point's route is one of these layers), an earlier call's lost lock
+// step, and the argument checks of the fused entry points for a stream to make when it is CREATED
+int vppx_hot_call_internal(vppx_ctx *ctx, const HotCall &c);
+int vppx_lockstep_check_internal(vppx_ctx *ctx);
+int vppx_check_hot_path_args_internal(const VppxVppParams *vp, const VppxRsgmParams *rp, int B, int H, int W, int C);
 
 int ws_reserve(vppx_ctx *ctx, WsSlot s, size_t bytes, void **out);
 template <typename T>

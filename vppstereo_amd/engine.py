@@ -158,6 +158,54 @@ class Engine:
         _lib.check(self.lib.vppx_rsgm_mid_dev(self.ctx.handle, B, Hp, Wp, _ptr(disp_l), _ptr(disp_r), _ptr(out_l), _ptr(out_r)))
         return out_l, out_r
 
+    def _chk_call(self, left, right, planes, scale, g_occ, heuristic, out, l_vpp, r_vpp, occ_out, disp_small=None, gt_scale=None,
+                  errormap=None):
+        """The tensors of one `vpp_rsgm` call, whatever its route.  left / right: uint8 [B,H,W,C]; planes: (tensor or None, name)
+        pairs of the float32 [B,H,W] maps at the full frame shape (hints, validhints, gt, ...); scale: (iscale, oscale), or None
+        for the unscaled call.  g_occ (a tensor), occ_out, l_vpp, r_vpp and disp_small have the shape (h, w) the call runs at,
+        out -- allocated here when None -- and errormap the restored one (Ho, Wo); gt_scale: given, it must take (H, W) there.
+        Returns (B, H, W, C, out)."""
+        torch = self.torch
+        self._chk(left, torch.uint8, 4, "left")
+        B, H, W, Cc = left.shape
+        if Cc not in (1, 3):
+            raise ValueError("left: channels must be 1 or 3")
+        self._chk(right, torch.uint8, 4, "right", left.shape)
+        h, w, Ho, Wo = _lib.scaled_shape(H, W, *scale) if scale else (H, W, H, W)
+        for t, n in planes:
+            if t is not None:
+                self._chk(t, torch.float32, 3, n, (B, H, W))
+        if gt_scale is not None:
+            _lib.check_gt_shape(H, W, gt_scale, Ho, Wo)
+        if g_occ is not None and not heuristic:
+            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
+        if out is None:
+            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
+        if disp_small is not None:
+            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
+        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
+            if t is not None:
+                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
+        if occ_out is not None:
+            if not heuristic:
+                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
+            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
+        if errormap is not None:
+            self._chk(errormap, torch.float32, 3, "errormap", (B, Ho, Wo))
+        return B, H, W, Cc, out
+
+    def _call_params(self, seed, vpp_kw, rsgm_kw, g_occ, heuristic, inputs_ready):
+        """Last step in front of the C entry point of a `vpp_rsgm` call: bind the stream, build the parameter blocks (vp, rp, op
+        -- None without the heuristic) and hand over the inputs-ready event, which the next hot-path call consumes."""
+        self._bind_stream()
+        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
+        rp = _lib.rsgm_params(**(rsgm_kw or {}))
+        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
+        if inputs_ready is not None:
+            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        return vp, rp, op
+
     def vpp_rsgm(self, left, right, hints=None, g_occ=None, out=None, l_vpp=None, r_vpp=None, seed=1, vpp_kw=None,
                  rsgm_kw=None, occ_out=None, inputs_ready=None, validhints=None, iscale=1, oscale=1, disp_small=None,
                  gt=None, validgt=None, metrics_out=None, errormap=None, sample=None):
@@ -185,7 +233,6 @@ class Engine:
         describes the stream), frame f with sampling seed `seed + f`, from src / validsrc (float32 [B,H,W]) or, without them,
         from gt / validgt.  `hints` and `validhints` must then be None; guided=True is --guided with the sampled mask
         (test.py:207-208); hints_out / validhints_out: float32 [B,H,W] tensors that receive the sampled maps."""
-        torch = self.torch
         if sample is not None:
             if hints is not None or validhints is not None:
                 raise ValueError("sample: the hints are sampled on the device; pass hints=None and validhints=None")
@@ -207,33 +254,16 @@ class Engine:
         if int(iscale) != 1 or int(oscale) != 1 or disp_small is not None:
             return self._vpp_rsgm_scaled(left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out,
                                          inputs_ready, validhints, int(iscale), int(oscale), disp_small)
-        B, H, W, Cc = self._chk_pair(left, right, hints, None if heuristic else g_occ)
-        if out is None:
-            out = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
-        self._chk(out, torch.float32, 3, "out", (B, H, W))
+        B, H, W, Cc, out = self._chk_call(left, right, ((hints, "hints"), (validhints, "validhints")), None, g_occ, heuristic, out,
+                                          l_vpp, r_vpp, occ_out)
+        vp, rp, op = self._call_params(seed, vpp_kw, rsgm_kw, g_occ, heuristic, inputs_ready)
         if validhints is not None:
-            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
-        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
-            if t is not None:
-                self._chk(t, torch.uint8, 4, n, left.shape)
-        if occ_out is not None:
-            if not heuristic:
-                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
-            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, H, W))
-        self._bind_stream()
-        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
-        rp = _lib.rsgm_params(**(rsgm_kw or {}))
-        if inputs_ready is not None:
-            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
-        if validhints is not None:
-            op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
             _lib.check(self.lib.vppx_occ_vpp_rsgm_guided_dev(self.ctx.handle, C.byref(op) if heuristic else None,
                                                              C.byref(vp), C.byref(rp), B, H, W, Cc, _ptr(left), _ptr(right),
                                                              _ptr(hints), None if heuristic else _ptr(g_occ),
                                                              _ptr(validhints), _ptr(occ_out), _ptr(l_vpp), _ptr(r_vpp),
                                                              _ptr(out)))
         elif heuristic:
-            op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {}))
             _lib.check(self.lib.vppx_occ_vpp_rsgm_dev(self.ctx.handle, C.byref(op), C.byref(vp), C.byref(rp), B, H, W, Cc,
                                                       _ptr(left), _ptr(right), _ptr(hints), _ptr(occ_out), _ptr(l_vpp),
                                                       _ptr(r_vpp), _ptr(out)))
@@ -245,37 +275,10 @@ class Engine:
 
     def _vpp_rsgm_scaled(self, left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
                          validhints, iscale, oscale, disp_small):
-        torch = self.torch
-        self._chk(left, torch.uint8, 4, "left")
-        B, H, W, Cc = left.shape
-        if Cc not in (1, 3):
-            raise ValueError("left: channels must be 1 or 3")
-        self._chk(right, torch.uint8, 4, "right", left.shape)
-        self._chk(hints, torch.float32, 3, "hints", (B, H, W))
+        B, H, W, Cc, out = self._chk_call(left, right, ((hints, "hints"), (validhints, "validhints")), (iscale, oscale), g_occ, heuristic,
+                                          out, l_vpp, r_vpp, occ_out, disp_small)
         sp = _lib.scale_params(iscale=iscale, oscale=oscale)
-        h, w, Ho, Wo = _lib.scaled_shape(H, W, iscale, oscale)
-        if g_occ is not None and not heuristic:
-            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
-        if validhints is not None:
-            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
-        if out is None:
-            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
-        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
-        if disp_small is not None:
-            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
-        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
-            if t is not None:
-                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
-        if occ_out is not None:
-            if not heuristic:
-                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
-            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
-        self._bind_stream()
-        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
-        rp = _lib.rsgm_params(**(rsgm_kw or {}))
-        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
-        if inputs_ready is not None:
-            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        vp, rp, op = self._call_params(seed, vpp_kw, rsgm_kw, g_occ, heuristic, inputs_ready)
         _lib.check(self.lib.vppx_occ_vpp_rsgm_scaled_dev(self.ctx.handle, C.byref(op) if heuristic else None, C.byref(vp), C.byref(rp),
                                                          C.byref(sp), B, H, W, Cc, _ptr(left), _ptr(right), _ptr(hints),
                                                          None if heuristic else _ptr(g_occ), _ptr(validhints), _ptr(occ_out),
@@ -397,46 +400,15 @@ class Engine:
 
     def _vpp_rsgm_eval(self, left, right, hints, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
                        validhints, iscale, oscale, disp_small, gt, validgt, metrics_out, errormap):
-        torch = self.torch
         if gt is None or validgt is None:
             raise ValueError("gt and validgt go together")
-        self._chk(left, torch.uint8, 4, "left")
-        B, H, W, Cc = left.shape
-        if Cc not in (1, 3):
-            raise ValueError("left: channels must be 1 or 3")
-        self._chk(right, torch.uint8, 4, "right", left.shape)
-        self._chk(hints, torch.float32, 3, "hints", (B, H, W))
+        planes = ((hints, "hints"), (gt, "gt"), (validgt, "validgt"), (validhints, "validhints"))
+        B, H, W, Cc, out = self._chk_call(left, right, planes, (iscale, oscale), g_occ, heuristic, out, l_vpp, r_vpp, occ_out, disp_small,
+                                          gt_scale=oscale, errormap=errormap)
         sp = _lib.scale_params(iscale=iscale, oscale=oscale)
-        h, w, Ho, Wo = _lib.scaled_shape(H, W, iscale, oscale)
-        self._chk(gt, torch.float32, 3, "gt", (B, H, W))
-        self._chk(validgt, torch.float32, 3, "validgt", (B, H, W))
-        _lib.check_gt_shape(H, W, oscale, Ho, Wo)
-        if g_occ is not None and not heuristic:
-            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
-        if validhints is not None:
-            self._chk(validhints, torch.float32, 3, "validhints", (B, H, W))
-        if out is None:
-            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
-        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
-        if disp_small is not None:
-            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
-        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
-            if t is not None:
-                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
-        if occ_out is not None:
-            if not heuristic:
-                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
-            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
-        if errormap is not None:
-            self._chk(errormap, torch.float32, 3, "errormap", (B, Ho, Wo))
         m = self._metrics_tensor(B, metrics_out)
-        self._bind_stream()
-        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
-        rp = _lib.rsgm_params(**(rsgm_kw or {}))
-        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
         ep = _lib.eval_params(gt_scale=oscale)
-        if inputs_ready is not None:
-            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        vp, rp, op = self._call_params(seed, vpp_kw, rsgm_kw, g_occ, heuristic, inputs_ready)
         _lib.check(self.lib.vppx_occ_vpp_rsgm_eval_dev(self.ctx.handle, C.byref(op) if heuristic else None, C.byref(vp), C.byref(rp),
                                                        C.byref(sp), C.byref(ep), B, H, W, Cc, _ptr(left), _ptr(right), _ptr(hints),
                                                        None if heuristic else _ptr(g_occ), _ptr(validhints), _ptr(gt), _ptr(validgt),
@@ -467,7 +439,6 @@ class Engine:
 
     def _vpp_rsgm_sampled(self, left, right, sample, g_occ, heuristic, out, l_vpp, r_vpp, seed, vpp_kw, rsgm_kw, occ_out, inputs_ready,
                           iscale, oscale, disp_small, gt, validgt, metrics_out, errormap):
-        torch = self.torch
         unknown = set(sample) - set(self.SAMPLE_KEYS)
         if unknown:
             raise TypeError(f"sample: unknown keys {sorted(unknown)} (keys: {list(self.SAMPLE_KEYS)})")
@@ -481,44 +452,15 @@ class Engine:
             raise ValueError("sample: without src / validsrc the hints are sampled from gt / validgt: pass them")
         if not evaluating and (metrics_out is not None or errormap is not None):
             raise ValueError("metrics_out / errormap are outputs of the evaluating call: pass gt and validgt")
-        self._chk(left, torch.uint8, 4, "left")
-        B, H, W, Cc = left.shape
-        if Cc not in (1, 3):
-            raise ValueError("left: channels must be 1 or 3")
-        self._chk(right, torch.uint8, 4, "right", left.shape)
+        planes = ((src, "src"), (validsrc, "validsrc"), (gt, "gt"), (validgt, "validgt"), (sample.get("hints_out"), "hints_out"),
+                  (sample.get("validhints_out"), "validhints_out"))
+        B, H, W, Cc, out = self._chk_call(left, right, planes, (iscale, oscale), g_occ, heuristic, out, l_vpp, r_vpp, occ_out, disp_small,
+                                          gt_scale=oscale if evaluating else None, errormap=errormap)
         sp = _lib.scale_params(iscale=iscale, oscale=oscale)
-        h, w, Ho, Wo = _lib.scaled_shape(H, W, iscale, oscale)
-        for t, n in ((src, "src"), (validsrc, "validsrc"), (gt, "gt"), (validgt, "validgt"), (sample.get("hints_out"), "hints_out"),
-                     (sample.get("validhints_out"), "validhints_out")):
-            if t is not None:
-                self._chk(t, torch.float32, 3, n, (B, H, W))
-        if evaluating:
-            _lib.check_gt_shape(H, W, oscale, Ho, Wo)
-        if g_occ is not None and not heuristic:
-            self._chk(g_occ, torch.uint8, 3, "g_occ", (B, h, w))
-        if out is None:
-            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
-        self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
-        if disp_small is not None:
-            self._chk(disp_small, torch.float32, 3, "disp_small", (B, h, w))
-        for t, n in ((l_vpp, "l_vpp"), (r_vpp, "r_vpp")):
-            if t is not None:
-                self._chk(t, torch.uint8, 4, n, (B, h, w, Cc))
-        if occ_out is not None:
-            if not heuristic:
-                raise ValueError("occ_out is the mask output of g_occ='occlusion_heuristic'")
-            self._chk(occ_out, torch.uint8, 3, "occ_out", (B, h, w))
-        if errormap is not None:
-            self._chk(errormap, torch.float32, 3, "errormap", (B, Ho, Wo))
         m = self._metrics_tensor(B, metrics_out) if evaluating else None
-        self._bind_stream()
-        vp = _lib.vpp_params(seed=int(seed) & 0xFFFFFFFF, **(vpp_kw or {}))
-        rp = _lib.rsgm_params(**(rsgm_kw or {}))
-        op = _lib.occ_params(**(g_occ if isinstance(g_occ, dict) else {})) if heuristic else None
         ep = _lib.eval_params(gt_scale=oscale) if evaluating else None
         smp = _lib.sample_params(probability=float(sample.get("probability", 0.05)), seed=int(sample.get("seed", 1)) & 0xFFFFFFFF)
-        if inputs_ready is not None:
-            _lib.check(self.lib.vppx_inputs_ready_event(self.ctx.handle, C.c_void_p(inputs_ready.cuda_event)))
+        vp, rp, op = self._call_params(seed, vpp_kw, rsgm_kw, g_occ, heuristic, inputs_ready)
         _lib.check(self.lib.vppx_occ_vpp_rsgm_sampled_dev(
             self.ctx.handle, C.byref(op) if heuristic else None, C.byref(vp), C.byref(rp), C.byref(sp), C.byref(ep) if evaluating else None,
             C.byref(smp), B, H, W, Cc, _ptr(left), _ptr(right), _ptr(src), _ptr(validsrc), 1 if sample.get("guided") else 0,
