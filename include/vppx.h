@@ -598,8 +598,14 @@ int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n
  * file of a batch: `blob` (device) holds n_files files back to back -- no alignment or padding is required of it --,
  * `offsets` (HOST, n_files + 1 entries) their byte ranges.  Non-interlaced gray 8/16 bit (C = 1) or RGB 8 bit (C = 3), all files H x W.  disp/valid (C = 1):
  * disp = sample * scale as float32 (scale 1/256 = readDispKITTI frame_utils.py:66-69, 1 = readDispMidd :71-74),
- * valid = disp > 0; out_u8 [n,H,W,C]: the 8-bit samples.  status (device int32 [n_files], may be NULL): 0 = ok,
- * 1 signature, 2 IHDR, 3 unsupported format, 4 size mismatch, 5 bad stream, 6 bad Huffman code, 7 bad filter,
+ * valid = disp > 0; out_u8 [n,H,W,C]: the 8-bit samples of an 8-bit file (a 16-bit file asked into out_u8 is refused with
+ * status 3).  status (device int32 [n_files], may be NULL): 0 = ok,
+ * 1 signature, 2 IHDR, 3 unsupported format (palette, alpha, gray below 8 bits, RGB of 16 bits, interlaced, 16 bits into out_u8),
+ * 4 size mismatch (IHDR against H, W, C; a stream that inflates to more or fewer bytes than H scanlines), 5 bad stream (zlib
+ * header: CM other than 8, FDICT, FCHECK; block type 3; stored LEN / NLEN; a distance beyond the start of the output), 6 bad
+ * Huffman code (code lengths over-subscribed or incomplete, a repeat with nothing to repeat or past the last length, no
+ * end-of-block code, HLIT above 286 or HDIST above 30, a symbol without meaning, a length without a distance code; an incomplete
+ * code is accepted only as a single code of one bit, as zlib does: a lone distance code of two bits is refused), 7 bad filter,
  * 8 truncated, 9 Adler-32 of the inflated stream does not match the one in the file (chunk CRCs are not verified); a file that
  * fails before its first scanline leaves its outputs untouched, one that fails later has written the scanlines decoded so far.
  * Scanlines up to 16 KB (1 + W * bytes per pixel). */

@@ -4,11 +4,12 @@ readDispMidd :71-74).  Files come from PIL's encoder (adaptive filters, dynamic 
 levels incl. stored blocks) and from a hand-rolled writer that forces every filter type, fixed-Huffman blocks, split
 IDAT chunks and ancillary chunks."""
 import io
-import struct
 import zlib
 
 import numpy as np
 import pytest
+
+from _deflate import _raw_png  # (the hand-rolled writer lives with the DEFLATE writer now)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,67 +35,6 @@ def _pil_png(arr, **kw):
 def _pil_decode(b):
     from PIL import Image
     return np.array(Image.open(io.BytesIO(b)))
-
-
-def _chunk(tag, data):
-    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
-
-
-def _filter_rows(img_bytes, bpp, types):
-    """img_bytes: [H, rowbytes] uint8 -> filtered scanlines (PNG spec 9.2) with the given filter type per row."""
-    H, nb = img_bytes.shape
-    out = bytearray()
-    prev = np.zeros(nb, np.int32)
-    for y in range(H):
-        cur = img_bytes[y].astype(np.int32)
-        a = np.concatenate([np.zeros(bpp, np.int32), cur[:-bpp]])
-        c = np.concatenate([np.zeros(bpp, np.int32), prev[:-bpp]])
-        t = types[y % len(types)]
-        if t == 0:
-            f = cur
-        elif t == 1:
-            f = cur - a
-        elif t == 2:
-            f = cur - prev
-        elif t == 3:
-            f = cur - ((a + prev) >> 1)
-        else:
-            p = a + prev - c
-            pa, pb, pc = np.abs(p - a), np.abs(p - prev), np.abs(p - c)
-            pr = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, prev, c))
-            f = cur - pr
-        out.append(t)
-        out += (f & 255).astype(np.uint8).tobytes()
-        prev = cur
-    return bytes(out)
-
-
-def _raw_png(arr, types=(0, 1, 2, 3, 4), level=6, strategy=zlib.Z_DEFAULT_STRATEGY, idat_split=(1 << 30,), extra=True):
-    """hand-rolled PNG writer: explicit filter types, zlib strategy and IDAT chunking"""
-    H, W = arr.shape[:2]
-    if arr.dtype == np.uint16:
-        depth, ctype, bpp = 16, 0, 2
-        rows = arr.astype(">u2").view(np.uint8).reshape(H, W * 2)
-    elif arr.ndim == 3:
-        depth, ctype, bpp = 8, 2, 3
-        rows = arr.reshape(H, W * 3)
-    else:
-        depth, ctype, bpp = 8, 0, 1
-        rows = arr.reshape(H, W)
-    co = zlib.compressobj(level, zlib.DEFLATED, 15, 9, strategy)
-    z = co.compress(_filter_rows(rows, bpp, types)) + co.flush()
-    out = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, depth, ctype, 0, 0, 0))
-    if extra:
-        out += _chunk(b"tEXt", b"Comment\x00ancillary chunk before the image data") + _chunk(b"pHYs", struct.pack(">IIB", 1, 1, 0))
-    pos, k = 0, 0
-    while pos < len(z):
-        n = idat_split[k % len(idat_split)]
-        out += _chunk(b"IDAT", z[pos:pos + n])
-        if k == 1:
-            out += _chunk(b"IDAT", b"")  # an empty IDAT chunk is legal
-        pos += n
-        k += 1
-    return out + _chunk(b"IEND", b"")
 
 
 def _kitti_like(rng, H, W, p=0.2):

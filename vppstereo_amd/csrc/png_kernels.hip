@@ -57,7 +57,7 @@ struct PngLds {
     u16 *tab_l;  // [1 << PNG_LBITS] sym << 4 | len, 0xFFFF = longer code
     u16 *tab_d;  // [1 << PNG_DBITS]
     u16 *cnt_l, *sym_l, *cnt_d, *sym_d; // canonical tables (huff_build)
-    u8 *lens;    // [320]
+    u8 *lens;    // [384]: the code-length code's own 19 lengths, from [32] on the decoded lengths (at most 286 + 30)
 };
 
 // The decoder's state is the same in every lane.  Telling the compiler so -- every value that comes out of LDS passes
@@ -377,6 +377,7 @@ __global__ void __launch_bounds__(64) png_decode_kernel(PngJobs j)
         if (comp != 0 || filt != 0 || inter != 0 || !((ctype == 0 && (depth == 8 || depth == 16)) || (ctype == 2 && depth == 8))) {
             st = PNG_E_UNSUPPORTED; break;
         }
+        if (j.out_u8 && depth != 8) { st = PNG_E_UNSUPPORTED; break; } // out_u8 holds 8-bit samples: no 16-bit file goes there
         const int ch = ctype == 2 ? 3 : 1;
         if ((int)w != j.W || (int)h != j.H || ch != j.C) { st = PNG_E_SIZE; break; }
         const int bpp = ch * depth / 8;
@@ -523,9 +524,11 @@ __global__ void __launch_bounds__(64) png_decode_kernel(PngJobs j)
                     int ed = 0, el = 0;
                     if (lane == 0) {
                         ed = png_huff_build(L.cnt_d, L.sym_d, cl + nlen, ndist);
-                        if (ed > 0 && ndist - L.cnt_d[0] == 1) ed = 0; // one distance code of any length is allowed (RFC 1951 3.2.7)
+                        // an incomplete code is allowed only as ONE code of ONE bit (RFC 1951 3.2.7: "one distance code ... using
+                        // one bit"); zlib refuses a lone code of any other length, and so do cv2 and PIL
+                        if (ed > 0 && ndist - L.cnt_d[0] == 1 && L.cnt_d[1] == 1) ed = 0;
                         el = png_huff_build(L.cnt_l, L.sym_l, cl, nlen);
-                        if (el > 0 && nlen - L.cnt_l[0] == 1) el = 0;
+                        if (el > 0 && nlen - L.cnt_l[0] == 1 && L.cnt_l[1] == 1) el = 0;
                     }
                     ed = __builtin_amdgcn_readfirstlane(ed);
                     el = __builtin_amdgcn_readfirstlane(el);
