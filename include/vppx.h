@@ -580,13 +580,22 @@ int vppx_u8_to_nchw_dev(vppx_ctx *ctx, int B, int H, int W, int C, int pad_multi
  *   cost[b,c,i,y,x] = x>=i ? fea_l[b,c,y,x] : 0,  cost[b,C+c,i,y,x] = x>=i ? fea_r[b,c,y,x-i] : 0,
  * multiplied, when hints != NULL, by (1-v) + v*10*exp(-(i-h)^2 / (2*(1/4)^2)) with h, v the hints
  * (float32 [B,1,H,W], H/4 == H4, W/4 == W4) and validhints sub-sampled 'nearest' like F.upsample and
- * h = hints*valid/4 (psmnet.py:172-197).  float32 throughout; exp() is the only inexact step. */
+ * h = hints*valid/4 (psmnet.py:172-197).  float32 throughout; exp() is the only inexact step: every other operation
+ * is the reference's, correctly rounded, so the argument of exp() is the reference's bit for bit, and a cell is within
+ * one unit in the last place of expf, carried through the three roundings behind it, of the same expression with an
+ * exact exp (tests/_handoff_ref.py, limit()).
+ * A pixel with v == 0 is untouched: its cells are the un-modulated volume's, bit for bit.  That equals the reference,
+ * which multiplies by (1-0) + (0*10)*exp(..) = 1, for every finite hint, and differs from it where an invalid pixel
+ * carries a hint that is not finite (inf for "unknown"): there hints*valid is NaN and the reference's cells turn NaN. */
 int vppx_psmnet_cost_volume_dev(vppx_ctx *ctx, const float *fea_l, const float *fea_r, const float *hints,
                                 const float *validhints, int B, int C, int H4, int W4, int H, int W, int maxdisp,
                                 float *cost);
 /* RAFT-Stereo hint modulation of the all-pairs correlation, in place (models/raft_stereo/corr.py:160-178):
  * corr float32 [B,H4,W2,1,W3] (= einsum(fmap2,fmap3)/sqrt(D), a library GEMM left to the caller);
- * corr[b,y,x,0,k] *= (1-v) + v*10*exp(-(k-(x*v-h))^2/2).  Rows without a hint are untouched. */
+ * corr[b,y,x,0,k] *= (1-v) + v*10*exp(-(k-(x*v-h))^2/2).  Rows with v == 0 are untouched (not read, not written): the
+ * reference's factor is exactly 1 there for a finite hint and NaN for a non-finite one, as above.
+ * hints / validhints are float32 [B,1,H,W] with H/4 == H4 and W/4 == W2: the library can check only those two
+ * quotients, the caller answers for B frames of H*W floats behind both pointers and B*H4*W2*W3 behind corr. */
 int vppx_raft_corr_modulate_dev(vppx_ctx *ctx, float *corr, const float *hints, const float *validhints, int B, int H4,
                                 int W2, int W3, int H, int W);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256

@@ -63,7 +63,8 @@ __global__ void __launch_bounds__(256) psm_volume_kernel(const float *__restrict
         if (hs && x0 + j < W4) {
             const size_t pi = ((size_t)b * H4 + y) * W4 + x0 + j;
             const float v = vs[pi];
-            if (v != 0.0f) { // v == 0: (1 - 0) + 0 * 10 * e = 1 exactly
+            if (v != 0.0f) { // v == 0 (or -0): untouched.  The reference's (1 - 0) + 0 * 10 * e is 1 exactly for a finite
+                             // hint only; under a non-finite one it is NaN, and this library keeps the cell (vppx.h)
                 mod[j] = modulation(v, hs[pi], (float)i, 0.125f); // 2 * (1/4)^2  (psmnet.py:187)
                 any = true;
             }
@@ -97,8 +98,9 @@ __global__ void __launch_bounds__(256) psm_volume_kernel(const float *__restrict
     }
 }
 
-// corr[b, y, x2, 0, k] *= modulation(b, y, x2; k); rows with valid == 0 are multiplied by exactly 1
-// in the reference, i.e. untouched: one 64-lane wave per (b, y, x2) row, skipping those.
+// corr[b, y, x2, 0, k] *= modulation(b, y, x2; k); rows with valid == 0 are untouched, which is the
+// reference's "times exactly 1" for every finite hint (vppx.h has the non-finite case): one 64-lane
+// wave per (b, y, x2) row, skipping those.
 __global__ void __launch_bounds__(256) raft_modulate_kernel(float *__restrict__ corr, const float *__restrict__ hs,
                                                             const float *__restrict__ vs, size_t nrows, int W3)
 {

@@ -510,10 +510,7 @@ class Engine:
         B, Cc, H4, W4 = fea_l.shape
         H = W = 0
         if hints is not None:
-            self._chk(hints, torch.float32, 4, "hints")
-            self._chk(validhints, torch.float32, 4, "validhints")
-            if hints.shape != validhints.shape or hints.shape[:2] != (B, 1):
-                raise ValueError("hints / validhints must be [B,1,H,W]")
+            self._chk_hint_pair(hints, validhints, B)
             H, W = hints.shape[2:]
         cost = torch.empty((B, 2 * Cc, int(maxdisp) // 4, H4, W4), dtype=torch.float32, device=self.device)
         self._bind_stream()
@@ -523,6 +520,14 @@ class Engine:
                                                         B, Cc, H4, W4, int(H), int(W), int(maxdisp), _ptr(cost)))
         return cost
 
+    def _chk_hint_pair(self, hints, validhints, B):
+        """Both [B,1,H,W] float32: the kernels index the two with one offset and read B frames of each."""
+        torch = self.torch
+        self._chk(hints, torch.float32, 4, "hints")
+        self._chk(validhints, torch.float32, 4, "validhints")
+        if hints.shape != validhints.shape or hints.shape[:2] != (B, 1):
+            raise ValueError("hints / validhints must be [B,1,H,W]")
+
     def raft_corr(self, fmap2, fmap3, hints=None, validhints=None):
         """CorrBlock1D.corr (models/raft_stereo/corr.py:151-180): all-pairs correlation along the row
         (a library GEMM through torch) / sqrt(D), then the hint modulation in place on the device."""
@@ -530,12 +535,14 @@ class Engine:
         self._chk(fmap2, torch.float32, 4, "fmap2")
         self._chk(fmap3, torch.float32, 4, "fmap3")
         B, Dc, H4, W2 = fmap2.shape
+        if fmap3.shape[:3] != fmap2.shape[:3]:
+            raise ValueError("fmap2 / fmap3 must be [B,D,H4,W2] / [B,D,H4,W3]")
         W3 = fmap3.shape[3]
+        if hints is not None:
+            self._chk_hint_pair(hints, validhints, B)
         corr = torch.einsum('aijk,aijh->ajkh', fmap2, fmap3).reshape(B, H4, W2, 1, W3).contiguous()
         corr = corr / torch.sqrt(torch.tensor(Dc).float())
         if hints is not None:
-            self._chk(hints, torch.float32, 4, "hints")
-            self._chk(validhints, torch.float32, 4, "validhints")
             self._bind_stream()
             _lib.check(self.lib.vppx_raft_corr_modulate_dev(self.ctx.handle, _ptr(corr), _ptr(hints), _ptr(validhints), B, H4,
                                                             W2, W3, int(hints.shape[2]), int(hints.shape[3])))
@@ -545,9 +552,10 @@ class Engine:
         """In-place hint modulation of an existing correlation volume [B,H4,W2,1,W3] (corr.py:160-178)."""
         torch = self.torch
         self._chk(corr, torch.float32, 5, "corr")
-        self._chk(hints, torch.float32, 4, "hints")
-        self._chk(validhints, torch.float32, 4, "validhints")
-        B, H4, W2, _, W3 = corr.shape
+        B, H4, W2, one, W3 = corr.shape
+        if one != 1:
+            raise ValueError("corr must be [B,H4,W2,1,W3]")
+        self._chk_hint_pair(hints, validhints, B)
         self._bind_stream()
         _lib.check(self.lib.vppx_raft_corr_modulate_dev(self.ctx.handle, _ptr(corr), _ptr(hints), _ptr(validhints), B, H4, W2,
                                                         W3, int(hints.shape[2]), int(hints.shape[3])))
@@ -561,6 +569,8 @@ class Engine:
             raise ValueError("png_u16 must be a contiguous 16-bit device tensor")
         disp = torch.empty(png_u16.shape, dtype=torch.float32, device=self.device)
         valid = torch.empty(png_u16.shape, dtype=torch.uint8, device=self.device)
+        if png_u16.numel() == 0:            # an empty tensor has no storage: its NULL pointer is not the library's n = 0
+            return disp, valid
         self._bind_stream()
         _lib.check(self.lib.vppx_kitti_disp_decode_dev(self.ctx.handle, _ptr(png_u16), png_u16.numel(), _ptr(disp), _ptr(valid)))
         return disp, valid
