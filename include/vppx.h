@@ -598,6 +598,32 @@ int vppx_psmnet_cost_volume_dev(vppx_ctx *ctx, const float *fea_l, const float *
  * quotients, the caller answers for B frames of H*W floats behind both pointers and B*H4*W2*W3 behind corr. */
 int vppx_raft_corr_modulate_dev(vppx_ctx *ctx, float *corr, const float *hints, const float *validhints, int B, int H4,
                                 int W2, int W3, int H, int W);
+/* The same two calls with the storage type of the large tensors as an argument. */
+typedef enum VppxDtype {
+    VPPX_DT_F32 = 0,  /* float32: exactly vppx_psmnet_cost_volume_dev / vppx_raft_corr_modulate_dev, which are this case */
+    VPPX_DT_BF16 = 1  /* bfloat16 (the upper 16 bits of a float32) for fea_l, fea_r and cost / for corr                   */
+                      /* (2 is kept for float16, which is not implemented)                                                 */
+} VppxDtype;
+/* dtype = VPPX_DT_BF16: fea_l, fea_r and cost (corr) hold bfloat16, 2-byte aligned; hints and validhints stay float32
+ * [B,1,H,W].  Only the storage type differs from the float32 call:
+ *   - a cell is widened to float32 (exact), multiplied in float32 by the same float32 factor as above, and rounded to
+ *     bfloat16 ONCE, to nearest even.  Nothing in between is held in bfloat16, neither the factor nor the sub-sampled
+ *     hints.  NaN stays NaN; a product beyond the largest bfloat16 becomes infinity, as round-to-nearest-even gives.
+ *   - a cell that is not modulated keeps the 16 bits of its feature (of corr): hints == NULL, a pixel with v == 0 (the
+ *     v == 0 rule above; RAFT rows with v == 0 are neither read nor written).  NaN payloads, -0 and subnormals come
+ *     through unchanged.  Cells with x < i are +0 (bits 0x0000).
+ * What differs from the float32 call on the widened features followed by a cast to bfloat16 (round-to-nearest-even):
+ * nothing in value, the result is the float32 result rounded once.  Two bit patterns differ: the cast quiets a
+ * signalling NaN of an un-modulated cell where this call copies it, and a cell with x < i is +0 here where the float32
+ * call leaves 0 * factor, which is -0 under a negative factor (v < 0) and NaN under a NaN factor.
+ * The argument checks, their order and their messages are those of the float32 entries; a dtype other than the two
+ * above is VPPX_E_INVALID_ARG with nothing launched and no output byte touched.  The volume is written with 16-byte
+ * stores when W4 % 8 == 0 and cost, fea_l and fea_r are 16-byte aligned, and cell by cell otherwise. */
+int vppx_psmnet_cost_volume_dt_dev(vppx_ctx *ctx, const void *fea_l, const void *fea_r, const float *hints,
+                                   const float *validhints, int B, int C, int H4, int W4, int H, int W, int maxdisp,
+                                   void *cost, int dtype);
+int vppx_raft_corr_modulate_dt_dev(vppx_ctx *ctx, void *corr, const float *hints, const float *validhints, int B, int H4,
+                                   int W2, int W3, int H, int W, int dtype);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

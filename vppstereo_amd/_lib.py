@@ -40,7 +40,9 @@ EXPORTS = [
     "vppx_colorize_dev", "vppx_colorize_host", "vppx_finite_max_dev",
     "vppx_sample_params_default", "vppx_sample_threshold", "vppx_sample_hints_dev", "vppx_sample_hints_host", "vppx_occ_vpp_rsgm_sampled_dev",
     "vppx_fstream_create_sampled", "vppx_fstream_push_sampled",
+    "vppx_psmnet_cost_volume_dt_dev", "vppx_raft_corr_modulate_dt_dev",
 ]
+DT_F32, DT_BF16 = 0, 1          # VppxDtype
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 FS_METRICS, FS_NO_DISP = 16, 32
 FS_SAMPLE = 64
@@ -182,6 +184,8 @@ def load():
         lib.vppx_u8_to_nchw_dev.argtypes = [vp, i, i, i, i, i, vp, vp, i]
         lib.vppx_psmnet_cost_volume_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
         lib.vppx_raft_corr_modulate_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i]
+        lib.vppx_psmnet_cost_volume_dt_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
+        lib.vppx_raft_corr_modulate_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i]
         lib.vppx_kitti_disp_decode_dev.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.vppx_pfm_decode_dev.argtypes = [vp, vp, i, i, i, i, vp]
         lib.vppx_png_decode_dev.argtypes = [vp, i, vp, C.POINTER(C.c_int64), i, i, i, f, vp, vp, vp, vp]

@@ -2434,9 +2434,16 @@ extern "C" int vppx_u8_to_nchw_dev(vppx_ctx *ctx, int B, int H, int W, int C, in
 // ---------------------------------------------------------------------------------------
 // hand-off rows: PSMNet volume, RAFT correlation modulation, payload decoders
 // ---------------------------------------------------------------------------------------
-extern "C" int vppx_psmnet_cost_volume_dev(vppx_ctx *ctx, const float *fea_l, const float *fea_r, const float *hints,
-                                           const float *validhints, int B, int C, int H4, int W4, int H, int W,
-                                           int maxdisp, float *cost)
+static bool handoff_dtype_ok(const char *who, int dtype)
+{
+    if (dtype == VPPX_DT_F32 || dtype == VPPX_DT_BF16) return true;
+    vppx_set_error("%s: dtype %d is neither VPPX_DT_F32 (0) nor VPPX_DT_BF16 (1)", who, dtype);
+    return false;
+}
+
+extern "C" int vppx_psmnet_cost_volume_dt_dev(vppx_ctx *ctx, const void *fea_l, const void *fea_r, const float *hints,
+                                              const float *validhints, int B, int C, int H4, int W4, int H, int W,
+                                              int maxdisp, void *cost, int dtype)
 {
     int rc;
     VPPX_ENTER(ctx);
@@ -2444,11 +2451,19 @@ extern "C" int vppx_psmnet_cost_volume_dev(vppx_ctx *ctx, const float *fea_l, co
         vppx_set_error("vppx_psmnet_cost_volume: bad arguments");
         return VPPX_E_INVALID_ARG;
     }
-    return handoff_psmnet_cost_volume(ctx, fea_l, fea_r, hints, validhints, B, C, H4, W4, H, W, maxdisp, cost);
+    if (!handoff_dtype_ok("vppx_psmnet_cost_volume", dtype)) return VPPX_E_INVALID_ARG;
+    return handoff_psmnet_cost_volume(ctx, fea_l, fea_r, hints, validhints, B, C, H4, W4, H, W, maxdisp, cost, dtype);
 }
 
-extern "C" int vppx_raft_corr_modulate_dev(vppx_ctx *ctx, float *corr, const float *hints, const float *validhints, int B,
-                                           int H4, int W2, int W3, int H, int W)
+extern "C" int vppx_psmnet_cost_volume_dev(vppx_ctx *ctx, const float *fea_l, const float *fea_r, const float *hints,
+                                           const float *validhints, int B, int C, int H4, int W4, int H, int W,
+                                           int maxdisp, float *cost)
+{
+    return vppx_psmnet_cost_volume_dt_dev(ctx, fea_l, fea_r, hints, validhints, B, C, H4, W4, H, W, maxdisp, cost, VPPX_DT_F32);
+}
+
+extern "C" int vppx_raft_corr_modulate_dt_dev(vppx_ctx *ctx, void *corr, const float *hints, const float *validhints, int B,
+                                              int H4, int W2, int W3, int H, int W, int dtype)
 {
     int rc;
     VPPX_ENTER(ctx);
@@ -2456,7 +2471,14 @@ extern "C" int vppx_raft_corr_modulate_dev(vppx_ctx *ctx, float *corr, const flo
         vppx_set_error("vppx_raft_corr_modulate: bad arguments");
         return VPPX_E_INVALID_ARG;
     }
-    return handoff_raft_corr_modulate(ctx, corr, hints, validhints, B, H4, W2, W3, H, W);
+    if (!handoff_dtype_ok("vppx_raft_corr_modulate", dtype)) return VPPX_E_INVALID_ARG;
+    return handoff_raft_corr_modulate(ctx, corr, hints, validhints, B, H4, W2, W3, H, W, dtype);
+}
+
+extern "C" int vppx_raft_corr_modulate_dev(vppx_ctx *ctx, float *corr, const float *hints, const float *validhints, int B,
+                                           int H4, int W2, int W3, int H, int W)
+{
+    return vppx_raft_corr_modulate_dt_dev(ctx, corr, hints, validhints, B, H4, W2, W3, H, W, VPPX_DT_F32);
 }
 
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)

@@ -520,10 +520,10 @@ int vpp_launch_rand_stream(vppx_ctx *ctx, u32 seed, u64 offset, int64_t n, int32
 u64 vpp_draws_upper_bound(const VppxVppParams &p, const VppGeom &g);
 
 // handoff_kernels.hip
-int handoff_psmnet_cost_volume(vppx_ctx *ctx, const float *fl, const float *fr, const float *hints, const float *valid, int B,
-                               int C, int H4, int W4, int H, int W, int maxdisp, float *cost);
-int handoff_raft_corr_modulate(vppx_ctx *ctx, float *corr, const float *hints, const float *valid, int B, int H4, int W2, int W3,
-                               int H, int W);
+int handoff_psmnet_cost_volume(vppx_ctx *ctx, const void *fl, const void *fr, const float *hints, const float *valid, int B, int C,
+                               int H4, int W4, int H, int W, int maxdisp, void *cost, int dtype);
+int handoff_raft_corr_modulate(vppx_ctx *ctx, void *corr, const float *hints, const float *valid, int B, int H4, int W2, int W3, int H,
+                               int W, int dtype);
 int handoff_kitti_decode(vppx_ctx *ctx, const uint16_t *png, size_t n, float *disp, u8 *valid);
 int handoff_pfm_decode(vppx_ctx *ctx, const u8 *raw, int H, int W, int channels, int little, float *out);
 // png_kernels.hip

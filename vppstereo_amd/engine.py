@@ -498,13 +498,24 @@ class Engine:
         return out
 
     # ---- hand-off rows ----
+    def _handoff_dtype(self, t):
+        """float32 or bfloat16 storage of a hand-off tensor -> (torch dtype, VppxDtype)."""
+        torch = self.torch
+        if getattr(t, "dtype", None) == torch.bfloat16:
+            return torch.bfloat16, _lib.DT_BF16
+        return torch.float32, _lib.DT_F32          # anything else fails _chk's float32 check with its usual message
+
     def psmnet_cost_volume(self, fea_l, fea_r, maxdisp, hints=None, validhints=None):
         """The tensor PSMNet.forward hands to dres0 (models/psmnet/psmnet.py:157-197): concat volume
         [B,2C,maxdisp//4,H4,W4] from the two feature maps [B,C,H4,W4], times the hint modulation when
-        hints / validhints ([B,1,H,W] float32) are given."""
+        hints / validhints ([B,1,H,W] float32) are given.  The feature maps are float32 or bfloat16 (both the same) and
+        the volume has their dtype; a bfloat16 cell is the float32 product rounded once (include/vppx.h)."""
         torch = self.torch
-        self._chk(fea_l, torch.float32, 4, "fea_l")
-        self._chk(fea_r, torch.float32, 4, "fea_r")
+        dtype, dt = self._handoff_dtype(fea_l)
+        if getattr(fea_r, "dtype", None) in (torch.float32, torch.bfloat16) and fea_r.dtype != dtype:
+            raise ValueError("feature maps must have the same dtype (float32 or bfloat16)")
+        self._chk(fea_l, dtype, 4, "fea_l")
+        self._chk(fea_r, dtype, 4, "fea_r")
         if fea_r.shape != fea_l.shape:
             raise ValueError("feature maps must have the same shape")
         B, Cc, H4, W4 = fea_l.shape
@@ -512,12 +523,12 @@ class Engine:
         if hints is not None:
             self._chk_hint_pair(hints, validhints, B)
             H, W = hints.shape[2:]
-        cost = torch.empty((B, 2 * Cc, int(maxdisp) // 4, H4, W4), dtype=torch.float32, device=self.device)
+        cost = torch.empty((B, 2 * Cc, int(maxdisp) // 4, H4, W4), dtype=dtype, device=self.device)
         self._bind_stream()
-        _lib.check(self.lib.vppx_psmnet_cost_volume_dev(self.ctx.handle, _ptr(fea_l), _ptr(fea_r),
-                                                        _ptr(hints) if hints is not None else None,
-                                                        _ptr(validhints) if hints is not None else None,
-                                                        B, Cc, H4, W4, int(H), int(W), int(maxdisp), _ptr(cost)))
+        _lib.check(self.lib.vppx_psmnet_cost_volume_dt_dev(self.ctx.handle, _ptr(fea_l), _ptr(fea_r),
+                                                           _ptr(hints) if hints is not None else None,
+                                                           _ptr(validhints) if hints is not None else None,
+                                                           B, Cc, H4, W4, int(H), int(W), int(maxdisp), _ptr(cost), dt))
         return cost
 
     def _chk_hint_pair(self, hints, validhints, B):
@@ -530,10 +541,14 @@ class Engine:
 
     def raft_corr(self, fmap2, fmap3, hints=None, validhints=None):
         """CorrBlock1D.corr (models/raft_stereo/corr.py:151-180): all-pairs correlation along the row
-        (a library GEMM through torch) / sqrt(D), then the hint modulation in place on the device."""
+        (a library GEMM through torch) / sqrt(D), then the hint modulation in place on the device.  bfloat16 maps (both
+        the same dtype) give a bfloat16 volume: torch does the GEMM and the division in bfloat16."""
         torch = self.torch
-        self._chk(fmap2, torch.float32, 4, "fmap2")
-        self._chk(fmap3, torch.float32, 4, "fmap3")
+        dtype, dt = self._handoff_dtype(fmap2)
+        if getattr(fmap3, "dtype", None) in (torch.float32, torch.bfloat16) and fmap3.dtype != dtype:
+            raise ValueError("feature maps must have the same dtype (float32 or bfloat16)")
+        self._chk(fmap2, dtype, 4, "fmap2")
+        self._chk(fmap3, dtype, 4, "fmap3")
         B, Dc, H4, W2 = fmap2.shape
         if fmap3.shape[:3] != fmap2.shape[:3]:
             raise ValueError("fmap2 / fmap3 must be [B,D,H4,W2] / [B,D,H4,W3]")
@@ -542,23 +557,26 @@ class Engine:
             self._chk_hint_pair(hints, validhints, B)
         corr = torch.einsum('aijk,aijh->ajkh', fmap2, fmap3).reshape(B, H4, W2, 1, W3).contiguous()
         corr = corr / torch.sqrt(torch.tensor(Dc).float())
+        if corr.dtype != dtype:
+            raise RuntimeError(f"raft_corr: torch returned {corr.dtype} for {dtype} maps")
         if hints is not None:
             self._bind_stream()
-            _lib.check(self.lib.vppx_raft_corr_modulate_dev(self.ctx.handle, _ptr(corr), _ptr(hints), _ptr(validhints), B, H4,
-                                                            W2, W3, int(hints.shape[2]), int(hints.shape[3])))
+            _lib.check(self.lib.vppx_raft_corr_modulate_dt_dev(self.ctx.handle, _ptr(corr), _ptr(hints), _ptr(validhints), B, H4,
+                                                               W2, W3, int(hints.shape[2]), int(hints.shape[3]), dt))
         return corr
 
     def raft_corr_modulate_(self, corr, hints, validhints):
-        """In-place hint modulation of an existing correlation volume [B,H4,W2,1,W3] (corr.py:160-178)."""
-        torch = self.torch
-        self._chk(corr, torch.float32, 5, "corr")
+        """In-place hint modulation of an existing correlation volume [B,H4,W2,1,W3], float32 or bfloat16
+        (corr.py:160-178)."""
+        dtype, dt = self._handoff_dtype(corr)
+        self._chk(corr, dtype, 5, "corr")
         B, H4, W2, one, W3 = corr.shape
         if one != 1:
             raise ValueError("corr must be [B,H4,W2,1,W3]")
         self._chk_hint_pair(hints, validhints, B)
         self._bind_stream()
-        _lib.check(self.lib.vppx_raft_corr_modulate_dev(self.ctx.handle, _ptr(corr), _ptr(hints), _ptr(validhints), B, H4, W2,
-                                                        W3, int(hints.shape[2]), int(hints.shape[3])))
+        _lib.check(self.lib.vppx_raft_corr_modulate_dt_dev(self.ctx.handle, _ptr(corr), _ptr(hints), _ptr(validhints), B, H4, W2,
+                                                           W3, int(hints.shape[2]), int(hints.shape[3]), dt))
         return corr
 
     def kitti_disp_decode(self, png_u16):
