@@ -23,6 +23,8 @@
  *   color_error_image_kitti()           utils.py:17-36              vppx_error_colors_host / _dev
  *   guided_visualize()                  utils.py:39-79              vppx_guided_visualize_host / _dev
  *   test.py:318, :325-326, :343 (max_val, applyColorMap)            vppx_finite_max_dev, vppx_colorize_host / _dev
+ *   CorrBlock1D.__init__ pyramid        raft_stereo/corr.py:116-124 vppx_raft_corr_pyramid_dt_dev
+ *   CorrBlock1D.__call__                raft_stereo/corr.py:126-145 vppx_raft_corr_lookup_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -624,6 +626,55 @@ int vppx_psmnet_cost_volume_dt_dev(vppx_ctx *ctx, const void *fea_l, const void 
                                    void *cost, int dtype);
 int vppx_raft_corr_modulate_dt_dev(vppx_ctx *ctx, void *corr, const float *hints, const float *validhints, int B, int H4,
                                    int W2, int W3, int H, int W, int dtype);
+/* ---- CorrBlock1D: the pyramid and the lookup (models/raft_stereo/corr.py:116-145) ------------------------------
+ * The volume is N = B*H4*W2 rows of W3 cells, float32 or bfloat16 (dtype as above).  Level 0 is the volume itself, level i
+ * has Wi = W3 >> i cells per row.  Every step below is one correctly rounded float32 operation, in this order; the
+ * float32 results are those of the reference's avg_pool2d / grid_sample composition bit for bit.
+ *
+ * Pyramid:  level_i[k] = ((+0 + level_{i-1}[2k]) + level_{i-1}[2k+1]) / 2; an odd last column is dropped.  The sum starts
+ * at +0, so two -0 cells pool to +0.  Each level is pooled from the level below AS STORED: with bfloat16 storage the
+ * two bfloat16 cells are widened, summed and halved in float32 and the result is rounded to bfloat16 once, to nearest even
+ * (NaN as above), which is what torch's bfloat16 avg_pool2d gives.  One sign is IEEE's and not torch's CPU kernel's: a
+ * negative sum whose half rounds to zero gives -0 (torch on a CPU returns +0 there).
+ * With hints != NULL the call first modulates level 0 in place, exactly as the modulation call above does (the same
+ * factor, rows with v == 0 untouched), and pools the modulated values: one pass over the volume instead of two.  Rows
+ * with v == 0 are not written, and are pooled like every other row.  With hints == NULL corr is not written.
+ * pyr receives levels 1 .. levels-1 back to back, each dense [N][W3 >> i], in the volume's dtype; the cells-query below gives
+ * the total number of cells and, in offsets[i] for i = 1 .. levels-1 (offsets[0] = 0, unused; offsets may be NULL), the first cell of
+ * level i.  It returns a negative VPPX_E_* code for N, W3 <= 0, levels < 1 (INVALID_ARG) or levels > 4 (UNSUPPORTED).
+ * pyr may be NULL when levels == 1 (nothing is pooled; with hints the call is then the modulation alone).
+ *
+ * Lookup:  for pixel n = (b, y, x) with c = coords_x[b * coords_frame_stride + y * W2 + x], level i of width W = Wi and
+ * tap t = 0 .. 2*radius:
+ *     x  = (float)(t - radius) + c / 2^i
+ *     xg = (2 * x) / (W - 1) - 1
+ *     ix = ((xg + 1) / 2) * (W - 1)          the round trip changes the position in its last bits; it is not shortcut
+ *     fl = floor(ix);  wr = ix - fl;  wl = (fl + 1) - ix
+ *     a  = fl     in [0, W-1] ? level_i[n][fl]     : +0
+ *     b  = fl + 1 in [0, W-1] ? level_i[n][fl + 1] : +0          (compared in float: 1e30 is outside, not an index)
+ *     out[b][i * (2*radius+1) + t][y][x] = fma(b, wr, +0 + a * wl)
+ * out is float32 [B, levels*(2*radius+1), H4, W2], the reference's .permute(0,3,1,2).contiguous().float() layout, every
+ * cell written.  A cell with neither tap in range is +0.  A NaN cell of the volume under a weight of zero gives NaN,
+ * as the formula says.  Where ix is not finite (a NaN or infinite coordinate) the cell is +0: the reference converts
+ * such a position to an integer index, which is undefined, so there is nothing to be equal to.
+ * coords_x points at channel 0 of the reference's coords1 [B,2,H4,W2] (coords_frame_stride = 2*H4*W2) or at a bare
+ * [B,H4,W2] (H4*W2); channel 1 is never read.
+ * bfloat16 storage: the two taps are widened to float32 and everything else is as above; out stays float32 and is
+ * not rounded.  This has no reference counterpart: torch's bfloat16 grid_sample does its arithmetic in bfloat16 and
+ * does not take a float32 grid.
+ * Both device calls are stream-ordered and do not synchronise.  Refused before anything is launched, with no output
+ * byte touched: a NULL corr / coords_x / out, pyr == NULL with levels > 1, hints without validhints, B, H4, W2 or
+ * W3 <= 0, levels < 1, radius < 0, coords_frame_stride < H4*W2, a dtype other than the two (VPPX_E_INVALID_ARG);
+ * W3 >> (levels-1) < 2, where the reference divides by W - 1 = 0 (VPPX_E_INVALID_ARG); levels > VPPX_CORR_MAX_LEVELS or
+ * radius > VPPX_CORR_MAX_RADIUS (VPPX_E_UNSUPPORTED); with hints, H/4 != H4 or W/4 != W2 with the modulation call's message. */
+#define VPPX_CORR_MAX_LEVELS 4
+#define VPPX_CORR_MAX_RADIUS 8
+int64_t vppx_raft_corr_pyramid_cells(int64_t N, int W3, int levels, int64_t *offsets);
+int vppx_raft_corr_pyramid_dt_dev(vppx_ctx *ctx, void *corr, const float *hints, const float *validhints, int B, int H4, int W2,
+                                  int W3, int H, int W, int levels, void *pyr, int dtype);
+int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
+                                 int64_t coords_frame_stride, int B, int H4, int W2, int W3, int levels, int radius,
+                                 float *out, int dtype);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

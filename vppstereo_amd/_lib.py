@@ -41,7 +41,9 @@ EXPORTS = [
     "vppx_sample_params_default", "vppx_sample_threshold", "vppx_sample_hints_dev", "vppx_sample_hints_host", "vppx_occ_vpp_rsgm_sampled_dev",
     "vppx_fstream_create_sampled", "vppx_fstream_push_sampled",
     "vppx_psmnet_cost_volume_dt_dev", "vppx_raft_corr_modulate_dt_dev",
+    "vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev",
 ]
+CORR_MAX_LEVELS, CORR_MAX_RADIUS = 4, 8
 DT_F32, DT_BF16 = 0, 1          # VppxDtype
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 FS_METRICS, FS_NO_DISP = 16, 32
@@ -186,6 +188,10 @@ def load():
         lib.vppx_raft_corr_modulate_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i]
         lib.vppx_psmnet_cost_volume_dt_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
         lib.vppx_raft_corr_modulate_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i]
+        lib.vppx_raft_corr_pyramid_cells.argtypes = [C.c_int64, i, i, C.POINTER(C.c_int64)]
+        lib.vppx_raft_corr_pyramid_cells.restype = C.c_int64
+        lib.vppx_raft_corr_pyramid_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
+        lib.vppx_raft_corr_lookup_dt_dev.argtypes = [vp, vp, vp, vp, C.c_int64, i, i, i, i, i, i, vp, i]
         lib.vppx_kitti_disp_decode_dev.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.vppx_pfm_decode_dev.argtypes = [vp, vp, i, i, i, i, vp]
         lib.vppx_png_decode_dev.argtypes = [vp, i, vp, C.POINTER(C.c_int64), i, i, i, f, vp, vp, vp, vp]

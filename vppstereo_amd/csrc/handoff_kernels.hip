@@ -33,13 +33,7 @@ __global__ void __launch_bounds__(256) subsample_hints_kernel(const float *__res
     vs[di] = v;
 }
 
-// (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)
-__device__ __forceinline__ float modulation(float v, float h, float d, float two_w2)
-{
-    const float diff = __fsub_rn(d, h);
-    const float e = expf(__fdiv_rn(-__fmul_rn(diff, diff), two_w2));
-    return __fadd_rn(__fsub_rn(1.0f, v), __fmul_rn(__fmul_rn(v, 10.0f), e));
-}
+// modulation(): (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2), shared with corr_kernels.hip (vppx_internal.h)
 
 // cost[b, c, i, y, x]     = x >= i ? fea_l[b, c, y, x]     : 0
 // cost[b, C + c, i, y, x] = x >= i ? fea_r[b, c, y, x - i] : 0      (psmnet.py:157-166), times the
@@ -119,17 +113,7 @@ __global__ void __launch_bounds__(256) raft_modulate_kernel(float *__restrict__ 
 // even; hs / vs and the factor are never held in bf16.  A cell that is not modulated (no hints, v == 0) keeps its 16
 // bits: it does not pass through a float, so NaN payloads, -0 and subnormals survive.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float bf16_widen(u32 bits) { return __uint_as_float(bits << 16); }
-
-// round-to-nearest-even; NaN stays NaN (quieted, sign and upper payload kept), beyond the largest bf16 -> infinity
-__device__ __forceinline__ u32 bf16_rne(float f)
-{
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
-__device__ __forceinline__ u32 bf16_scale(u32 bits, float mod) { return bf16_rne(__fmul_rn(bf16_widen(bits), mod)); }
+// bf16_widen / bf16_rne / bf16_scale: vppx_internal.h
 
 // the factors of `N` consecutive x of one (b, i, y): mod[j] is valid where bit j of the result is set
 template <int N>
@@ -293,8 +277,8 @@ __global__ void __launch_bounds__(256) pfm_decode_kernel(const u32 *__restrict__
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-static int launch_subsample(vppx_ctx *ctx, const float *hints, const float *valid, int B, int H, int W, int H4, int W4,
-                            float **hs, float **vs, int raft)
+int handoff_subsample_hints(vppx_ctx *ctx, const float *hints, const float *valid, int B, int H, int W, int H4, int W4, float **hs,
+                            float **vs, int raft)
 {
     int rc;
     if (H / 4 != H4 || W / 4 != W4) {
@@ -316,7 +300,7 @@ int handoff_psmnet_cost_volume(vppx_ctx *ctx, const void *fl, const void *fr, co
     int rc;
     const int D4 = maxdisp / 4;
     float *hs = nullptr, *vs = nullptr;
-    if (hints && (rc = launch_subsample(ctx, hints, valid, B, H, W, H4, W4, &hs, &vs, 0))) return rc;
+    if (hints && (rc = handoff_subsample_hints(ctx, hints, valid, B, H, W, H4, W4, &hs, &vs, 0))) return rc;
     if (D4 > 65535 || B > 65535) {
         vppx_set_error("psmnet cost volume: maxdisp/4 and B must be <= 65535");
         return VPPX_E_UNSUPPORTED;
@@ -345,7 +329,7 @@ int handoff_raft_corr_modulate(vppx_ctx *ctx, void *corr, const float *hints, co
 {
     int rc;
     float *hs, *vs;
-    if ((rc = launch_subsample(ctx, hints, valid, B, H, W, H4, W2, &hs, &vs, 1))) return rc;
+    if ((rc = handoff_subsample_hints(ctx, hints, valid, B, H, W, H4, W2, &hs, &vs, 1))) return rc;
     const size_t nrows = (size_t)B * H4 * W2;
     const dim3 grid((unsigned)((nrows + 3) / 4));
     if (dtype == VPPX_DT_BF16)

@@ -2481,6 +2481,71 @@ extern "C" int vppx_raft_corr_modulate_dev(vppx_ctx *ctx, float *corr, const flo
     return vppx_raft_corr_modulate_dt_dev(ctx, corr, hints, validhints, B, H4, W2, W3, H, W, VPPX_DT_F32);
 }
 
+// CorrBlock1D's pyramid and lookup (corr_kernels.hip).  Every refusal comes before anything is launched.
+extern "C" int64_t vppx_raft_corr_pyramid_cells(int64_t N, int W3, int levels, int64_t *offsets)
+{
+    if (N <= 0 || W3 <= 0 || levels < 1) {
+        vppx_set_error("vppx_raft_corr_pyramid_cells: bad arguments");
+        return VPPX_E_INVALID_ARG;
+    }
+    if (levels > VPPX_CORR_MAX_LEVELS) {
+        vppx_set_error("vppx_raft_corr_pyramid_cells: %d levels, at most %d are built", levels, VPPX_CORR_MAX_LEVELS);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return corr_pyramid_offsets(N, W3, levels, offsets);
+}
+
+static int corr_shape_ok(const char *who, int B, int H4, int W2, int W3, int levels, int radius, int dtype)
+{
+    if (B <= 0 || H4 <= 0 || W2 <= 0 || W3 <= 0 || levels < 1 || radius < 0) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok(who, dtype)) return VPPX_E_INVALID_ARG;
+    if (levels > VPPX_CORR_MAX_LEVELS || radius > VPPX_CORR_MAX_RADIUS) {
+        vppx_set_error("%s: %d levels of radius %d, at most %d levels and radius %d are built", who, levels, radius, VPPX_CORR_MAX_LEVELS,
+                       VPPX_CORR_MAX_RADIUS);
+        return VPPX_E_UNSUPPORTED;
+    }
+    if ((W3 >> (levels - 1)) < 2) {
+        vppx_set_error("%s: level %d of a %d-wide row has %d cells; the lookup divides by that width - 1, so 2 is the least", who,
+                       levels - 1, W3, W3 >> (levels - 1));
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vppx_raft_corr_pyramid_dt_dev(vppx_ctx *ctx, void *corr, const float *hints, const float *validhints, int B, int H4,
+                                             int W2, int W3, int H, int W, int levels, void *pyr, int dtype)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!corr || (hints && !validhints) || (!pyr && levels > 1)) {
+        vppx_set_error("vppx_raft_corr_pyramid: bad arguments");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = corr_shape_ok("vppx_raft_corr_pyramid", B, H4, W2, W3, levels, 0, dtype))) return rc;
+    return corr_pyramid(ctx, corr, hints, validhints, B, H4, W2, W3, H, W, levels, pyr, dtype);
+}
+
+extern "C" int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
+                                            int64_t coords_frame_stride, int B, int H4, int W2, int W3, int levels, int radius,
+                                            float *out, int dtype)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!corr || !coords_x || !out || (!pyr && levels > 1)) {
+        vppx_set_error("vppx_raft_corr_lookup: bad arguments");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = corr_shape_ok("vppx_raft_corr_lookup", B, H4, W2, W3, levels, radius, dtype))) return rc;
+    if (coords_frame_stride < (int64_t)H4 * W2) {
+        vppx_set_error("vppx_raft_corr_lookup: coords_frame_stride %lld is less than one %dx%d plane", (long long)coords_frame_stride, H4, W2);
+        return VPPX_E_INVALID_ARG;
+    }
+    return corr_lookup(ctx, corr, pyr, coords_x, coords_frame_stride, B, H4, W2, W3, levels, radius, out, dtype);
+}
+
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)
 {
     int rc;

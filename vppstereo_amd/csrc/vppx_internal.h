@@ -526,6 +526,46 @@ int handoff_raft_corr_modulate(vppx_ctx *ctx, void *corr, const float *hints, co
                                int W, int dtype);
 int handoff_kitti_decode(vppx_ctx *ctx, const uint16_t *png, size_t n, float *disp, u8 *valid);
 int handoff_pfm_decode(vppx_ctx *ctx, const u8 *raw, int H, int W, int channels, int little, float *out);
+// hints / valid -> feature resolution in WS_HANDOFF_H / _V (raft: h = x * v - hints * v / 4); refuses H / 4 != H4 or W / 4 != W4
+int handoff_subsample_hints(vppx_ctx *ctx, const float *hints, const float *valid, int B, int H, int W, int H4, int W4, float **hs,
+                            float **vs, int raft);
+// corr_kernels.hip: CorrBlock1D's pyramid and lookup (models/raft_stereo/corr.py:116-145)
+int corr_pyramid(vppx_ctx *ctx, void *corr, const float *hints, const float *valid, int B, int H4, int W2, int W3, int H, int W,
+                 int levels, void *pyr, int dtype);
+int corr_lookup(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x, int64_t coords_frame_stride, int B, int H4,
+                int W2, int W3, int levels, int radius, float *out, int dtype);
+// levels 1 .. levels-1 back to back, each dense [N][W3 >> i]: off[i] = first cell of level i (off[0] = 0, unused) -> cells in all
+static inline int64_t corr_pyramid_offsets(int64_t N, int W3, int levels, int64_t *off)
+{
+    int64_t cells = 0;
+    if (off) off[0] = 0;
+    for (int i = 1; i < levels; i++) {
+        if (off) off[i] = cells;
+        cells += N * (int64_t)(W3 >> i);
+    }
+    return cells;
+}
+
+// device functions the hand-off and the correlation kernels share
+// (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)
+__device__ __forceinline__ float modulation(float v, float h, float d, float two_w2)
+{
+    const float diff = __fsub_rn(d, h);
+    const float e = expf(__fdiv_rn(-__fmul_rn(diff, diff), two_w2));
+    return __fadd_rn(__fsub_rn(1.0f, v), __fmul_rn(__fmul_rn(v, 10.0f), e));
+}
+
+__device__ __forceinline__ float bf16_widen(u32 bits) { return __uint_as_float(bits << 16); }
+
+// round-to-nearest-even; NaN stays NaN (quieted, sign and upper payload kept), beyond the largest bf16 -> infinity
+__device__ __forceinline__ u32 bf16_rne(float f)
+{
+    const u32 u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+__device__ __forceinline__ u32 bf16_scale(u32 bits, float mod) { return bf16_rne(__fmul_rn(bf16_widen(bits), mod)); }
 // png_kernels.hip
 int handoff_png_decode(vppx_ctx *ctx, int n_files, const u8 *blob_dev, const long long *offs_dev, int H, int W, int C, u8 *zcat,
                        const long long *zoffs_dev, float scale, float *disp, u8 *valid, u8 *out_u8, int *status_dev);

@@ -579,6 +579,78 @@ class Engine:
                                                            W3, int(hints.shape[2]), int(hints.shape[3]), dt))
         return corr
 
+    def _corr_offsets(self, N, W3, levels):
+        """(cells of levels 1.., [first cell of level i]) from the library; its refusals raise."""
+        off = (C.c_int64 * _lib.CORR_MAX_LEVELS)()
+        cells = self.lib.vppx_raft_corr_pyramid_cells(N, W3, levels, off)
+        if cells < 0:
+            _lib.check(int(cells))
+        return int(cells), list(off)[:levels]
+
+    def raft_corr_pyramid(self, corr, hints=None, validhints=None, num_levels=4):
+        """CorrBlock1D.__init__ after the GEMM (models/raft_stereo/corr.py:117-124): the hint modulation of `corr`
+        [B,H4,W2,1,W3] (float32 or bfloat16) in place, when hints are given, and the avg_pool2d pyramid, in one pass over
+        the volume.  -> list of `num_levels` tensors [N,1,1,W3 >> i], N = B*H4*W2: entry 0 is `corr` itself, the others
+        are views into one buffer (include/vppx.h has the arithmetic)."""
+        torch = self.torch
+        dtype, dt = self._handoff_dtype(corr)
+        self._chk(corr, dtype, 5, "corr")
+        B, H4, W2, one, W3 = corr.shape
+        if one != 1:
+            raise ValueError("corr must be [B,H4,W2,1,W3]")
+        H = W = 0
+        if hints is not None:
+            self._chk_hint_pair(hints, validhints, B)
+            H, W = hints.shape[2:]
+        levels, N = int(num_levels), B * H4 * W2
+        cells, off = self._corr_offsets(N, W3, levels)
+        pyr = torch.empty((cells,), dtype=dtype, device=self.device) if levels > 1 else None
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_corr_pyramid_dt_dev(self.ctx.handle, _ptr(corr), _ptr(hints) if hints is not None else None,
+                                                          _ptr(validhints) if hints is not None else None, B, H4, W2, W3,
+                                                          int(H), int(W), levels, _ptr(pyr) if pyr is not None else None, dt))
+        out = [corr.view(N, 1, 1, W3)]
+        for i in range(1, levels):
+            Wi = W3 >> i
+            out.append(pyr[off[i]:off[i] + N * Wi].view(N, 1, 1, Wi))
+        return out
+
+    def raft_corr_lookup(self, pyramid, coords, radius=4, out=None):
+        """CorrBlock1D.__call__ (corr.py:126-145) in one launch: `pyramid` is what raft_corr_pyramid returned, `coords`
+        float32 [B,2,H4,W2] (channel 0 is read, as the reference does) or [B,H4,W2].  -> float32
+        [B, levels*(2*radius+1), H4, W2]."""
+        torch = self.torch
+        levels = len(pyramid)
+        if levels < 1:
+            raise ValueError("pyramid: no levels")
+        dtype, dt = self._handoff_dtype(pyramid[0])
+        self._chk(pyramid[0], dtype, 4, "pyramid[0]")
+        N, W3 = pyramid[0].shape[0], pyramid[0].shape[3]
+        if coords.dim() == 4:
+            self._chk(coords, torch.float32, 4, "coords")
+            B, ch, H4, W2 = coords.shape
+            if ch != 2:
+                raise ValueError("coords must be [B,2,H4,W2] or [B,H4,W2]")
+        else:
+            self._chk(coords, torch.float32, 3, "coords")
+            (B, H4, W2), ch = coords.shape, 1
+        if B * H4 * W2 != N:
+            raise ValueError(f"coords are {tuple(coords.shape)}: the pyramid has {N} rows, not {B * H4 * W2}")
+        _, off = self._corr_offsets(N, W3, levels)
+        for i in range(1, levels):      # the library takes one pointer for levels 1..: they must lie where it expects them
+            self._chk(pyramid[i], dtype, 4, f"pyramid[{i}]", (N, 1, 1, W3 >> i))
+            if pyramid[i].data_ptr() != pyramid[1].data_ptr() + off[i] * pyramid[i].element_size():
+                raise ValueError("pyramid: levels 1.. must be the views raft_corr_pyramid returned")
+        shape = (B, levels * (2 * int(radius) + 1), H4, W2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            self._chk(out, torch.float32, 4, "out", shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_corr_lookup_dt_dev(self.ctx.handle, _ptr(pyramid[0]), _ptr(pyramid[1]) if levels > 1 else None,
+                                                         _ptr(coords), ch * H4 * W2, B, H4, W2, W3, levels, int(radius), _ptr(out), dt))
+        return out
+
     def kitti_disp_decode(self, png_u16):
         """uint16 PNG samples (device tensor, int16/uint16 storage) -> (disp float32, valid uint8), same shape
         (frame_utils.readDispKITTI :66-69)."""
