@@ -337,6 +337,15 @@ void vppx_scale_params_default(VppxScaleParams *p);
 /* (h, w): the shape the matcher runs at; (Ho, Wo): the shape of the returned map.  VPPX_E_INVALID_ARG for iscale < 1,
  * oscale < 1 or an empty scaled shape. */
 int vppx_scaled_shape(int H, int W, const VppxScaleParams *sp, int *h, int *w, int *Ho, int *Wo);
+/* Times this context built the resize / restore index tables of a scaled call and uploaded them: once for the first scaled
+ * call, once more whenever (H, W, iscale, oscale) differs from the previous scaled call's; a call of the same shape reuses
+ * them.  A host counter, for tests and diagnostics: reading it launches and waits for nothing. */
+long vppx_scale_table_builds(vppx_ctx *ctx);
+/* Which of the two sets of library-owned maps the last resizing call (scale_set) and the last sampling call (sample_set) of this
+ * context wrote: 0 or 1, -1 before the first such call.  Without vppx_set_pipeline every call writes set 0; with it consecutive
+ * calls alternate, since the next call's front stage may write while this call still reads.  Either pointer may be NULL.  Host
+ * stores only, for tests and diagnostics. */
+int vppx_last_front_sets(vppx_ctx *ctx, int *scale_set, int *sample_set);
 /* As vppx_occ_vpp_rsgm_guided_dev on full-size inputs left / right (uint8 [B,H,W,C]), g and validhints (float32 [B,H,W]):
  * validhints == NULL runs unguided; op != NULL computes the mask on the way, op == NULL takes g_occ (may be NULL) as the
  * caller's mask at (h, w).  conf_out [B,h,w], l_vpp / r_vpp [B,h,w,C] are at the scaled shape (may be NULL), disp_out is

@@ -183,6 +183,27 @@ def compare(got, ref, exp_ulps):
     return worst, int(beyond.sum()), int(changed.sum())
 
 
+def corr_whole(f2, f3, hints, valid, exp_ulps):
+    """CorrBlock1D.corr through a float32 GEMM: -> (the float64 value of every cell, how far a float32 implementation may be
+    from it).  A float32 dot product of Dc terms is within Dc * 2^-24 * sum |a_i * b_i| of the exact one in any order of
+    summation; / sqrt(Dc) adds its rounding, the float32 sqrt's and the rounding of the cell handed to the modulation
+    (3 * 2^-24 relative, 4 allowed); behind it the modulation's own limit (tests/test_gpu_handoff_ref.py states the same bound
+    on the golden arrays).  hints None: the plain volume."""
+    Dc = f2.shape[1]
+    a, b = np.asarray(f2, F64), np.asarray(f3, F64)
+    dot = np.einsum("aijk,aijh->ajkh", a, b)[:, :, :, None, :]
+    mag = np.einsum("aijk,aijh->ajkh", np.abs(a), np.abs(b))[:, :, :, None, :]
+    c64 = dot / np.sqrt(float(Dc))
+    c_err = (Dc * U * mag) / np.sqrt(float(Dc)) + 4 * U * np.abs(c64)
+    if hints is None:
+        return c64, c_err
+    whole = raft_modulate(c64.astype(F32), hints, valid, rule="library")
+    keep = whole.v == 0
+    factor = np.where(keep, 1.0, np.abs(whole.mod64))
+    lim = np.where(keep, 0.0, limit(whole, exp_ulps)) + factor * c_err * (1 + 2.0 ** -10)
+    return np.where(keep, c64, c64 * whole.mod64), lim
+
+
 def kitti_decode(u16):
     """disp = u16 / 256 (exact in float32), valid = disp > 0."""
     d = np.asarray(u16, np.uint16).astype(F64) / 256.0

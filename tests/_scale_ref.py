@@ -1,6 +1,6 @@
 """numpy restatement of --iscale / --oscale (test.py:136-148, :247-248), written from DESIGN section 5 (rule 1) -- not from the
 HIP code.  Rule 1 is OpenCV 4.x `cv2.resize(img, (w, h))` (INTER_LINEAR) for 8U as we read it; rules 2 and 4 are torch's own
-expressions, which the tests run on the CPU instead of restating them."""
+expressions, which the tests run on the CPU instead of restating them (scale_hints, decimate, restore below)."""
 import numpy as np
 
 COEF = 2048  # INTER_RESIZE_COEF_SCALE
@@ -58,3 +58,37 @@ def area_fast_2x(img):
     h, w = H // 2, W // 2
     a = a[:2 * h, :2 * w]
     return ((a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+
+
+def scale_hints(hints, s):
+    """test.py:147-148: F.interpolate(hints, scale_factor=1./s, mode='nearest') / s, and the same for validhints (not divided)."""
+    import torch
+    import torch.nn.functional as F
+    t = torch.from_numpy(np.ascontiguousarray(hints, np.float32))[None, None]
+    return (F.interpolate(t, scale_factor=1. / s, mode='nearest') / s)[0, 0].numpy()
+
+
+def decimate(valid, s):
+    import torch
+    import torch.nn.functional as F
+    t = torch.from_numpy(np.ascontiguousarray(valid, np.float32))[None, None]
+    return F.interpolate(t, scale_factor=1. / s, mode='nearest')[0, 0].numpy()
+
+
+def restore(d, iscale, oscale):
+    """test.py:247-248 on the CPU."""
+    import torch
+    import torch.nn.functional as F
+    if iscale != 1 and iscale / oscale != 1:
+        t = torch.from_numpy(np.ascontiguousarray(d, np.float32))[None]
+        return (F.interpolate(t.unsqueeze(0), scale_factor=iscale / oscale, mode='nearest').squeeze(0) * iscale / oscale)[0].numpy()
+    return d
+
+
+def scaled_shape(H, W, iscale, oscale):
+    """(h, w, Ho, Wo): the shape the matcher runs at and the shape of the restored map (F.interpolate: floor(n * scale_factor))."""
+    h, w = H // iscale, W // iscale
+    if iscale != 1 and iscale / oscale != 1:
+        f = iscale / oscale
+        return h, w, int(np.floor(h * f)), int(np.floor(w * f))
+    return h, w, h, w

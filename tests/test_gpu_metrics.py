@@ -12,45 +12,14 @@ import os
 import numpy as np
 import pytest
 
+import _metrics_ref as MR
 import oracle
 import synth
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')
-
-
-def _check_record(rec, disp, gt, valid, tag=""):
-    """rec: the 8 doubles of one VppxMetrics; disp, gt, valid: what the oracle gets (gt already decimated and divided)."""
-    m = oracle.guided_metrics(disp, gt, valid)
-    n = int((np.asarray(valid) > 0).sum())
-    assert rec[6] == n and rec[7] == 0.0, (tag, rec[6], n)
-    if n == 0:
-        assert np.isnan(rec[:6]).all(), (tag, rec)
-        assert all(np.isnan(m[k]) for k in KEYS)
-        return
-    for k in range(4):
-        assert np.float64(rec[k]).tobytes() == np.float64(m[KEYS[k]]).tobytes(), (tag, KEYS[k], rec[k], m[KEYS[k]])
-    bound = (2 * n + 4) * 2.0 ** -53
-    for k in (4, 5):
-        o = m[KEYS[k]]
-        if np.isnan(o):
-            assert np.isnan(rec[k]), (tag, KEYS[k], rec[k])
-            continue
-        print(f"{tag} {KEYS[k]}: ours {rec[k]!r} oracle {o!r} |diff| {abs(rec[k] - o):.3e} bound {bound * o:.3e}")
-        assert abs(rec[k] - o) <= bound * o, (tag, KEYS[k], rec[k], o, abs(rec[k] - o), bound * o)
-
-
-def _numpy_errormap(disp, gt, valid):
-    """losses.py:14-15, :24"""
-    with np.errstate(invalid="ignore"):
-        error = np.abs(disp - gt)
-        error[valid == 0] = 0
-        return error * (valid > 0)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+# the comparison and its bound live in tests/_metrics_ref.py (the sequence tests hold their references to the same ones)
+KEYS, _check_record, _numpy_errormap, _same_bits = MR.KEYS, MR.check_record, MR.numpy_errormap, MR.same_bits
 
 
 def _data(B, H, W, seed):

@@ -22,29 +22,7 @@ def _valid(hints):
     return (hints > 0).astype(np.float32)
 
 
-def _scale_hints(hints, s):
-    """test.py:147-148: F.interpolate(hints, scale_factor=1./s, mode='nearest') / s, and the same for validhints (not divided)."""
-    import torch
-    import torch.nn.functional as F
-    t = torch.from_numpy(np.ascontiguousarray(hints, np.float32))[None, None]
-    return (F.interpolate(t, scale_factor=1. / s, mode='nearest') / s)[0, 0].numpy()
-
-
-def _decimate(valid, s):
-    import torch
-    import torch.nn.functional as F
-    t = torch.from_numpy(np.ascontiguousarray(valid, np.float32))[None, None]
-    return F.interpolate(t, scale_factor=1. / s, mode='nearest')[0, 0].numpy()
-
-
-def _restore(d, iscale, oscale):
-    """test.py:247-248 on the CPU."""
-    import torch
-    import torch.nn.functional as F
-    if iscale != 1 and iscale / oscale != 1:
-        t = torch.from_numpy(np.ascontiguousarray(d, np.float32))[None]
-        return (F.interpolate(t.unsqueeze(0), scale_factor=iscale / oscale, mode='nearest').squeeze(0) * iscale / oscale)[0].numpy()
-    return d
+_scale_hints, _decimate, _restore = ref.scale_hints, ref.decimate, ref.restore   # torch's own expressions, on the CPU
 
 
 def _want(left, right, hints, valid, iscale, oscale, seed, D, maskocc=False, g_occ=None, vpp_kw=None, rsgm_kw=None):

@@ -31,7 +31,7 @@ EXPORTS = [
     "vppx_enable_stage_timing", "vppx_get_stage_ms", "vppx_stage_name",
     "vppx_fstream_create", "vppx_fstream_destroy", "vppx_fstream_push", "vppx_fstream_flush", "vppx_fstream_pop", "vppx_fstream_counts",
     "vppx_occ_vpp_rsgm_guided_dev", "vppx_occ_vpp_rsgm_guided_host", "vppx_fstream_push_guided",
-    "vppx_scale_params_default", "vppx_scaled_shape", "vppx_occ_vpp_rsgm_scaled_dev", "vppx_occ_vpp_rsgm_scaled_host",
+    "vppx_scale_params_default", "vppx_scaled_shape", "vppx_scale_table_builds", "vppx_last_front_sets", "vppx_occ_vpp_rsgm_scaled_dev", "vppx_occ_vpp_rsgm_scaled_host",
     "vppx_fstream_create_scaled",
     "vppx_eval_params_default", "vppx_guided_metrics_dev", "vppx_guided_metrics_host", "vppx_occ_vpp_rsgm_eval_dev",
     "vppx_fstream_create_eval", "vppx_fstream_push_eval", "vppx_fstream_pop_eval",
@@ -230,6 +230,9 @@ def load():
         lib.vppx_scale_params_default.restype = None
         pi = C.POINTER(C.c_int)
         lib.vppx_scaled_shape.argtypes = [i, i, ps, pi, pi, pi, pi]
+        lib.vppx_scale_table_builds.argtypes = [vp]
+        lib.vppx_scale_table_builds.restype = C.c_long
+        lib.vppx_last_front_sets.argtypes = [vp, pi, pi]
         lib.vppx_occ_vpp_rsgm_scaled_dev.argtypes = [vp, po, pv, pr, ps, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.vppx_occ_vpp_rsgm_scaled_host.argtypes = [vp, po, pv, pr, ps, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(C.c_uint64)]

@@ -320,6 +320,14 @@ extern "C" int vppx_set_graph_mode(vppx_ctx *ctx, int enable)
 }
 
 extern "C" long vppx_graph_replays(vppx_ctx *ctx) { return ctx ? ctx->graph_replays : 0; }
+extern "C" long vppx_scale_table_builds(vppx_ctx *ctx) { return ctx ? ctx->scale_tab_builds : 0; }
+extern "C" int vppx_last_front_sets(vppx_ctx *ctx, int *scale_set, int *sample_set)
+{
+    if (!ctx) { vppx_set_error("vppx_last_front_sets: ctx is NULL"); return VPPX_E_INVALID_ARG; }
+    if (scale_set) *scale_set = ctx->last_scale_set;
+    if (sample_set) *sample_set = ctx->last_sample_set;
+    return 0;
+}
 
 // Drop the context's own stream (after draining it) before it is pointed at a caller's stream.
 static int release_own_stream(vppx_ctx *ctx)
@@ -1788,6 +1796,7 @@ static int scale_tables(vppx_ctx *ctx, int H, int W, const VppxScaleParams &sp, 
     VPPX_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
     memcpy(ctx->scale_key, key, sizeof(key));
     ctx->scale_tab_at = d;
+    ctx->scale_tab_builds++;
     *tab = (const int *)d;
     return 0;
 }
@@ -1865,6 +1874,7 @@ static int scaled_call(vppx_ctx *ctx, const HotCall &c)
     const int *tab = nullptr;
     if ((rc = scale_tables(ctx, H, W, *sp, h, w, Ho, Wo, &tab))) return rc;
     const int set = pipeline_applies(ctx) ? ctx->scale_parity : 0;
+    ctx->last_scale_set = set;
     const size_t np = (size_t)B * h * w, nb = np * C;
     u8 *ls, *rs;
     float *gs, *vhs = nullptr;
@@ -2160,6 +2170,7 @@ static int sampled_call(vppx_ctx *ctx, const HotCall &c)
     }
     if ((rc = lockstep_check(ctx))) return rc;
     const int set = pipeline_applies(ctx) ? ctx->sample_parity : 0;
+    ctx->last_sample_set = set;
     const size_t np = (size_t)B * H * W;
     float *gs, *vs = nullptr;
     if ((rc = ws_get(ctx, set ? WS_SAMPLE_G1 : WS_SAMPLE_G0, np, &gs))) return rc;

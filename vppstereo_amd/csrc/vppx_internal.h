@@ -318,6 +318,8 @@ struct vppx_ctx {
     // scaled buffers the next pipelined scaled call writes
     int scale_key[6] = {0, 0, 0, 0, 0, 0};
     const void *scale_tab_at = nullptr;
+    int last_scale_set = -1, last_sample_set = -1; // the set of scaled / sampled maps the last such call wrote: vppx_last_front_sets
+    long scale_tab_builds = 0;     // times the tables were (re)built: vppx_scale_table_builds
     int scale_parity = 0;
     hipEvent_t ev_scaled = nullptr;
     // hint sampling in front of a fused call (vppx_occ_vpp_rsgm_sampled_dev): which set of sampled maps the next pipelined call writes

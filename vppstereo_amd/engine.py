@@ -736,6 +736,18 @@ class Engine:
     def graph_replays(self):
         return int(self.lib.vppx_graph_replays(self.ctx.handle))
 
+    def last_front_sets(self):
+        """(scale set, sample set): which of the two sets of library-owned maps the last resizing / sampling call wrote
+        (vppx_last_front_sets); -1 before the first such call."""
+        a, b = C.c_int(-1), C.c_int(-1)
+        _lib.check(self.lib.vppx_last_front_sets(self.ctx.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def scale_table_builds(self):
+        """Times the context built the index tables of a scaled call (vppx_scale_table_builds): a call of the previous scaled
+        call's shape reuses them."""
+        return int(self.lib.vppx_scale_table_builds(self.ctx.handle))
+
     # ---- measurement helpers (bench.py) ----
     def time_aggregate(self, iters=10):
         ms = C.c_float()
