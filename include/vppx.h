@@ -684,6 +684,48 @@ int vppx_raft_corr_pyramid_dt_dev(vppx_ctx *ctx, void *corr, const float *hints,
 int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
                                  int64_t coords_frame_stride, int B, int H4, int W2, int W3, int levels, int radius,
                                  float *out, int dtype);
+/* ---- The read-out: the networks' output back as a float32 disparity map ---------------------------------------
+ * (models/psmnet/psmnet.py:227-233 + submodule.py:115-128, models/raft_stereo/raft_stereo.py:69-81,153-154, and the
+ * negation and crop of test.py:237-245).  Both outputs are what vppx_guided_metrics_dev, vppx_error_colors_dev and
+ * vppx_colorize_dev take.  Neither call is bit-equal to the torch composition, whose summation order is torch's own:
+ * both do the arithmetic below in float32 with float32 accumulators, and tests/_readout_ref.py derives how far any
+ * float32 association of it can lie from the exact value.  dtype (VppxDtype) is the storage of cost / of flow and mask:
+ * bfloat16 cells are widened on load (exact); out is float32 always.
+ *
+ * PSMNet:  cost [B,D4,H4,W4] (cost3 without its channel of one), D = maxdisp, the map is H x W.  Per axis with n_in
+ * source and n_out output cells, all in float32, as ATen's align_corners = False linear upsampling to a given size:
+ *     scale = (float)n_in / (float)n_out;  src = max(fma(scale, dst + 0.5f, -0.5f), 0)        one rounding, as ATen compiles it
+ *     i0 = (int)src;  i1 = i0 + (i0 < n_in - 1);  l1 = src - i0;  l0 = 1 - l1
+ *     p_k = ly0 * (lx0 * c[k,y0,x0] + lx1 * c[k,y0,x1]) + ly1 * (lx0 * c[k,y1,x0] + lx1 * c[k,y1,x1])      k = 0 .. D4-1
+ *     z_d = l0(d) * p_i0(d) + l1(d) * p_i1(d)                                                              d = 0 .. D-1
+ *     out[b,y,x] = sum_d d * exp(z_d - max_d z) / sum_d exp(z_d - max_d z)
+ * Any D4, H4, W4 >= 1 and any maxdisp, H, W >= 1 (F.upsample takes any size); the 401 MB volume [B,D,H,W] of the
+ * 544x960x192 case is never formed.
+ *
+ * RAFT-Stereo:  flow [B,C,H4,W4], frame b at flow + b * flow_frame_stride cells (so channel 0 of a [B,2,H4,W4] tensor
+ * is C = 1 with a stride of 2*H4*W4, without a copy), mask [B,mask_channels,H4,W4] with mask_channels = 9*f*f, f = 1, 2,
+ * 4 or 8 (2^n_downsample); the map is f*H4 x f*W4:
+ *     p_k = softmax over k = 0 .. 8 of mask[b, k*f*f + i*f + j, y, x], the maximum subtracted
+ *     out[b, c, f*y+i, f*x+j] = sign * sum_k p_k * (f * flow[b, c, y+ky-1, x+kx-1]),   k = 3*ky + kx
+ * with flow = +0 outside the map and sign = +1 or -1 (test.py:238 negates).
+ *
+ * The crop (test.py:242-245):  out is [B,Hout,Wout] / [B,C,Hout,Wout], the window of Hout x Wout pixels whose first
+ * pixel is (top, left) of the map; pixels outside it are not computed.  top = left = 0, Hout = H, Wout = W is the map.
+ * Non-finite input follows the arithmetic and stays in its pixel: a NaN or +inf logit (mask cell) makes the pixels
+ * that read it NaN, a -inf one has weight 0 (a pixel whose logits are all -inf is NaN, as 0/0 is); a non-finite flow
+ * cell makes the pixels that read it NaN or infinite; as in torch, a cell under a weight of exactly zero still counts
+ * (0 * inf = NaN).  Other pixels are untouched.
+ * Both calls are stream-ordered and do not synchronise.  Refused before anything is launched, with no output byte
+ * touched: a NULL cost / flow / mask / out, B, C, D4, H4, W4, maxdisp, H or W <= 0, a sign other than +1 and -1, a
+ * dtype other than the two, f not 1, 2, 4 or 8, mask_channels != 9*f*f, flow_frame_stride < C*H4*W4, a window with
+ * top or left < 0, Hout or Wout <= 0, or reaching past the map (VPPX_E_INVALID_ARG); more pixels than one launch
+ * takes, or, for PSMNet, 16*maxdisp + 256*D4 bytes above 64 KiB (VPPX_E_UNSUPPORTED: maxdisp = 192 with D4 = 48 is
+ * 15 KiB). */
+int vppx_psmnet_readout_dt_dev(vppx_ctx *ctx, const void *cost, int B, int D4, int H4, int W4, int maxdisp, int H, int W,
+                               int top, int left, int Hout, int Wout, float *out, int dtype);
+int vppx_raft_upsample_dt_dev(vppx_ctx *ctx, const void *flow, int64_t flow_frame_stride, const void *mask, int B, int C,
+                              int H4, int W4, int f, int mask_channels, int sign, int top, int left, int Hout, int Wout,
+                              float *out, int dtype);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

@@ -42,6 +42,7 @@ EXPORTS = [
     "vppx_fstream_create_sampled", "vppx_fstream_push_sampled",
     "vppx_psmnet_cost_volume_dt_dev", "vppx_raft_corr_modulate_dt_dev",
     "vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev",
+    "vppx_psmnet_readout_dt_dev", "vppx_raft_upsample_dt_dev",
 ]
 CORR_MAX_LEVELS, CORR_MAX_RADIUS = 4, 8
 DT_F32, DT_BF16 = 0, 1          # VppxDtype
@@ -192,6 +193,8 @@ def load():
         lib.vppx_raft_corr_pyramid_cells.restype = C.c_int64
         lib.vppx_raft_corr_pyramid_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
         lib.vppx_raft_corr_lookup_dt_dev.argtypes = [vp, vp, vp, vp, C.c_int64, i, i, i, i, i, i, vp, i]
+        lib.vppx_psmnet_readout_dt_dev.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, i]
+        lib.vppx_raft_upsample_dt_dev.argtypes = [vp, vp, C.c_int64, vp, i, i, i, i, i, i, i, i, i, i, i, vp, i]
         lib.vppx_kitti_disp_decode_dev.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.vppx_pfm_decode_dev.argtypes = [vp, vp, i, i, i, i, vp]
         lib.vppx_png_decode_dev.argtypes = [vp, i, vp, C.POINTER(C.c_int64), i, i, i, f, vp, vp, vp, vp]

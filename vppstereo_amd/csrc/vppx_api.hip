@@ -2557,6 +2557,61 @@ extern "C" int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, con
     return corr_lookup(ctx, corr, pyr, coords_x, coords_frame_stride, B, H4, W2, W3, levels, radius, out, dtype);
 }
 
+// The read-out of the two networks (readout_kernels.hip).  Every refusal comes before anything is launched.
+static int readout_window_ok(const char *who, int H, int W, int top, int left, int Hout, int Wout)
+{
+    if (top < 0 || left < 0 || Hout <= 0 || Wout <= 0 || (int64_t)top + Hout > H || (int64_t)left + Wout > W) {
+        vppx_set_error("%s: the window of %dx%d pixels at row %d, column %d is not inside the %dx%d map", who, Hout, Wout, top, left, H, W);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vppx_psmnet_readout_dt_dev(vppx_ctx *ctx, const void *cost, int B, int D4, int H4, int W4, int maxdisp, int H, int W,
+                                          int top, int left, int Hout, int Wout, float *out, int dtype)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!cost || !out || B <= 0 || D4 <= 0 || H4 <= 0 || W4 <= 0 || maxdisp <= 0 || H <= 0 || W <= 0) {
+        vppx_set_error("vppx_psmnet_readout: bad arguments");
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok("vppx_psmnet_readout", dtype)) return VPPX_E_INVALID_ARG;
+    if ((rc = readout_window_ok("vppx_psmnet_readout", H, W, top, left, Hout, Wout))) return rc;
+    return readout_psm(ctx, cost, B, D4, H4, W4, maxdisp, H, W, top, left, Hout, Wout, out, dtype);
+}
+
+extern "C" int vppx_raft_upsample_dt_dev(vppx_ctx *ctx, const void *flow, int64_t flow_frame_stride, const void *mask, int B, int C,
+                                         int H4, int W4, int f, int mask_channels, int sign, int top, int left, int Hout, int Wout,
+                                         float *out, int dtype)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!flow || !mask || !out || B <= 0 || C <= 0 || H4 <= 0 || W4 <= 0 || (sign != 1 && sign != -1)) {
+        vppx_set_error("vppx_raft_upsample: bad arguments (sign is +1 or -1)");
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok("vppx_raft_upsample", dtype)) return VPPX_E_INVALID_ARG;
+    if (f != 1 && f != 2 && f != 4 && f != 8) {
+        vppx_set_error("vppx_raft_upsample: factor %d is not 1, 2, 4 or 8", f);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (mask_channels != 9 * f * f) {
+        vppx_set_error("vppx_raft_upsample: the mask has %d channels, factor %d takes 9*%d*%d = %d", mask_channels, f, f, f, 9 * f * f);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (flow_frame_stride < (int64_t)C * H4 * W4) {
+        vppx_set_error("vppx_raft_upsample: flow_frame_stride %lld is less than %d planes of %dx%d", (long long)flow_frame_stride, C, H4, W4);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((int64_t)f * H4 > 0x7FFFFFFF || (int64_t)f * W4 > 0x7FFFFFFF) {
+        vppx_set_error("vppx_raft_upsample: a %dx%d map times %d is more than the call takes", H4, W4, f);
+        return VPPX_E_UNSUPPORTED;
+    }
+    if ((rc = readout_window_ok("vppx_raft_upsample", f * H4, f * W4, top, left, Hout, Wout))) return rc;
+    return readout_raft_upsample(ctx, flow, flow_frame_stride, mask, B, C, H4, W4, f, sign, top, left, Hout, Wout, out, dtype);
+}
+
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)
 {
     int rc;

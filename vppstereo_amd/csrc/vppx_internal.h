@@ -548,6 +548,12 @@ static inline int64_t corr_pyramid_offsets(int64_t N, int W3, int levels, int64_
     return cells;
 }
 
+// readout_kernels.hip: the networks' output back as a float32 disparity map (psmnet.py:227-233, raft_stereo.py:69-81, test.py:237-245)
+int readout_psm(vppx_ctx *ctx, const void *cost, int B, int D4, int H4, int W4, int D, int H, int W, int top, int left, int Hout,
+                int Wout, float *out, int dtype);
+int readout_raft_upsample(vppx_ctx *ctx, const void *flow, int64_t flow_frame_stride, const void *mask, int B, int C, int H4, int W4, int f,
+                          int sign, int top, int left, int Hout, int Wout, float *out, int dtype);
+
 // device functions the hand-off and the correlation kernels share
 // (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)
 __device__ __forceinline__ float modulation(float v, float h, float d, float two_w2)

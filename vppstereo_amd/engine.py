@@ -651,6 +651,79 @@ class Engine:
                                                          _ptr(coords), ch * H4 * W2, B, H4, W2, W3, levels, int(radius), _ptr(out), dt))
         return out
 
+    # ---- the read-out: the networks' output back as a disparity map ----
+    @staticmethod
+    def _window(H, W, crop):
+        """test.py's `_pad` list [left, right, top, bottom] (:194, :242-245) -> (top, left, Hout, Wout) of the H x W map."""
+        if crop is None:
+            return 0, 0, H, W
+        if len(crop) != 4 or any(int(c) != c or c < 0 for c in crop):
+            raise ValueError("crop must be [left, right, top, bottom], four integers >= 0")
+        left, right, top, bottom = (int(c) for c in crop)
+        if top + bottom >= H or left + right >= W:
+            raise ValueError(f"crop {list(crop)} leaves nothing of a {H}x{W} map")
+        return top, left, H - top - bottom, W - left - right
+
+    def psmnet_disparity(self, cost, maxdisp, size, crop=None, out=None):
+        """What PSMNet.forward does with cost3 (models/psmnet/psmnet.py:227-233, submodule.py:115-128) and test.py:242-245
+        with the result, in one launch: trilinear upsampling to [maxdisp, H, W] = [maxdisp, *size], softmax over the
+        disparities, the regression sum d * p_d, and the crop.  cost: [B,1,D4,H4,W4] or [B,D4,H4,W4], float32 or bfloat16;
+        crop: test.py's `_pad` list [left, right, top, bottom] or None.  -> float32 [B,Hout,Wout], which `guided_metrics`,
+        `error_colors` and `colorize` take as it is (include/vppx.h has the arithmetic)."""
+        torch = self.torch
+        dtype, dt = self._handoff_dtype(cost)
+        if getattr(cost, "dim", lambda: 0)() == 5:
+            self._chk(cost, dtype, 5, "cost")
+            if cost.shape[1] != 1:
+                raise ValueError("cost must be [B,1,D4,H4,W4] or [B,D4,H4,W4]")
+            B, _, D4, H4, W4 = cost.shape
+        else:
+            self._chk(cost, dtype, 4, "cost")
+            B, D4, H4, W4 = cost.shape
+        if len(size) != 2:
+            raise ValueError("size must be (H, W)")
+        H, W = int(size[0]), int(size[1])
+        if min(B, D4, H4, W4) < 1 or int(maxdisp) < 1 or H < 1 or W < 1:
+            raise ValueError("cost, maxdisp and size must not be empty")
+        top, left, Ho, Wo = self._window(H, W, crop)
+        if out is None:
+            out = torch.empty((B, Ho, Wo), dtype=torch.float32, device=self.device)
+        else:
+            self._chk(out, torch.float32, 3, "out", (B, Ho, Wo))
+        self._bind_stream()
+        _lib.check(self.lib.vppx_psmnet_readout_dt_dev(self.ctx.handle, _ptr(cost), B, D4, H4, W4, int(maxdisp), H, W, top, left, Ho,
+                                                       Wo, _ptr(out), dt))
+        return out
+
+    def raft_upsample(self, flow, mask, n_downsample=2, negate=False, channels=None, crop=None, out=None):
+        """RAFTStereo.upsample_flow (models/raft_stereo/raft_stereo.py:69-81) in one launch, with what follows it folded in:
+        `channels=1` is the slice [:, :1] of :154 (the other channels are not read), `negate` the sign of test.py:238, `crop`
+        test.py's `_pad` list [left, right, top, bottom] (:242-245).  flow [B,C,H4,W4] and mask [B,9*f*f,H4,W4], f =
+        2**n_downsample, float32 or bfloat16 (both the same).  -> float32 [B,channels,Hout,Wout]; with the defaults
+        [B,C,f*H4,f*W4], the reference's result."""
+        torch = self.torch
+        dtype, dt = self._handoff_dtype(flow)
+        if getattr(mask, "dtype", None) in (torch.float32, torch.bfloat16) and mask.dtype != dtype:
+            raise ValueError("flow and mask must have the same dtype (float32 or bfloat16)")
+        self._chk(flow, dtype, 4, "flow")
+        B, Cf, H4, W4 = flow.shape
+        if int(n_downsample) not in (0, 1, 2, 3):
+            raise ValueError("n_downsample must be 0, 1, 2 or 3")
+        f = 2 ** int(n_downsample)
+        self._chk(mask, dtype, 4, "mask", (B, 9 * f * f, H4, W4))
+        Cc = Cf if channels is None else int(channels)
+        if not 1 <= Cc <= Cf or min(B, H4, W4) < 1:
+            raise ValueError(f"channels must be 1 .. {Cf} of a flow that is not empty")
+        top, left, Ho, Wo = self._window(f * H4, f * W4, crop)
+        if out is None:
+            out = torch.empty((B, Cc, Ho, Wo), dtype=torch.float32, device=self.device)
+        else:
+            self._chk(out, torch.float32, 4, "out", (B, Cc, Ho, Wo))
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_upsample_dt_dev(self.ctx.handle, _ptr(flow), Cf * H4 * W4, _ptr(mask), B, Cc, H4, W4, f, 9 * f * f,
+                                                      -1 if negate else 1, top, left, Ho, Wo, _ptr(out), dt))
+        return out
+
     def kitti_disp_decode(self, png_u16):
         """uint16 PNG samples (device tensor, int16/uint16 storage) -> (disp float32, valid uint8), same shape
         (frame_utils.readDispKITTI :66-69)."""
