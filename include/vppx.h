@@ -23,6 +23,7 @@
  *   color_error_image_kitti()           utils.py:17-36              vppx_error_colors_host / _dev
  *   guided_visualize()                  utils.py:39-79              vppx_guided_visualize_host / _dev
  *   test.py:318, :325-326, :343 (max_val, applyColorMap)            vppx_finite_max_dev, vppx_colorize_host / _dev
+ *   CorrBlock1D.corr GEMM + pyramid     raft_stereo/corr.py:116-124,151-155 vppx_raft_corr_fused_dt_dev
  *   CorrBlock1D.__init__ pyramid        raft_stereo/corr.py:116-124 vppx_raft_corr_pyramid_dt_dev
  *   CorrBlock1D.__call__                raft_stereo/corr.py:126-145 vppx_raft_corr_lookup_dt_dev
  *
@@ -684,6 +685,34 @@ int vppx_raft_corr_pyramid_dt_dev(vppx_ctx *ctx, void *corr, const float *hints,
 int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
                                  int64_t coords_frame_stride, int B, int H4, int W2, int W3, int levels, int radius,
                                  float *out, int dtype);
+/* ---- CorrBlock1D: the all-pairs correlation itself, fused into the pyramid (models/raft_stereo/corr.py:151-155, 116-124)
+ * One launch reads fmap2 [B,D,H4,W2] and fmap3 [B,D,H4,W3] (NCHW, float32 or bfloat16, both of `dtype`) and writes level 0
+ * into corr [B,H4,W2,1,W3] and levels 1 .. levels-1 into pyr, both of `dtype`, in the layout of the pyramid call above
+ * (vppx_raft_corr_pyramid_cells): what it leaves is what vppx_raft_corr_lookup_dt_dev takes.  The volume is not read back.
+ *     acc[b,y,x2,x3] = sum over k < D of fmap2[b,k,y,x2] * fmap3[b,k,y,x3]
+ *         a float32 sum that starts at +0, accumulated in float32 by the matrix cores in an order the library chooses
+ *         and this header does not promise; a bfloat16 product is exact in float32.  Where every partial sum is exact in
+ *         float32, as for features on a coarse grid, the order does not matter and acc is the exact value.
+ *     c = acc / sqrt((float)D)          one correctly rounded float32 square root and one correctly rounded float32
+ *                                        DIVISION, never a multiplication by a reciprocal
+ *     with hints != NULL, for a row (b, y, x2) with v != 0:  c = c * modulation(v, h, (float)x3, 2)
+ *         the factor, the sub-sampling of hints / validhints [B,1,H,W] and the v == 0 rule are those of
+ *         vppx_raft_corr_modulate_dt_dev; a row with v == 0 (or -0) keeps c.
+ *     level 0: float32 storage holds c; bfloat16 storage holds c rounded to bfloat16 once, to nearest even (NaN as above): the
+ *         only rounding to bfloat16 a level-0 cell sees.
+ *     levels 1..: the pyramid rule above applied to the level below AS STORED, an odd last column dropped.  They equal,
+ *         bit for bit in both dtypes, what vppx_raft_corr_pyramid_dt_dev without hints makes of this call's level 0.
+ * A feature that is not finite makes the cells of its row (fmap2) or column (fmap3) not finite and no others; cells of
+ * the matrices' padding inside the kernel are zeros and are never stored.
+ * The feature maps are read with 16-byte loads when the pointer is 16-byte aligned and the row (W2, W3 cells) is a whole
+ * number of 16 bytes, and cell by cell otherwise; the same holds for the stores, per level.  A map may start anywhere.
+ * The call is stream-ordered and does not synchronise.  Refused before anything is launched, with no output byte touched:
+ * a NULL fmap2 / fmap3 / corr, pyr == NULL with levels > 1, hints without validhints, B, D, H4, W2 or W3 <= 0,
+ * levels < 1, W3 >> (levels-1) < 2, a dtype other than the two (VPPX_E_INVALID_ARG); levels > VPPX_CORR_MAX_LEVELS
+ * (VPPX_E_UNSUPPORTED); with hints, H/4 != H4 or W/4 != W2 with the modulation call's message. */
+int vppx_raft_corr_fused_dt_dev(vppx_ctx *ctx, const void *fmap2, const void *fmap3, const float *hints,
+                                const float *validhints, int B, int D, int H4, int W2, int W3, int H, int W, int levels,
+                                void *corr, void *pyr, int dtype);
 /* ---- The read-out: the networks' output back as a float32 disparity map ---------------------------------------
  * (models/psmnet/psmnet.py:227-233 + submodule.py:115-128, models/raft_stereo/raft_stereo.py:69-81,153-154, and the
  * negation and crop of test.py:237-245).  Both outputs are what vppx_guided_metrics_dev, vppx_error_colors_dev and

@@ -41,7 +41,7 @@ EXPORTS = [
     "vppx_sample_params_default", "vppx_sample_threshold", "vppx_sample_hints_dev", "vppx_sample_hints_host", "vppx_occ_vpp_rsgm_sampled_dev",
     "vppx_fstream_create_sampled", "vppx_fstream_push_sampled",
     "vppx_psmnet_cost_volume_dt_dev", "vppx_raft_corr_modulate_dt_dev",
-    "vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev",
+    "vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev", "vppx_raft_corr_fused_dt_dev",
     "vppx_psmnet_readout_dt_dev", "vppx_raft_upsample_dt_dev",
 ]
 CORR_MAX_LEVELS, CORR_MAX_RADIUS = 4, 8
@@ -192,6 +192,7 @@ def load():
         lib.vppx_raft_corr_pyramid_cells.argtypes = [C.c_int64, i, i, C.POINTER(C.c_int64)]
         lib.vppx_raft_corr_pyramid_cells.restype = C.c_int64
         lib.vppx_raft_corr_pyramid_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
+        lib.vppx_raft_corr_fused_dt_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, vp, i]
         lib.vppx_raft_corr_lookup_dt_dev.argtypes = [vp, vp, vp, vp, C.c_int64, i, i, i, i, i, i, vp, i]
         lib.vppx_psmnet_readout_dt_dev.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, i]
         lib.vppx_raft_upsample_dt_dev.argtypes = [vp, vp, C.c_int64, vp, i, i, i, i, i, i, i, i, i, i, i, vp, i]

@@ -7,44 +7,7 @@
 
 #include <math.h>
 
-struct CorrLevels {
-    long long off[VPPX_CORR_MAX_LEVELS]; // first cell of level i inside pyr (off[0] unused: level 0 is corr)
-    unsigned vec;                        // bit i: a lane's group of 8 >> i cells of level i may go as one aligned store
-};
-
-// ((+0 + a) + b) / 2: the sum starts at +0 as avg_pool2d's accumulator does, so two -0 cells pool to +0
-__device__ __forceinline__ float pool2(float a, float b) { return __fdiv_rn(__fadd_rn(__fadd_rn(0.0f, a), b), 2.0f); }
-
-// N consecutive cells of one level, the first `valid` of them inside the row; `vec`: p is aligned to the N cells
-template <int N>
-__device__ __forceinline__ void store_cells(float *p, const float *c, int valid, bool vec)
-{
-    if (N == 4 && vec && valid >= 4) {
-        *(float4 *)p = make_float4(c[0], c[1], c[2], c[3]);
-    } else if (N == 2 && vec && valid >= 2) {
-        *(float2 *)p = make_float2(c[0], c[1]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            if (j < valid) p[j] = c[j];
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void store_cells(u16 *p, const u32 *c, int valid, bool vec)
-{
-    if (N == 8 && vec && valid >= 8) {
-        *(uint4 *)p = make_uint4(c[0] | (c[1] << 16), c[2] | (c[3] << 16), c[4] | (c[5] << 16), c[6] | (c[7] << 16));
-    } else if (N == 4 && vec && valid >= 4) {
-        *(uint2 *)p = make_uint2(c[0] | (c[1] << 16), c[2] | (c[3] << 16));
-    } else if (N == 2 && vec && valid >= 2) {
-        *(u32 *)p = c[0] | (c[1] << 16);
-    } else {
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            if (j < valid) p[j] = (u16)c[j];
-    }
-}
+// CorrLevels, pool2, store_cells and corr_levels are shared with corr_gemm_kernels.hip: vppx_internal.h
 
 // One 64-lane wave per (b, y, x2) row, four rows per workgroup; a lane owns 8 consecutive cells of level 0 per trip of
 // 512, which are 4, 2 and 1 cells of levels 1, 2 and 3: every pooled cell is made in the lane's registers from the
@@ -191,22 +154,6 @@ __global__ void __launch_bounds__(256) raft_lookup_kernel(const void *__restrict
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-static CorrLevels corr_levels(const void *pyr, size_t nrows, int W3, int levels, int dtype, const void *corr)
-{
-    CorrLevels lv = {};
-    int64_t off[VPPX_CORR_MAX_LEVELS];
-    corr_pyramid_offsets((int64_t)nrows, W3, levels, off);
-    const size_t cell = dtype == VPPX_DT_BF16 ? 2 : 4;
-    for (int i = 0; i < levels; i++) {
-        lv.off[i] = off[i];
-        // level 0 goes as 16-byte vectors (4 float32 cells, 8 bf16 cells); level i >= 1 as the lane's whole group of 8 >> i cells
-        const size_t width = i ? (8 >> i) * cell : 16;
-        const uintptr_t first = i ? (uintptr_t)pyr + (size_t)off[i] * cell : (uintptr_t)corr;
-        if (width > cell && first % width == 0 && ((size_t)(W3 >> i) * cell) % width == 0) lv.vec |= 1u << i;
-    }
-    return lv;
-}
-
 int corr_pyramid(vppx_ctx *ctx, void *corr, const float *hints, const float *valid, int B, int H4, int W2, int W3, int H, int W,
                  int levels, void *pyr, int dtype)
 {

@@ -2539,6 +2539,20 @@ extern "C" int vppx_raft_corr_pyramid_dt_dev(vppx_ctx *ctx, void *corr, const fl
     return corr_pyramid(ctx, corr, hints, validhints, B, H4, W2, W3, H, W, levels, pyr, dtype);
 }
 
+extern "C" int vppx_raft_corr_fused_dt_dev(vppx_ctx *ctx, const void *fmap2, const void *fmap3, const float *hints,
+                                           const float *validhints, int B, int D, int H4, int W2, int W3, int H, int W, int levels,
+                                           void *corr, void *pyr, int dtype)
+{
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!fmap2 || !fmap3 || !corr || (hints && !validhints) || (!pyr && levels > 1) || D <= 0) {
+        vppx_set_error("vppx_raft_corr_fused: bad arguments");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = corr_shape_ok("vppx_raft_corr_fused", B, H4, W2, W3, levels, 0, dtype))) return rc;
+    return corr_fused(ctx, fmap2, fmap3, hints, validhints, B, D, H4, W2, W3, H, W, levels, corr, pyr, dtype);
+}
+
 extern "C" int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
                                             int64_t coords_frame_stride, int B, int H4, int W2, int W3, int levels, int radius,
                                             float *out, int dtype)

@@ -536,6 +536,10 @@ int corr_pyramid(vppx_ctx *ctx, void *corr, const float *hints, const float *val
                  int levels, void *pyr, int dtype);
 int corr_lookup(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x, int64_t coords_frame_stride, int B, int H4,
                 int W2, int W3, int levels, int radius, float *out, int dtype);
+// corr_gemm_kernels.hip: the all-pairs correlation itself (corr.py:151-155) on the matrix cores, fused with / sqrt(D), the hint
+// modulation and the pyramid
+int corr_fused(vppx_ctx *ctx, const void *fmap2, const void *fmap3, const float *hints, const float *valid, int B, int D, int H4,
+               int W2, int W3, int H, int W, int levels, void *corr, void *pyr, int dtype);
 // levels 1 .. levels-1 back to back, each dense [N][W3 >> i]: off[i] = first cell of level i (off[0] = 0, unused) -> cells in all
 static inline int64_t corr_pyramid_offsets(int64_t N, int W3, int levels, int64_t *off)
 {
@@ -574,6 +578,63 @@ __device__ __forceinline__ u32 bf16_rne(float f)
 }
 
 __device__ __forceinline__ u32 bf16_scale(u32 bits, float mod) { return bf16_rne(__fmul_rn(bf16_widen(bits), mod)); }
+
+// what corr_kernels.hip and corr_gemm_kernels.hip share: where the levels lie, how a level is pooled, how a lane stores its cells
+struct CorrLevels {
+    long long off[VPPX_CORR_MAX_LEVELS]; // first cell of level i inside pyr (off[0] unused: level 0 is corr)
+    unsigned vec;                        // bit i: a lane's group of 8 >> i cells of level i may go as one aligned store
+};
+
+// ((+0 + a) + b) / 2: the sum starts at +0 as avg_pool2d's accumulator does, so two -0 cells pool to +0
+__device__ __forceinline__ float pool2(float a, float b) { return __fdiv_rn(__fadd_rn(__fadd_rn(0.0f, a), b), 2.0f); }
+
+// N consecutive cells of one level, the first `valid` of them inside the row; `vec`: p is aligned to the N cells
+template <int N>
+__device__ __forceinline__ void store_cells(float *p, const float *c, int valid, bool vec)
+{
+    if (N == 4 && vec && valid >= 4) {
+        *(float4 *)p = make_float4(c[0], c[1], c[2], c[3]);
+    } else if (N == 2 && vec && valid >= 2) {
+        *(float2 *)p = make_float2(c[0], c[1]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++)
+            if (j < valid) p[j] = c[j];
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void store_cells(u16 *p, const u32 *c, int valid, bool vec)
+{
+    if (N == 8 && vec && valid >= 8) {
+        *(uint4 *)p = make_uint4(c[0] | (c[1] << 16), c[2] | (c[3] << 16), c[4] | (c[5] << 16), c[6] | (c[7] << 16));
+    } else if (N == 4 && vec && valid >= 4) {
+        *(uint2 *)p = make_uint2(c[0] | (c[1] << 16), c[2] | (c[3] << 16));
+    } else if (N == 2 && vec && valid >= 2) {
+        *(u32 *)p = c[0] | (c[1] << 16);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++)
+            if (j < valid) p[j] = (u16)c[j];
+    }
+}
+
+static inline CorrLevels corr_levels(const void *pyr, size_t nrows, int W3, int levels, int dtype, const void *corr)
+{
+    CorrLevels lv = {};
+    int64_t off[VPPX_CORR_MAX_LEVELS];
+    corr_pyramid_offsets((int64_t)nrows, W3, levels, off);
+    const size_t cell = dtype == VPPX_DT_BF16 ? 2 : 4;
+    for (int i = 0; i < levels; i++) {
+        lv.off[i] = off[i];
+        // level 0 goes as 16-byte vectors (4 float32 cells, 8 bf16 cells); level i >= 1 as the lane's whole group of 8 >> i cells
+        const size_t width = i ? (8 >> i) * cell : 16;
+        const uintptr_t first = i ? (uintptr_t)pyr + (size_t)off[i] * cell : (uintptr_t)corr;
+        if (width > cell && first % width == 0 && ((size_t)(W3 >> i) * cell) % width == 0) lv.vec |= 1u << i;
+    }
+    return lv;
+}
+
 // png_kernels.hip
 int handoff_png_decode(vppx_ctx *ctx, int n_files, const u8 *blob_dev, const long long *offs_dev, int H, int W, int C, u8 *zcat,
                        const long long *zoffs_dev, float scale, float *disp, u8 *valid, u8 *out_u8, int *status_dev);

@@ -615,6 +615,41 @@ class Engine:
             out.append(pyr[off[i]:off[i] + N * Wi].view(N, 1, 1, Wi))
         return out
 
+    def raft_corr_fused(self, fmap2, fmap3, hints=None, validhints=None, num_levels=4):
+        """CorrBlock1D's GEMM, / sqrt(D), hint modulation and pyramid (models/raft_stereo/corr.py:151-155, 116-124) in one
+        launch on the matrix cores: the feature maps [B,D,H4,W2] / [B,D,H4,W3] (float32 or bfloat16, both the same) are
+        read, the levels are written, the volume is never read back.  The division is one IEEE division and a bfloat16
+        cell is the float32 result rounded once (include/vppx.h).  -> the list raft_corr_pyramid returns: entry 0 is
+        [N,1,1,W3], N = B*H4*W2, the others are views into one buffer."""
+        torch = self.torch
+        dtype, dt = self._handoff_dtype(fmap2)
+        if getattr(fmap3, "dtype", None) in (torch.float32, torch.bfloat16) and fmap3.dtype != dtype:
+            raise ValueError("feature maps must have the same dtype (float32 or bfloat16)")
+        self._chk(fmap2, dtype, 4, "fmap2")
+        self._chk(fmap3, dtype, 4, "fmap3")
+        B, Dc, H4, W2 = fmap2.shape
+        if fmap3.shape[:3] != fmap2.shape[:3]:
+            raise ValueError("fmap2 / fmap3 must be [B,D,H4,W2] / [B,D,H4,W3]")
+        W3 = fmap3.shape[3]
+        H = W = 0
+        if hints is not None:
+            self._chk_hint_pair(hints, validhints, B)
+            H, W = hints.shape[2:]
+        levels, N = int(num_levels), B * H4 * W2
+        cells, off = self._corr_offsets(N, W3, levels)
+        corr = torch.empty((N, 1, 1, W3), dtype=dtype, device=self.device)
+        pyr = torch.empty((cells,), dtype=dtype, device=self.device) if levels > 1 else None
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_corr_fused_dt_dev(self.ctx.handle, _ptr(fmap2), _ptr(fmap3),
+                                                        _ptr(hints) if hints is not None else None,
+                                                        _ptr(validhints) if hints is not None else None, B, Dc, H4, W2, W3,
+                                                        int(H), int(W), levels, _ptr(corr), _ptr(pyr) if pyr is not None else None, dt))
+        out = [corr]
+        for i in range(1, levels):
+            Wi = W3 >> i
+            out.append(pyr[off[i]:off[i] + N * Wi].view(N, 1, 1, Wi))
+        return out
+
     def raft_corr_lookup(self, pyramid, coords, radius=4, out=None):
         """CorrBlock1D.__call__ (corr.py:126-145) in one launch: `pyramid` is what raft_corr_pyramid returned, `coords`
         float32 [B,2,H4,W2] (channel 0 is read, as the reference does) or [B,H4,W2].  -> float32
