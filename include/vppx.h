@@ -755,6 +755,65 @@ int vppx_psmnet_readout_dt_dev(vppx_ctx *ctx, const void *cost, int B, int D4, i
 int vppx_raft_upsample_dt_dev(vppx_ctx *ctx, const void *flow, int64_t flow_frame_stride, const void *mask, int B, int C,
                               int H4, int W4, int f, int mask_channels, int sign, int top, int left, int Hout, int Wout,
                               float *out, int dtype);
+/* ---- The update block's glue: what BasicMultiUpdateBlock.forward runs between its convolutions ------------------
+ * (models/raft_stereo/update.py:119-142 with ConvGRU.forward :23-32, pool2x :89-90, interp :95-97 and the encoder's
+ * cat :87).  Three calls; the convolutions between them stay the caller's.  dtype (VppxDtype) is the storage of every
+ * tensor of a call: bfloat16 cells are widened on load (exact), the arithmetic below is float32, one correctly rounded
+ * operation per step, and a bfloat16 result is the float32 result rounded once, to nearest even (NaN stays NaN).
+ * tests/_gru_ref.py derives how far any float32 evaluation of it can lie from the exact value.
+ *
+ * Addressing.  Every tensor argument is [B,C,H,W]; frame b starts b * its frame stride cells behind the pointer, and a
+ * frame is contiguous.  A frame stride is at least C*H*W.  cz, cr and cq are therefore passed as the three channel
+ * slices of one [B,3C,H,W] convolution output (raft_stereo.py:104) with a stride of 3C*H*W, without a copy.  No
+ * pointer has to be aligned beyond its cell: a call moves 16 bytes per lane where every pointer it takes is 16-byte
+ * aligned and every frame stride a whole number of 16 bytes, and cell by cell otherwise, with the same results.
+ *
+ * Assemble:  hx [B,hx_channels,H,W] contiguous; channels 0 .. sum C_i - 1 receive cat(sources, dim=1), channels beyond
+ * them are not written.  Source i is [B,C,Hs,Ws] and arrives by its mode:
+ *     VPPX_GRU_COPY     Hs = H, Ws = W; the cell itself (a bfloat16 cell keeps its 16 bits where the copy moves whole vectors,
+ *                       and is widened and rounded back, which changes no value, elsewhere)
+ *     VPPX_GRU_POOL2X   F.avg_pool2d(x, 3, stride=2, padding=1):  (Hs-1)/2 + 1 == H and (Ws-1)/2 + 1 == W;
+ *                       out[y,x] = (sum over ky, kx = 0 .. 2 of x[2y-1+ky, 2x-1+kx], +0 outside the map, started at +0
+ *                       and taken in the order k = 3*ky + kx) / 9, the divisor being 9 at the border too
+ *     VPPX_GRU_INTERP   F.interpolate(x, (H,W), mode='bilinear', align_corners=True) from any Hs, Ws >= 1.  Per axis:
+ *                       scale = (float)(n_in-1) / (float)(n_out-1), or 0 when n_out == 1;  src = scale * dst
+ *                       i0 = (int)src;  i1 = i0 + (i0 < n_in-1);  l1 = src - i0;  l0 = 1 - l1
+ *                       out = (ly0 * (lx0*a + lx1*b)) + (ly1 * (lx0*c + lx1*d)),  a, b on row y0 and c, d on row y1
+ * Reset:  r = sigmoid(ar + cr);  hx[b, c] = r * h[b, c] for c < C, IN PLACE over the first C channels of hx
+ * [B,hx_channels,H,W]; channels C .. hx_channels-1 are neither read nor written.
+ *     Ordering contract.  The call overwrites the h part of the buffer the z and r convolutions read.  It is stream-
+ *     ordered: enqueue it after both convolutions on the same stream (or behind an event of theirs) and the q
+ *     convolution after it; that convolution then reads cat([r*h, x]) from the same buffer, with no second buffer and no
+ *     copy of x.  h is read from its own tensor (net[i]), never from hx, and must not overlap the cells written.
+ * Update:  z = sigmoid(az + cz);  q = tanh(aq + cq);  out = ((1 - z) * h) + (z * q).  z is recomputed from az rather than
+ * kept by the reset call.  out may be h itself (every cell is read before it is written, by the lane that writes it);
+ * it must not overlap any other argument.
+ *     sigmoid(v) = 1 / (1 + expf(-v))            tanh(v) = 1 - 2 / (expf(2 * v) + 1)
+ * with the device's expf and IEEE operations otherwise, so that v = +inf gives 1 and 1, v = -inf gives 0 and -1, neither
+ * gives NaN, and a large finite v saturates the same way (expf overflows to +inf).  Non-finite input follows the arithmetic
+ * and stays in its cell: a NaN gives NaN in that cell (and, through pool2x and interp, in the cells whose window holds it).
+ * All three calls are stream-ordered, never synchronise and allocate nothing.  Refused before anything is launched, with
+ * no output byte touched: a NULL pointer (sources, a source's ptr, any tensor); B, C, H, W, Hs or Ws <= 0; a frame stride
+ * below C*H*W (C*Hs*Ws for a source); a dtype other than the two; n_sources < 1 or > VPPX_GRU_MAX_SOURCES; an unknown
+ * mode; a copied source that is not H x W, a pooled one of the wrong size; hx_channels below sum C_i (assemble) or below
+ * C (reset), where hx_frame_stride below hx_channels*H*W is refused as well (VPPX_E_INVALID_ARG); more cells than one launch
+ * takes (VPPX_E_UNSUPPORTED). */
+#define VPPX_GRU_MAX_SOURCES 4
+typedef enum VppxGruMode { VPPX_GRU_COPY = 0, VPPX_GRU_POOL2X = 1, VPPX_GRU_INTERP = 2 } VppxGruMode;
+typedef struct VppxGruSource {
+    const void *ptr;      /* [B,C,Hs,Ws] of the call's dtype (device)                */
+    int64_t frame_stride; /* cells between frames, >= C*Hs*Ws                        */
+    int32_t C, Hs, Ws;
+    int32_t mode;         /* VppxGruMode                                             */
+} VppxGruSource;
+int vppx_raft_gru_assemble_dt_dev(vppx_ctx *ctx, const VppxGruSource *sources, int n_sources, int B, int H, int W, void *hx,
+                                  int hx_channels, int dtype);
+int vppx_raft_gru_reset_dt_dev(vppx_ctx *ctx, const void *ar, int64_t ar_frame_stride, const void *cr, int64_t cr_frame_stride,
+                               const void *h, int64_t h_frame_stride, void *hx, int64_t hx_frame_stride, int B, int C, int H, int W,
+                               int hx_channels, int dtype);
+int vppx_raft_gru_update_dt_dev(vppx_ctx *ctx, const void *az, int64_t az_frame_stride, const void *cz, int64_t cz_frame_stride,
+                                const void *aq, int64_t aq_frame_stride, const void *cq, int64_t cq_frame_stride, const void *h,
+                                int64_t h_frame_stride, void *out, int64_t out_frame_stride, int B, int C, int H, int W, int dtype);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

@@ -2626,6 +2626,124 @@ extern "C" int vppx_raft_upsample_dt_dev(vppx_ctx *ctx, const void *flow, int64_
     return readout_raft_upsample(ctx, flow, flow_frame_stride, mask, B, C, H4, W4, f, sign, top, left, Hout, Wout, out, dtype);
 }
 
+// The update block's glue (gru_kernels.hip).  Every refusal comes before anything is launched.
+static int gru_shape_ok(const char *who, int B, int C, int H, int W, int dtype)
+{
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) {
+        vppx_set_error("%s: bad arguments (B, C, H and W must be positive)", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok(who, dtype)) return VPPX_E_INVALID_ARG;
+    if ((int64_t)H * W > 0x7FFFFFFF) {
+        vppx_set_error("%s: a %dx%d map is more than the call takes", who, H, W);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+static int gru_stride_ok(const char *who, const char *what, int64_t stride, int C, int H, int W)
+{
+    if (stride < (int64_t)C * H * W) {
+        vppx_set_error("%s: %s_frame_stride %lld is less than %d planes of %dx%d", who, what, (long long)stride, C, H, W);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vppx_raft_gru_assemble_dt_dev(vppx_ctx *ctx, const VppxGruSource *sources, int n_sources, int B, int H, int W, void *hx,
+                                             int hx_channels, int dtype)
+{
+    static const char *who = "vppx_raft_gru_assemble";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!sources || !hx) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (n_sources < 1 || n_sources > VPPX_GRU_MAX_SOURCES) {
+        vppx_set_error("%s: %d sources, 1 .. %d are taken", who, n_sources, VPPX_GRU_MAX_SOURCES);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, 1, H, W, dtype))) return rc;
+    int64_t channels = 0;
+    for (int k = 0; k < n_sources; k++) {
+        const VppxGruSource &s = sources[k];
+        if (!s.ptr || s.C <= 0 || s.Hs <= 0 || s.Ws <= 0) {
+            vppx_set_error("%s: source %d: bad arguments", who, k);
+            return VPPX_E_INVALID_ARG;
+        }
+        if ((int64_t)s.Hs * s.Ws > 0x7FFFFFFF) {
+            vppx_set_error("%s: source %d: a %dx%d map is more than the call takes", who, k, s.Hs, s.Ws);
+            return VPPX_E_UNSUPPORTED;
+        }
+        if (s.mode == VPPX_GRU_COPY) {
+            if (s.Hs != H || s.Ws != W) {
+                vppx_set_error("%s: source %d is copied and is %dx%d, hx is %dx%d", who, k, s.Hs, s.Ws, H, W);
+                return VPPX_E_INVALID_ARG;
+            }
+        } else if (s.mode == VPPX_GRU_POOL2X) {
+            if ((s.Hs - 1) / 2 + 1 != H || (s.Ws - 1) / 2 + 1 != W) {
+                vppx_set_error("%s: source %d is %dx%d and pools to %dx%d, hx is %dx%d", who, k, s.Hs, s.Ws, (s.Hs - 1) / 2 + 1,
+                               (s.Ws - 1) / 2 + 1, H, W);
+                return VPPX_E_INVALID_ARG;
+            }
+        } else if (s.mode != VPPX_GRU_INTERP) {
+            vppx_set_error("%s: source %d: mode %d is not VPPX_GRU_COPY, VPPX_GRU_POOL2X or VPPX_GRU_INTERP", who, k, s.mode);
+            return VPPX_E_INVALID_ARG;
+        }
+        if ((rc = gru_stride_ok(who, "source", s.frame_stride, s.C, s.Hs, s.Ws))) return rc;
+        channels += s.C;
+    }
+    if (hx_channels < channels) {
+        vppx_set_error("%s: hx has %d channels, the sources have %lld", who, hx_channels, (long long)channels);
+        return VPPX_E_INVALID_ARG;
+    }
+    return gru_assemble(ctx, sources, n_sources, B, H, W, hx, hx_channels, dtype);
+}
+
+extern "C" int vppx_raft_gru_reset_dt_dev(vppx_ctx *ctx, const void *ar, int64_t ar_frame_stride, const void *cr, int64_t cr_frame_stride,
+                                          const void *h, int64_t h_frame_stride, void *hx, int64_t hx_frame_stride, int B, int C, int H,
+                                          int W, int hx_channels, int dtype)
+{
+    static const char *who = "vppx_raft_gru_reset";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!ar || !cr || !h || !hx) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, C, H, W, dtype))) return rc;
+    if (hx_channels < C) {
+        vppx_set_error("%s: hx has %d channels, h has %d", who, hx_channels, C);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_stride_ok(who, "ar", ar_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "cr", cr_frame_stride, C, H, W)) ||
+        (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "hx", hx_frame_stride, hx_channels, H, W)))
+        return rc;
+    return gru_reset(ctx, ar, ar_frame_stride, cr, cr_frame_stride, h, h_frame_stride, hx, hx_frame_stride, B, C, H, W, dtype);
+}
+
+extern "C" int vppx_raft_gru_update_dt_dev(vppx_ctx *ctx, const void *az, int64_t az_frame_stride, const void *cz, int64_t cz_frame_stride,
+                                           const void *aq, int64_t aq_frame_stride, const void *cq, int64_t cq_frame_stride, const void *h,
+                                           int64_t h_frame_stride, void *out, int64_t out_frame_stride, int B, int C, int H, int W,
+                                           int dtype)
+{
+    static const char *who = "vppx_raft_gru_update";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!az || !cz || !aq || !cq || !h || !out) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, C, H, W, dtype))) return rc;
+    if ((rc = gru_stride_ok(who, "az", az_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "cz", cz_frame_stride, C, H, W)) ||
+        (rc = gru_stride_ok(who, "aq", aq_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "cq", cq_frame_stride, C, H, W)) ||
+        (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "out", out_frame_stride, C, H, W)))
+        return rc;
+    return gru_update(ctx, az, az_frame_stride, cz, cz_frame_stride, aq, aq_frame_stride, cq, cq_frame_stride, h, h_frame_stride, out,
+                      out_frame_stride, B, C, H, W, dtype);
+}
+
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)
 {
     int rc;

@@ -558,6 +558,13 @@ int readout_psm(vppx_ctx *ctx, const void *cost, int B, int D4, int H4, int W4, 
 int readout_raft_upsample(vppx_ctx *ctx, const void *flow, int64_t flow_frame_stride, const void *mask, int B, int C, int H4, int W4, int f,
                           int sign, int top, int left, int Hout, int Wout, float *out, int dtype);
 
+// gru_kernels.hip: the update block's glue (models/raft_stereo/update.py:23-32, 87-97, 119-142)
+int gru_assemble(vppx_ctx *ctx, const VppxGruSource *src, int n_src, int B, int H, int W, void *hx, int hx_channels, int dtype);
+int gru_reset(vppx_ctx *ctx, const void *ar, int64_t sar, const void *cr, int64_t scr, const void *h, int64_t sh, void *hx, int64_t shx,
+              int B, int C, int H, int W, int dtype);
+int gru_update(vppx_ctx *ctx, const void *az, int64_t saz, const void *cz, int64_t scz, const void *aq, int64_t saq, const void *cq,
+               int64_t scq, const void *h, int64_t sh, void *out, int64_t so, int B, int C, int H, int W, int dtype);
+
 // device functions the hand-off and the correlation kernels share
 // (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)
 __device__ __forceinline__ float modulation(float v, float h, float d, float two_w2)

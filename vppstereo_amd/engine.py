@@ -759,6 +759,94 @@ class Engine:
                                                       -1 if negate else 1, top, left, Ho, Wo, _ptr(out), dt))
         return out
 
+    # ---- the update block's glue: what BasicMultiUpdateBlock.forward runs between its convolutions ----
+    def _chk_frames(self, t, dtype, name, shape=None):
+        """A [B,C,H,W] tensor whose frames are contiguous and lie a frame stride apart (a channel slice of a wider
+        tensor, as `.split(dim=1)` returns, or a contiguous tensor) -> the frame stride in cells."""
+        if getattr(t, "device", None) != self.device or t.dtype != dtype or t.dim() != 4:
+            raise ValueError(f"{name}: expected a {dtype} tensor with 4 dims on {self.device}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        B, Cc, H, W = t.shape
+        if min(B, Cc, H, W) < 1:
+            raise ValueError(f"{name}: empty tensor {tuple(t.shape)}")
+        want = (Cc * H * W, H * W, W, 1)
+        st = t.stride()
+        if any(t.shape[d] > 1 and st[d] != want[d] for d in (1, 2, 3)) or (B > 1 and st[0] < want[0]):
+            raise ValueError(f"{name}: every frame must be contiguous (strides {tuple(st)} of shape {tuple(t.shape)})")
+        return int(st[0]) if B > 1 else want[0]
+
+    def raft_gru_assemble(self, sources, out=None):
+        """hx = torch.cat(sources, dim=1) for a ConvGRU (models/raft_stereo/update.py:24-25) in one launch.  `sources`:
+        up to four (tensor, mode); mode "copy" takes the tensor [B,C,H,W] as it is, "pool2x" is update.py's pool2x
+        (avg_pool2d(3, stride=2, padding=1)) and "interp" its interp (bilinear, align_corners=True) to the H x W of the
+        result, which a copied source or `out` fixes.  float32 or bfloat16, all the same; every tensor may be a channel
+        slice of a wider one.  -> contiguous [B, sum C_i, H, W]; with `out` nothing is allocated, and an `out` of more
+        channels keeps the others (include/vppx.h has the arithmetic)."""
+        torch = self.torch
+        sources = list(sources)
+        if not 1 <= len(sources) <= _lib.GRU_MAX_SOURCES:
+            raise ValueError(f"sources: {len(sources)} given, 1 .. {_lib.GRU_MAX_SOURCES} are taken")
+        dtype, dt = self._handoff_dtype(sources[0][0])
+        arr = (_lib.VppxGruSource * len(sources))()
+        size, total = None, 0
+        for k, (t, mode) in enumerate(sources):
+            if mode not in _lib.GRU_MODES:
+                raise ValueError(f"sources[{k}]: unknown mode {mode!r} (one of {tuple(_lib.GRU_MODES)})")
+            stride = self._chk_frames(t, dtype, f"sources[{k}]")
+            if t.shape[0] != sources[0][0].shape[0]:
+                raise ValueError(f"sources[{k}]: {t.shape[0]} frames, sources[0] has {sources[0][0].shape[0]}")
+            arr[k] = _lib.VppxGruSource(t.data_ptr(), stride, t.shape[1], t.shape[2], t.shape[3], _lib.GRU_MODES[mode])
+            total += t.shape[1]
+            if mode == "copy" and size is None:
+                size = tuple(t.shape[2:])
+        B = sources[0][0].shape[0]
+        if out is None:
+            if size is None:
+                raise ValueError("sources: no copied source fixes the size of hx; pass out=")
+            out = torch.empty((B, total) + size, dtype=dtype, device=self.device)
+        else:
+            self._chk(out, dtype, 4, "out")
+            if out.shape[0] != B:
+                raise ValueError(f"out: {out.shape[0]} frames, the sources have {B}")
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_gru_assemble_dt_dev(self.ctx.handle, arr, len(sources), B, out.shape[2], out.shape[3], _ptr(out),
+                                                          out.shape[1], dt))
+        return out
+
+    def raft_gru_reset(self, ar, cr, h, hx):
+        """r = sigmoid(ar + cr), then r * h over the first C channels of `hx` [B,>=C,H,W], IN PLACE (ConvGRU.forward,
+        update.py:28-29): `ar` is convr(hx), `cr` the context's share, `h` [B,C,H,W] the hidden state itself.  The z and
+        r convolutions must have read hx by then (stream order); convq then reads the same buffer as cat([r*h, x]).
+        -> hx."""
+        dtype, dt = self._handoff_dtype(h)
+        sh = self._chk_frames(h, dtype, "h")
+        B, Cc, H, W = h.shape
+        sa = self._chk_frames(ar, dtype, "ar", h.shape)
+        sc = self._chk_frames(cr, dtype, "cr", h.shape)
+        sx = self._chk_frames(hx, dtype, "hx")
+        if hx.shape[0] != B or tuple(hx.shape[2:]) != (H, W):
+            raise ValueError(f"hx: expected [{B},>={Cc},{H},{W}], got {tuple(hx.shape)}")
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_gru_reset_dt_dev(self.ctx.handle, _ptr(ar), sa, _ptr(cr), sc, _ptr(h), sh, _ptr(hx), sx, B, Cc, H, W,
+                                                       hx.shape[1], dt))
+        return hx
+
+    def raft_gru_update(self, az, cz, aq, cq, h, out=None):
+        """z = sigmoid(az + cz), q = tanh(aq + cq), -> (1 - z) * h + z * q (ConvGRU.forward, update.py:27-31): `az`
+        and `aq` are convz's and convq's outputs, `cz` and `cq` the context's shares.  `out` may be `h`."""
+        dtype, dt = self._handoff_dtype(h)
+        sh = self._chk_frames(h, dtype, "h")
+        B, Cc, H, W = h.shape
+        s = [self._chk_frames(t, dtype, n, h.shape) for t, n in ((az, "az"), (cz, "cz"), (aq, "aq"), (cq, "cq"))]
+        if out is None:
+            out = self.torch.empty(tuple(h.shape), dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", h.shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_gru_update_dt_dev(self.ctx.handle, _ptr(az), s[0], _ptr(cz), s[1], _ptr(aq), s[2], _ptr(cq), s[3],
+                                                        _ptr(h), sh, _ptr(out), so, B, Cc, H, W, dt))
+        return out
+
     def kitti_disp_decode(self, png_u16):
         """uint16 PNG samples (device tensor, int16/uint16 storage) -> (disp float32, valid uint8), same shape
         (frame_utils.readDispKITTI :66-69)."""
