@@ -26,6 +26,7 @@
  *   CorrBlock1D.corr GEMM + pyramid     raft_stereo/corr.py:116-124,151-155 vppx_raft_corr_fused_dt_dev
  *   CorrBlock1D.__init__ pyramid        raft_stereo/corr.py:116-124 vppx_raft_corr_pyramid_dt_dev
  *   CorrBlock1D.__call__                raft_stereo/corr.py:126-145 vppx_raft_corr_lookup_dt_dev
+ *   BasicMotionEncoder convc1 / convf1  raft_stereo/update.py:80,82 vppx_raft_motion_front_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -814,6 +815,43 @@ int vppx_raft_gru_reset_dt_dev(vppx_ctx *ctx, const void *ar, int64_t ar_frame_s
 int vppx_raft_gru_update_dt_dev(vppx_ctx *ctx, const void *az, int64_t az_frame_stride, const void *cz, int64_t cz_frame_stride,
                                 const void *aq, int64_t aq_frame_stride, const void *cq, int64_t cq_frame_stride, const void *h,
                                 int64_t h_frame_stride, void *out, int64_t out_frame_stride, int B, int C, int H, int W, int dtype);
+/* ---- The motion encoder's front: the lookup fused into convc1, and convf1 (models/raft_stereo/update.py:80,82) -------
+ * One launch makes cor1 = relu(convc1(corr_fn(coords1))) and flo1 = relu(convf1(flow)) of BasicMotionEncoder.forward; the
+ * float32 [B, levels*(2*radius+1), H4, W2] tensor of taps between the lookup and convc1 is never written.  corr, pyr,
+ * coords_x, coords_frame_stride, W3, levels, radius and dtype are those of vppx_raft_corr_lookup_dt_dev above.  Per pixel
+ * n = (b, y, x), with K = levels*(2*radius+1) and p = ks / 2:
+ *     taps[k], k = i * (2*radius+1) + t:  the lookup's arithmetic above, operation by operation (a bfloat16 cell of the
+ *         pyramid is widened first); the taps stay float32 and are bit for bit what the lookup call would have stored.
+ *     out_c[b][m][y][x] = relu(bias_c[m] + sum over k < K of wc[m][k] * taps[k])                                   m < Cc
+ *     out_f[b][m][y][x] = relu(bias_f[m] + sum over c < 2, dy < ks, dx < ks of
+ *                              wf[m][c][dy][dx] * flow[b][c][y + dy - p][x + dx - p])                              m < Cf
+ *         with flow = +0 outside the map: cross-correlation, as nn.Conv2d computes it, not a flipped kernel.
+ * The sums are float32, accumulated in float32 by the matrix cores (v_mfma_f32_16x16x4_f32 for both pyramid dtypes: a tap
+ * is never rounded to bfloat16), starting at +0, in an order the library chooses and this header does not promise, as in
+ * vppx_raft_corr_fused_dt_dev; the bias is one more term of that sum.  tests/_motion_ref.py derives how far any float32
+ * evaluation in any order can lie from the exact value.  relu(v) = v > 0 ? v : 0 where a NaN stays NaN, as torch's; the
+ * sign of a zero result is not specified.  A pixel whose taps are all +0 (a coordinate far outside, infinite or NaN) gives
+ * relu(bias_c[m]) exactly.  A flow cell that is not finite reaches the ks x ks pixels whose window holds it and no others.
+ * wc [Cc][K] and wf [Cf][2][ks][ks] are float32 always, in torch's [Cout, Cin, kh, kw] layout, contiguous; bias_c [Cc] and
+ * bias_f [Cf] are float32 and either may be NULL (no bias).  flow is float32 [B,2,H4,W2].  out_c [B,Cc,H4,W2] and out_f
+ * [B,Cf,H4,W2] are of out_dtype (VppxDtype), independent of the pyramid's dtype: a bfloat16 cell is the float32 result
+ * rounded once, to nearest even (NaN stays NaN).  Every cell of both is written.
+ * Addressing: frame b of flow, out_c and out_f starts b * its frame stride cells behind the pointer and is contiguous, so
+ * out_c and out_f may be channel slices of one [B,Cc+Cf,H4,W2] buffer.  No pointer has to be aligned beyond its cell: an
+ * output is written 16 bytes at a time where its pointer is 16-byte aligned and its frame stride and H4*W2 are whole numbers
+ * of 16 bytes, and cell by cell otherwise, with the same results.
+ * The call is stream-ordered, does not synchronise and allocates nothing.  Refused before anything is launched, with no output
+ * byte touched: everything the lookup refuses, with the lookup's codes; a NULL flow, wc, wf, out_c or out_f; a frame stride
+ * below its tensor's size (2, Cc or Cf planes of H4*W2); Cc or Cf <= 0; ks < 1 or even; an out_dtype other than the two
+ * (VPPX_E_INVALID_ARG); Cc or Cf not a multiple of 16 or above VPPX_MOTION_MAX_CH, ks above VPPX_MOTION_MAX_KS, B*H4*W2 above
+ * 2^31 - 1 pixels (VPPX_E_UNSUPPORTED). */
+#define VPPX_MOTION_MAX_CH 64
+#define VPPX_MOTION_MAX_KS 7
+int vppx_raft_motion_front_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
+                                  int64_t coords_frame_stride, const float *flow, int64_t flow_frame_stride, const float *wc,
+                                  const float *bias_c, int Cc, const float *wf, const float *bias_f, int Cf, int ks, int B, int H4,
+                                  int W2, int W3, int levels, int radius, void *out_c, int64_t out_c_frame_stride, void *out_f,
+                                  int64_t out_f_frame_stride, int dtype, int out_dtype);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

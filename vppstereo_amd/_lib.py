@@ -44,10 +44,12 @@ EXPORTS = [
     "vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev", "vppx_raft_corr_fused_dt_dev",
     "vppx_psmnet_readout_dt_dev", "vppx_raft_upsample_dt_dev",
     "vppx_raft_gru_assemble_dt_dev", "vppx_raft_gru_reset_dt_dev", "vppx_raft_gru_update_dt_dev",
+    "vppx_raft_motion_front_dt_dev",
 ]
 CORR_MAX_LEVELS, CORR_MAX_RADIUS = 4, 8
 DT_F32, DT_BF16 = 0, 1          # VppxDtype
 GRU_MAX_SOURCES = 4
+MOTION_MAX_CH, MOTION_MAX_KS = 64, 7
 GRU_MODES = {"copy": 0, "pool2x": 1, "interp": 2}      # VppxGruMode
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
 FS_METRICS, FS_NO_DISP = 16, 32
@@ -208,6 +210,8 @@ def load():
         lib.vppx_raft_gru_assemble_dt_dev.argtypes = [vp, C.POINTER(VppxGruSource), i, i, i, i, vp, i, i]
         lib.vppx_raft_gru_reset_dt_dev.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, i, i, i, i, i, i]
         lib.vppx_raft_gru_update_dt_dev.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i, i, i, i, i]
+        lib.vppx_raft_motion_front_dt_dev.argtypes = [vp, vp, vp, vp, i64, vp, i64, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, vp, i64, vp, i64,
+                                                      i, i]
         lib.vppx_kitti_disp_decode_dev.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.vppx_pfm_decode_dev.argtypes = [vp, vp, i, i, i, i, vp]
         lib.vppx_png_decode_dev.argtypes = [vp, i, vp, C.POINTER(C.c_int64), i, i, i, f, vp, vp, vp, vp]

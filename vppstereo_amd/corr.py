@@ -9,6 +9,7 @@ float32 where the float32 GEMM is exact; the fused block divides by sqrt(D) with
 device multiplies by a reciprocal.  bfloat16 feature maps give a bfloat16 pyramid (in the fused block every cell of
 level 0 is the float32 result rounded once); the lookup's result is float32 either way, as the reference's `.float()`
 makes it.  `CorrBlock1D.corr` and `Engine.raft_corr` are torch's GEMM in both classes.
+`deferred(coords)` hands the lookup on without running it: `FusedUpdate(block, motion_front=True)` fuses it into convc1.
 """
 from .engine import Engine
 
@@ -38,9 +39,25 @@ class CorrBlock1D:
     def __call__(self, coords):
         return self._eng.raft_corr_lookup(self.corr_pyramid, coords.contiguous(), self.radius)
 
+    def deferred(self, coords):
+        """The lookup at `coords`, not made yet: what `FusedUpdate(block, motion_front=True)` takes as `corr` and fuses
+        into convc1 (vppstereo_amd/update.py); `materialize()` is `self(coords)`."""
+        return DeferredCorr(self, coords)
+
     @staticmethod
     def corr(fmap2, fmap3, hints=None, validhints=None):
         return _engine(fmap2.device).raft_corr(fmap2, fmap3, hints, validhints)
+
+
+class DeferredCorr:
+    """A lookup that has not run: the pyramid, the coordinates and the radius of `CorrBlock1D.deferred(coords)`."""
+
+    def __init__(self, block, coords):
+        self.block, self.pyramid, self.coords, self.radius = block, block.corr_pyramid, coords, block.radius
+
+    def materialize(self):
+        """Today's lookup: float32 [B, levels*(2*radius+1), H4, W2]."""
+        return self.block(self.coords)
 
 
 class CorrBlock1DFused(CorrBlock1D):

@@ -7,7 +7,8 @@
 
 #include <math.h>
 
-// CorrLevels, pool2, store_cells and corr_levels are shared with corr_gemm_kernels.hip: vppx_internal.h
+// CorrLevels, pool2, store_cells and corr_levels are shared with corr_gemm_kernels.hip, corr_tap (one tap of the lookup) with
+// motion_kernels.hip: vppx_internal.h
 
 // One 64-lane wave per (b, y, x2) row, four rows per workgroup; a lane owns 8 consecutive cells of level 0 per trip of
 // 512, which are 4, 2 and 1 cells of levels 1, 2 and 3: every pooled cell is made in the lane's registers from the
@@ -133,19 +134,7 @@ __global__ void __launch_bounds__(256) raft_lookup_kernel(const void *__restrict
         const float *rf = (const float *)(i ? pyr_ : corr_) + base;
         const u16 *rb = (const u16 *)(i ? pyr_ : corr_) + base;
         for (int t = 0; t < taps; t++) {
-            const float x = __fadd_rn((float)(t - radius), xc);
-            const float xg = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, x), wm1), 1.0f);
-            const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(xg, 1.0f), 2.0f), wm1);
-            const float fl = floorf(ix), fl1 = __fadd_rn(fl, 1.0f);
-            const bool in_a = fl >= 0.0f && fl <= wm1, in_b = fl1 >= 0.0f && fl1 <= wm1; // false for NaN
-            float val = 0.0f;
-            if ((in_a || in_b) && isfinite(ix)) {
-                const float wr = __fsub_rn(ix, fl), wl = __fsub_rn(fl1, ix);
-                float a = 0.0f, bb = 0.0f;
-                if (in_a) a = BF16 ? bf16_widen(rb[(int)fl]) : rf[(int)fl];
-                if (in_b) bb = BF16 ? bf16_widen(rb[(int)fl1]) : rf[(int)fl1];
-                val = __fmaf_rn(bb, wr, __fadd_rn(0.0f, __fmul_rn(a, wl)));
-            }
+            const float val = corr_tap<BF16>(rf, rb, wm1, xc, t, radius);
             o[(size_t)(i * taps + t) * plane] = val;
         }
     }

@@ -2744,6 +2744,46 @@ extern "C" int vppx_raft_gru_update_dt_dev(vppx_ctx *ctx, const void *az, int64_
                       out_frame_stride, B, C, H, W, dtype);
 }
 
+// The motion encoder's front (motion_kernels.hip).  Every refusal comes before anything is launched; the lookup's come first.
+extern "C" int vppx_raft_motion_front_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
+                                             int64_t coords_frame_stride, const float *flow, int64_t flow_frame_stride, const float *wc,
+                                             const float *bias_c, int Cc, const float *wf, const float *bias_f, int Cf, int ks, int B,
+                                             int H4, int W2, int W3, int levels, int radius, void *out_c, int64_t out_c_frame_stride,
+                                             void *out_f, int64_t out_f_frame_stride, int dtype, int out_dtype)
+{
+    static const char *who = "vppx_raft_motion_front";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!corr || !coords_x || !flow || !wc || !wf || !out_c || !out_f || (!pyr && levels > 1)) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = corr_shape_ok(who, B, H4, W2, W3, levels, radius, dtype))) return rc;
+    if (coords_frame_stride < (int64_t)H4 * W2) {
+        vppx_set_error("%s: coords_frame_stride %lld is less than one %dx%d plane", who, (long long)coords_frame_stride, H4, W2);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (out_dtype != VPPX_DT_F32 && out_dtype != VPPX_DT_BF16) {
+        vppx_set_error("%s: out_dtype %d is neither VPPX_DT_F32 (0) nor VPPX_DT_BF16 (1)", who, out_dtype);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (Cc <= 0 || Cf <= 0 || ks < 1 || ks % 2 == 0) {
+        vppx_set_error("%s: %d and %d output channels and a %dx%d window: the channels must be positive and the window odd", who, Cc, Cf, ks,
+                       ks);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (Cc % 16 || Cf % 16 || Cc > VPPX_MOTION_MAX_CH || Cf > VPPX_MOTION_MAX_CH || ks > VPPX_MOTION_MAX_KS) {
+        vppx_set_error("%s: %d and %d output channels and a %dx%d window: multiples of 16 up to %d and windows up to %dx%d are built", who,
+                       Cc, Cf, ks, ks, VPPX_MOTION_MAX_CH, VPPX_MOTION_MAX_KS, VPPX_MOTION_MAX_KS);
+        return VPPX_E_UNSUPPORTED;
+    }
+    if ((rc = gru_stride_ok(who, "flow", flow_frame_stride, 2, H4, W2)) || (rc = gru_stride_ok(who, "out_c", out_c_frame_stride, Cc, H4, W2)) ||
+        (rc = gru_stride_ok(who, "out_f", out_f_frame_stride, Cf, H4, W2)))
+        return rc;
+    return motion_front(ctx, corr, pyr, coords_x, coords_frame_stride, flow, flow_frame_stride, wc, bias_c, Cc, wf, bias_f, Cf, ks, B, H4, W2,
+                        W3, levels, radius, out_c, out_c_frame_stride, out_f, out_f_frame_stride, dtype, out_dtype);
+}
+
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)
 {
     int rc;

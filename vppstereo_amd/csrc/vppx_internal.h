@@ -565,6 +565,12 @@ int gru_reset(vppx_ctx *ctx, const void *ar, int64_t sar, const void *cr, int64_
 int gru_update(vppx_ctx *ctx, const void *az, int64_t saz, const void *cz, int64_t scz, const void *aq, int64_t saq, const void *cq,
                int64_t scq, const void *h, int64_t sh, void *out, int64_t so, int B, int C, int H, int W, int dtype);
 
+// motion_kernels.hip: the lookup fused into BasicMotionEncoder's convc1, and convf1 (models/raft_stereo/update.py:80,82)
+int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x, int64_t coords_frame_stride, const float *flow,
+                 int64_t flow_frame_stride, const float *wc, const float *bias_c, int Cc, const float *wf, const float *bias_f, int Cf,
+                 int ks, int B, int H4, int W2, int W3, int levels, int radius, void *out_c, int64_t out_c_frame_stride, void *out_f,
+                 int64_t out_f_frame_stride, int dtype, int out_dtype);
+
 // device functions the hand-off and the correlation kernels share
 // (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)
 __device__ __forceinline__ float modulation(float v, float h, float d, float two_w2)
@@ -624,6 +630,29 @@ __device__ __forceinline__ void store_cells(u16 *p, const u32 *c, int valid, boo
         for (int j = 0; j < N; j++)
             if (j < valid) p[j] = (u16)c[j];
     }
+}
+
+// One tap of the lookup (include/vppx.h has the arithmetic): rf / rb point at row n of the level (float32 / bfloat16), wm1 is
+// (float)(W - 1) of the level, xc = c / 2^i.  Both cells are loaded per position, since floor(ix) of neighbouring positions
+// need not differ by one after the round trip through the normalised coordinate; a cell outside [0, W-1] is +0, compared
+// in float so that 1e30 is outside and not an index; a position that is not finite gives +0.
+template <bool BF16>
+__device__ __forceinline__ float corr_tap(const float *rf, const u16 *rb, float wm1, float xc, int t, int radius)
+{
+    const float x = __fadd_rn((float)(t - radius), xc);
+    const float xg = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, x), wm1), 1.0f);
+    const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(xg, 1.0f), 2.0f), wm1);
+    const float fl = floorf(ix), fl1 = __fadd_rn(fl, 1.0f);
+    const bool in_a = fl >= 0.0f && fl <= wm1, in_b = fl1 >= 0.0f && fl1 <= wm1; // false for NaN
+    float val = 0.0f;
+    if ((in_a || in_b) && isfinite(ix)) {
+        const float wr = __fsub_rn(ix, fl), wl = __fsub_rn(fl1, ix);
+        float a = 0.0f, bb = 0.0f;
+        if (in_a) a = BF16 ? bf16_widen(rb[(int)fl]) : rf[(int)fl];
+        if (in_b) bb = BF16 ? bf16_widen(rb[(int)fl1]) : rf[(int)fl1];
+        val = __fmaf_rn(bb, wr, __fadd_rn(0.0f, __fmul_rn(a, wl)));
+    }
+    return val;
 }
 
 static inline CorrLevels corr_levels(const void *pyr, size_t nrows, int W3, int levels, int dtype, const void *corr)

@@ -655,6 +655,20 @@ class Engine:
         float32 [B,2,H4,W2] (channel 0 is read, as the reference does) or [B,H4,W2].  -> float32
         [B, levels*(2*radius+1), H4, W2]."""
         torch = self.torch
+        _, dt, levels, N, W3, B, ch, H4, W2 = self._chk_pyramid(pyramid, coords)
+        shape = (B, levels * (2 * int(radius) + 1), H4, W2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            self._chk(out, torch.float32, 4, "out", shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_corr_lookup_dt_dev(self.ctx.handle, _ptr(pyramid[0]), _ptr(pyramid[1]) if levels > 1 else None,
+                                                         _ptr(coords), ch * H4 * W2, B, H4, W2, W3, levels, int(radius), _ptr(out), dt))
+        return out
+
+    def _chk_pyramid(self, pyramid, coords):
+        """What raft_corr_lookup checks of its pyramid and coordinates -> (dtype, dt, levels, N, W3, B, ch, H4, W2)."""
+        torch = self.torch
         levels = len(pyramid)
         if levels < 1:
             raise ValueError("pyramid: no levels")
@@ -676,15 +690,54 @@ class Engine:
             self._chk(pyramid[i], dtype, 4, f"pyramid[{i}]", (N, 1, 1, W3 >> i))
             if pyramid[i].data_ptr() != pyramid[1].data_ptr() + off[i] * pyramid[i].element_size():
                 raise ValueError("pyramid: levels 1.. must be the views raft_corr_pyramid returned")
-        shape = (B, levels * (2 * int(radius) + 1), H4, W2)
+        return dtype, dt, levels, N, W3, B, ch, H4, W2
+
+    def raft_motion_front(self, pyramid, coords, flow, convc1_weight, convc1_bias, convf1_weight, convf1_bias, radius=4, out_dtype=None,
+                          out=None):
+        """The front of BasicMotionEncoder.forward (models/raft_stereo/update.py:80,82) in one launch:
+        cor1 = relu(convc1(lookup(pyramid, coords))) and flo1 = relu(convf1(flow)); the tensor of taps between the lookup
+        and convc1 is never written.  `pyramid`, `coords` and `radius` are raft_corr_lookup's; `flow` is float32
+        [B,2,H4,W2]; the weights are float32 [Cc, levels*(2*radius+1), 1, 1] and [Cf, 2, ks, ks], the biases float32 [Cc] /
+        [Cf] or None.  `out_dtype`: torch.float32 (the default) or torch.bfloat16; `out`: a pair of tensors [B,Cc,H4,W2] and
+        [B,Cf,H4,W2] to write, which may be channel slices of one buffer.  -> (cor1, flo1) (include/vppx.h has the
+        arithmetic)."""
+        torch = self.torch
+        _, dt, levels, N, W3, B, ch, H4, W2 = self._chk_pyramid(pyramid, coords)
+        self._chk(flow, torch.float32, 4, "flow", (B, 2, H4, W2))
+        K = levels * (2 * int(radius) + 1)
+        self._chk(convc1_weight, torch.float32, 4, "convc1_weight")
+        Cc = convc1_weight.shape[0]
+        if tuple(convc1_weight.shape[1:]) != (K, 1, 1):
+            raise ValueError(f"convc1_weight: expected [Cc,{K},1,1] for {levels} levels of radius {int(radius)}, got {tuple(convc1_weight.shape)}")
+        self._chk(convf1_weight, torch.float32, 4, "convf1_weight")
+        Cf, cin, ks, kw = convf1_weight.shape
+        if cin != 2 or ks != kw:
+            raise ValueError(f"convf1_weight: expected [Cf,2,ks,ks], got {tuple(convf1_weight.shape)}")
+        if convc1_bias is not None:
+            self._chk(convc1_bias, torch.float32, 1, "convc1_bias", (Cc,))
+        if convf1_bias is not None:
+            self._chk(convf1_bias, torch.float32, 1, "convf1_bias", (Cf,))
         if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            odtype = torch.float32 if out_dtype is None else out_dtype
         else:
-            self._chk(out, torch.float32, 4, "out", shape)
+            if len(out) != 2:
+                raise ValueError("out must be the pair (cor1, flo1)")
+            odtype = out[0].dtype if out_dtype is None else out_dtype
+        if odtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16, not {odtype}")
+        if out is None:
+            out_c = torch.empty((B, Cc, H4, W2), dtype=odtype, device=self.device)
+            out_f = torch.empty((B, Cf, H4, W2), dtype=odtype, device=self.device)
+        else:
+            out_c, out_f = out
+        sc = self._chk_frames(out_c, odtype, "out[0]", (B, Cc, H4, W2))
+        sf = self._chk_frames(out_f, odtype, "out[1]", (B, Cf, H4, W2))
         self._bind_stream()
-        _lib.check(self.lib.vppx_raft_corr_lookup_dt_dev(self.ctx.handle, _ptr(pyramid[0]), _ptr(pyramid[1]) if levels > 1 else None,
-                                                         _ptr(coords), ch * H4 * W2, B, H4, W2, W3, levels, int(radius), _ptr(out), dt))
-        return out
+        _lib.check(self.lib.vppx_raft_motion_front_dt_dev(
+            self.ctx.handle, _ptr(pyramid[0]), _ptr(pyramid[1]) if levels > 1 else None, _ptr(coords), ch * H4 * W2, _ptr(flow), 2 * H4 * W2,
+            _ptr(convc1_weight), _ptr(convc1_bias), Cc, _ptr(convf1_weight), _ptr(convf1_bias), Cf, ks, B, H4, W2, W3, levels, int(radius),
+            _ptr(out_c), sc, _ptr(out_f), sf, dt, _lib.DT_BF16 if odtype == torch.bfloat16 else _lib.DT_F32))
+        return out_c, out_f
 
     # ---- the read-out: the networks' output back as a disparity map ----
     @staticmethod

@@ -10,6 +10,11 @@ that buffer, which convq then reads as cat([r*h, x]), and one launch makes the n
 `cat([out, flow])` (:87) becomes two sources of gru08's hx.  The convolutions, their ReLUs, `flow_head`, `mask` and the
 `.25 *` stay torch's.
 
+`FusedUpdate(block, motion_front=True)` also takes the front of the motion encoder (update.py:80,82): given
+`corr = corr_fn.deferred(coords1)` (vppstereo_amd.corr.DeferredCorr) instead of the lookup's result, one launch makes
+relu(convc1(lookup)) and relu(convf1(flow)) (`Engine.raft_motion_front`) and the 36-channel tensor between the lookup and
+convc1 is never written; convc2, convf2 and conv stay torch's.  It is opt-in: README.md has what was measured.
+
 Inference only: the hidden state of a level is overwritten inside a buffer that is reused from call to call, which
 autograd cannot follow.  float32 or bfloat16; a tensor of another dtype than the hidden state's (a convolution's output
 under autocast) is converted to it, and a dtype the kernels do not store (float16) is an error.
@@ -17,7 +22,7 @@ under autocast) is converted to it, and a dtype the kernels do not store (float1
 import torch
 import torch.nn.functional as F
 
-from .corr import _engine
+from .corr import DeferredCorr, _engine
 
 
 def _as(t, dtype):
@@ -79,9 +84,10 @@ class FusedUpdate(torch.nn.Module, GruGlue):
     """A module, so that it can take the block's place as `self.update_block` of a RAFTStereo; the block is its only child
     (`state_dict` keys gain the prefix `block.`: wrap after the weights are loaded)."""
 
-    def __init__(self, block):
+    def __init__(self, block, motion_front=False):
         torch.nn.Module.__init__(self)
         GruGlue.__init__(self)
+        self.motion_front = bool(motion_front)
         for name in ("encoder", "gru08", "gru16", "gru32", "flow_head", "mask", "n_gru_layers"):
             if not hasattr(block, name):
                 raise TypeError(f"FusedUpdate: the block has no {name!r}")
@@ -99,11 +105,27 @@ class FusedUpdate(torch.nn.Module, GruGlue):
     def _motion(self, flow, corr):
         """BasicMotionEncoder.forward (update.py:79-87) up to its last cat: -> (out [B,126,H,W], flow)."""
         enc = self.block.encoder
-        cor = F.relu(enc.convc1(corr))
+        if isinstance(corr, DeferredCorr) and self.motion_front:
+            cor, flo = self._front(enc, corr, flow)
+        else:
+            if isinstance(corr, DeferredCorr):
+                corr = corr.materialize()
+            cor, flo = F.relu(enc.convc1(corr)), None
         cor = F.relu(enc.convc2(cor))
-        flo = F.relu(enc.convf1(flow))
+        if flo is None:
+            flo = F.relu(enc.convf1(flow))
         flo = F.relu(enc.convf2(flo))
         return F.relu(enc.conv(torch.cat([cor, flo], dim=1))), flow
+
+    @staticmethod
+    def _front(enc, corr, flow):
+        """relu(convc1(lookup)) and relu(convf1(flow)) in one launch, in flow's dtype (float32 or bfloat16)."""
+        if flow.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"FusedUpdate: flow is {flow.dtype}; the kernels store float32 and bfloat16")
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()        # noqa: E731
+        c1, f1 = enc.convc1, enc.convf1
+        return _engine(flow.device).raft_motion_front(corr.pyramid, corr.coords.contiguous(), flow.float().contiguous(), f32(c1.weight),
+                                                      f32(c1.bias), f32(f1.weight), f32(f1.bias), corr.radius, out_dtype=flow.dtype)
 
     @torch.no_grad()
     def forward(self, net, inp, corr=None, flow=None, iter08=True, iter16=True, iter32=True, update=True):
