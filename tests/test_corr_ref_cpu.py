@@ -187,7 +187,7 @@ def test_new_symbols_are_exported_and_bound():
     i, vp = C.c_int, C.c_void_p
     for name in ("vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev"):
         assert name in _lib.EXPORTS and hasattr(lib, name), name
-    assert lib.vppx_raft_corr_pyramid_cells.argtypes == [C.c_int64, i, i, C.POINTER(C.c_int64)]
+    assert lib.vppx_raft_corr_pyramid_cells.argtypes == [C.c_int64, i, i, vp]     # int64_t *offsets: untyped, as every pointer to a scalar
     assert lib.vppx_raft_corr_pyramid_cells.restype == C.c_int64
     assert lib.vppx_raft_corr_pyramid_dt_dev.argtypes == [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
     assert lib.vppx_raft_corr_lookup_dt_dev.argtypes == [vp, vp, vp, vp, C.c_int64, i, i, i, i, i, i, vp, i]

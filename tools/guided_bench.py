@@ -1,8 +1,9 @@
 """--guided timing (test.py:207-223 with the rSGM matcher): ms per call of
 
-  * guided `vppx_rsgm_dev` (compute_rsgm with hints / validhints on a batch), bound through plain ctypes so that the same script
-    times an older library (VPPX_LIB=tools/bin/libvppx_head.so): whole call and its stages (vppx_enable_stage_timing);
-  * `Engine.vpp_rsgm(validhints=...)` against the same call without validhints (needs a library with the guided entry points).
+  * guided `vppx_rsgm_dev` (compute_rsgm with hints / validhints on a batch): whole call and its stages (vppx_enable_stage_timing);
+  * `Engine.vpp_rsgm(validhints=...)` against the same call without validhints.
+
+VPPX_LIB names another build of the library to time; it must export everything include/vppx.h declares.
 
 Default shape 540x960x192, 3 % hints, B = 16; after warm-up, the median of `--iters` timed calls.  Writes one JSON object.
 
@@ -48,18 +49,9 @@ def main():
 
     import torch
     import synth
-    from vppstereo_amd import _lib   # (the parameter structs only: the library is bound below)
-    lib_path = _lib.LIB_PATH
-    lib = C.CDLL(lib_path)
+    from vppstereo_amd import _lib
+    lib_path, lib = _lib.LIB_PATH, _lib.load()
     vp = C.c_void_p
-    lib.vppx_last_error.restype = C.c_char_p
-    lib.vppx_create.argtypes = [C.POINTER(vp), C.c_int]
-    lib.vppx_rsgm_params_default.argtypes = [C.POINTER(_lib.VppxRsgmParams)]
-    lib.vppx_rsgm_dev.argtypes = [vp, C.POINTER(_lib.VppxRsgmParams)] + [C.c_int] * 4 + [vp] * 6
-    lib.vppx_synchronize.argtypes = [vp]
-    lib.vppx_enable_stage_timing.argtypes = [vp, C.c_int]
-    lib.vppx_get_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
-    lib.vppx_stage_name.restype = C.c_char_p
 
     def chk(rc):
         if rc != 0:
@@ -101,16 +93,15 @@ def main():
     res["rsgm_dev_guided_stage_ms"] = {k: float(np.median(v)) for k, v in stages.items() if any(v)}
     res["guided_out_crc"] = int(np.frombuffer(guided_out.tobytes(), np.uint32).astype(np.uint64).sum() % (1 << 32))
 
-    if hasattr(lib, "vppx_occ_vpp_rsgm_guided_dev"):
-        from vppstereo_amd.engine import Engine
-        eng = Engine(0)
-        kw = dict(g_occ="occlusion_heuristic", out=out, seed=3, rsgm_kw=dict(dmax=D))
-        sync = torch.cuda.synchronize
-        res["vpp_rsgm_guided_ms"], res["vpp_rsgm_guided_all_ms"] = _median_ms(
-            lambda: eng.vpp_rsgm(left, right, hints, validhints=valid, **kw), sync, a.iters, a.warmup)
-        res["vpp_rsgm_unguided_ms"], res["vpp_rsgm_unguided_all_ms"] = _median_ms(
-            lambda: eng.vpp_rsgm(left, right, hints, **kw), sync, a.iters, a.warmup)
-        res["guided_over_unguided"] = res["vpp_rsgm_guided_ms"] / res["vpp_rsgm_unguided_ms"]
+    from vppstereo_amd.engine import Engine
+    eng = Engine(0)
+    kw = dict(g_occ="occlusion_heuristic", out=out, seed=3, rsgm_kw=dict(dmax=D))
+    sync = torch.cuda.synchronize
+    res["vpp_rsgm_guided_ms"], res["vpp_rsgm_guided_all_ms"] = _median_ms(
+        lambda: eng.vpp_rsgm(left, right, hints, validhints=valid, **kw), sync, a.iters, a.warmup)
+    res["vpp_rsgm_unguided_ms"], res["vpp_rsgm_unguided_all_ms"] = _median_ms(
+        lambda: eng.vpp_rsgm(left, right, hints, **kw), sync, a.iters, a.warmup)
+    res["guided_over_unguided"] = res["vpp_rsgm_guided_ms"] / res["vpp_rsgm_unguided_ms"]
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

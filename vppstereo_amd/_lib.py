@@ -10,99 +10,32 @@ import threading
 
 import numpy as np
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VPPX_LIB") or os.path.join(_HERE, "libvppx.so")  # VPPX_LIB: experiment builds
 
-VPPX_OK = 0
-ERR_NAMES = {
-    -1: "VPPX_E_INVALID_ARG", -2: "VPPX_E_DMAX_MOD8", -3: "VPPX_E_DMAX_GT256", -4: "VPPX_E_UNIQUENESS",
-    -5: "VPPX_E_WIDTH_MOD16", -6: "VPPX_E_METHOD", -7: "VPPX_E_NO_DEVICE", -8: "VPPX_E_HIP", -9: "VPPX_E_OOM",
-    -10: "VPPX_E_UNSUPPORTED",
-}
-
-# every symbol include/vppx.h declares (tests check that the library exports all of them)
-EXPORTS = [
-    "vppx_version", "vppx_last_error", "vppx_vpp_params_default", "vppx_rsgm_params_default", "vppx_occ_params_default", "vppx_create",
-    "vppx_destroy", "vppx_set_stream", "vppx_set_stream_legacy", "vppx_set_pipeline", "vppx_synchronize", "vppx_status", "vppx_lockstep_failures", "vppx_workspace_bytes", "vppx_device_name", "vppx_srand",
-    "vppx_rand_stream", "vppx_rand_state", "vppx_rand_advance", "vppx_virtual_projection_scan_rnd", "vppx_virtual_projection_scan_max_dist", "vppx_vpp_host",
-    "vppx_vpp_dev", "vppx_vpp_last_draws", "vppx_census5x5", "vppx_cost_census5x5_xyd", "vppx_aggregate", "vppx_aggregate_img", "vppx_match_wta",
-    "vppx_match_wta_right", "vppx_subpixel_refine", "vppx_median3x3", "vppx_rsgm_host", "vppx_rsgm_dev",
-    "vppx_vpp_rsgm_dev", "vppx_rsgm_post_dev", "vppx_occ_vpp_rsgm_dev", "vppx_occ_vpp_rsgm_host", "vppx_inputs_ready_event", "vppx_u8_to_nchw_dev", "vppx_psmnet_cost_volume_dev", "vppx_raft_corr_modulate_dev", "vppx_kitti_disp_decode_dev", "vppx_png_decode_dev", "vppx_pfm_decode_dev", "vppx_occlusion_heuristic_host", "vppx_occlusion_heuristic_dev", "vppx_occlusion_heuristic_full_host", "vppx_occlusion_heuristic_full_dev", "vppx_set_graph_mode", "vppx_graph_replays", "vppx_time_aggregate", "vppx_agg_kernel_ms", "vppx_we_kernel_ms", "vppx_time_aggregate_frames", "vppx_time_aggregate_part", "vppx_uses_vert", "vppx_last_call_parts", "vppx_we_last_pieces", "vppx_wsum_last_pieces", "vppx_wsum_default_route", "vppx_last_routes", "vppx_last_front_routes", "vppx_fused_pixels_per_wave", "vppx_batch_quantum",
-    "vppx_enable_stage_timing", "vppx_get_stage_ms", "vppx_stage_name",
-    "vppx_fstream_create", "vppx_fstream_destroy", "vppx_fstream_push", "vppx_fstream_flush", "vppx_fstream_pop", "vppx_fstream_counts",
-    "vppx_occ_vpp_rsgm_guided_dev", "vppx_occ_vpp_rsgm_guided_host", "vppx_fstream_push_guided",
-    "vppx_scale_params_default", "vppx_scaled_shape", "vppx_scale_table_builds", "vppx_last_front_sets", "vppx_occ_vpp_rsgm_scaled_dev", "vppx_occ_vpp_rsgm_scaled_host",
-    "vppx_fstream_create_scaled",
-    "vppx_eval_params_default", "vppx_guided_metrics_dev", "vppx_guided_metrics_host", "vppx_occ_vpp_rsgm_eval_dev",
-    "vppx_fstream_create_eval", "vppx_fstream_push_eval", "vppx_fstream_pop_eval",
-    "vppx_rsgm_front_dev", "vppx_rsgm_guided_rows_dev", "vppx_rsgm_mid_dev",
-    "vppx_error_colors_dev", "vppx_error_colors_host", "vppx_guided_visualize_dev", "vppx_guided_visualize_host",
-    "vppx_colorize_dev", "vppx_colorize_host", "vppx_finite_max_dev",
-    "vppx_sample_params_default", "vppx_sample_threshold", "vppx_sample_hints_dev", "vppx_sample_hints_host", "vppx_occ_vpp_rsgm_sampled_dev",
-    "vppx_fstream_create_sampled", "vppx_fstream_push_sampled",
-    "vppx_psmnet_cost_volume_dt_dev", "vppx_raft_corr_modulate_dt_dev",
-    "vppx_raft_corr_pyramid_cells", "vppx_raft_corr_pyramid_dt_dev", "vppx_raft_corr_lookup_dt_dev", "vppx_raft_corr_fused_dt_dev",
-    "vppx_psmnet_readout_dt_dev", "vppx_raft_upsample_dt_dev",
-    "vppx_raft_gru_assemble_dt_dev", "vppx_raft_gru_reset_dt_dev", "vppx_raft_gru_update_dt_dev",
-    "vppx_raft_motion_front_dt_dev",
-]
-CORR_MAX_LEVELS, CORR_MAX_RADIUS = 4, 8
-DT_F32, DT_BF16 = 0, 1          # VppxDtype
-GRU_MAX_SOURCES = 4
-MOTION_MAX_CH, MOTION_MAX_KS = 64, 7
-GRU_MODES = {"copy": 0, "pool2x": 1, "interp": 2}      # VppxGruMode
-FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED = 1, 2, 4, 8
-FS_METRICS, FS_NO_DISP = 16, 32
-FS_SAMPLE = 64
+# include/vppx.h is the only description of the C-ABI: the structs, the constants and (in load()) every signature come from it
+with open(os.path.join(_HERE, os.pardir, "include", "vppx.h")) as _f:
+    ABI = _header.parse(_f.read())
+_K = ABI.constants
+VPPX_OK = _K["VPPX_OK"]
+ERR_NAMES = {v: n for n, v in _K.items() if n.startswith("VPPX_E_")}
+EXPORTS = list(ABI.protos)      # every function the header declares, in its order
+CORR_MAX_LEVELS, CORR_MAX_RADIUS = _K["VPPX_CORR_MAX_LEVELS"], _K["VPPX_CORR_MAX_RADIUS"]
+DT_F32, DT_BF16 = _K["VPPX_DT_F32"], _K["VPPX_DT_BF16"]
+GRU_MAX_SOURCES = _K["VPPX_GRU_MAX_SOURCES"]
+MOTION_MAX_CH, MOTION_MAX_KS = _K["VPPX_MOTION_MAX_CH"], _K["VPPX_MOTION_MAX_KS"]
+GRU_MODES = {m: _K["VPPX_GRU_" + m.upper()] for m in ("copy", "pool2x", "interp")}
+FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED, FS_METRICS, FS_NO_DISP, FS_SAMPLE = (
+    _K["VPPX_FS_" + n] for n in ("PATTERNS", "MASK", "GOCC", "GUIDED", "METRICS", "NO_DISP", "SAMPLE"))
 VIZ_KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')  # utils.guided_visualize's dict keys (utils.py:79), VPPX_VIZ_* bit order
-VIZ_ALL = 63
-VIZ_MAX_DILATION = 31
+VIZ_ALL, VIZ_MAX_DILATION = _K["VPPX_VIZ_ALL"], _K["VPPX_VIZ_MAX_DILATION"]
 METRIC_KEYS = ('bad 1.0', 'bad 2.0', 'bad 3.0', 'bad 4.0', 'avgerr', 'rms')  # the reference's dict keys (losses.py:24), VppxMetrics order
 
-
-class VppxVppParams(C.Structure):
-    _fields_ = [
-        ("method", C.c_int32), ("wsize", C.c_int32), ("wsize_agg_x", C.c_int32), ("wsize_agg_y", C.c_int32),
-        ("direction", C.c_int32), ("uniform_color", C.c_int32), ("discard_occluded", C.c_int32),
-        ("interpolate", C.c_int32), ("c", C.c_float), ("c_occ", C.c_float), ("use_distance_patch", C.c_int32),
-        ("use_bilateral_patch", C.c_int32), ("distance_gamma", C.c_double), ("dmin", C.c_float), ("dmax", C.c_float),
-        ("seed", C.c_uint32), ("per_frame_range", C.c_uint32), ("rand_offset", C.c_uint64),
-        ("bilateral_o_xy", C.c_double), ("bilateral_o_i", C.c_double), ("bilateral_th", C.c_double),
-    ]
-
-
-class VppxRsgmParams(C.Structure):
-    _fields_ = [
-        ("dmax", C.c_int32), ("p1", C.c_int32), ("p2min", C.c_int32), ("alpha", C.c_float), ("gamma", C.c_int32),
-        ("uniqueness", C.c_float), ("subpixel", C.c_int32), ("reserved0", C.c_int32),
-    ]
-
-
-class VppxOccParams(C.Structure):
-    _fields_ = [("rx", C.c_int32), ("ry", C.c_int32), ("l", C.c_double), ("g", C.c_double), ("th_conf", C.c_double),
-                ("th_filter", C.c_double)]
-
-
-class VppxScaleParams(C.Structure):
-    _fields_ = [("iscale", C.c_int32), ("oscale", C.c_int32)]
-
-
-class VppxEvalParams(C.Structure):
-    _fields_ = [("gt_scale", C.c_int32), ("reserved0", C.c_int32)]
-
-
-class VppxSampleParams(C.Structure):
-    _fields_ = [("probability", C.c_double), ("seed", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_uint64)]
-
-
-class VppxGruSource(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("frame_stride", C.c_int64), ("C", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
-                ("mode", C.c_int32)]
-
-
-class VppxMetrics(C.Structure):
-    _fields_ = [("bad1", C.c_double), ("bad2", C.c_double), ("bad3", C.c_double), ("bad4", C.c_double), ("avgerr", C.c_double),
-                ("rms", C.c_double), ("n_valid", C.c_double), ("reserved", C.c_double)]
+VppxVppParams, VppxRsgmParams, VppxOccParams = (ABI.structs[n] for n in ("VppxVppParams", "VppxRsgmParams", "VppxOccParams"))
+VppxScaleParams, VppxEvalParams, VppxSampleParams = (ABI.structs[n] for n in ("VppxScaleParams", "VppxEvalParams", "VppxSampleParams"))
+VppxGruSource, VppxMetrics = ABI.structs["VppxGruSource"], ABI.structs["VppxMetrics"]
 
 
 class VppxError(Exception):
@@ -136,155 +69,11 @@ def load():
         except Exception:
             pass
         lib = C.CDLL(LIB_PATH)
-        vp = C.c_void_p
-        lib.vppx_version.restype = C.c_int
-        lib.vppx_last_error.restype = C.c_char_p
-        lib.vppx_device_name.restype = C.c_char_p
-        lib.vppx_device_name.argtypes = [vp]
-        lib.vppx_stage_name.restype = C.c_char_p
-        lib.vppx_stage_name.argtypes = [C.c_int]
-        lib.vppx_workspace_bytes.restype = C.c_size_t
-        lib.vppx_workspace_bytes.argtypes = [vp]
-        lib.vppx_create.argtypes = [C.POINTER(vp), C.c_int]
-        lib.vppx_destroy.argtypes = [vp]
-        lib.vppx_destroy.restype = None
-        lib.vppx_set_stream.argtypes = [vp, vp]
-        lib.vppx_set_stream_legacy.argtypes = [vp]
-        lib.vppx_set_pipeline.argtypes = [vp, C.c_int]
-        lib.vppx_synchronize.argtypes = [vp]
-        lib.vppx_status.argtypes = [vp]
-        lib.vppx_lockstep_failures.argtypes = [vp]
-        lib.vppx_lockstep_failures.restype = C.c_long
-        lib.vppx_srand.argtypes = [vp, C.c_uint32]
-        lib.vppx_rand_state.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-        lib.vppx_rand_advance.argtypes = [vp, C.c_uint64]
-        lib.vppx_rand_stream.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_int64, vp]
-        i, f, d = C.c_int, C.c_float, C.c_double
-        lib.vppx_virtual_projection_scan_rnd.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, f, f, vp, i, i]
-        lib.vppx_virtual_projection_scan_max_dist.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, f, vp, i, i]
-        pv, pr = C.POINTER(VppxVppParams), C.POINTER(VppxRsgmParams)
-        lib.vppx_vpp_params_default.argtypes = [pv]
-        lib.vppx_vpp_params_default.restype = None
-        lib.vppx_rsgm_params_default.argtypes = [pr]
-        lib.vppx_rsgm_params_default.restype = None
-        lib.vppx_vpp_host.argtypes = [vp, pv, i, i, i, i, vp, vp, vp, vp, vp, vp]
-        lib.vppx_vpp_dev.argtypes = [vp, pv, i, i, i, i, vp, vp, vp, vp, vp, vp]
-        lib.vppx_vpp_last_draws.argtypes = [vp, i, C.POINTER(C.c_uint64)]
-        lib.vppx_census5x5.argtypes = [vp, vp, vp, i, i]
-        lib.vppx_cost_census5x5_xyd.argtypes = [vp, vp, vp, vp, i, i, i, i]
-        lib.vppx_aggregate.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, i]
-        lib.vppx_aggregate_img.argtypes = [vp, vp, i, vp, vp, i, i, i, i, i, f, i]
-        lib.vppx_match_wta.argtypes = [vp, vp, vp, i, i, i, f]
-        lib.vppx_match_wta_right.argtypes = [vp, vp, vp, i, i, i, f]
-        lib.vppx_subpixel_refine.argtypes = [vp, vp, vp, i, i, i, i]
-        lib.vppx_median3x3.argtypes = [vp, vp, vp, i, i]
-        lib.vppx_rsgm_host.argtypes = [vp, pr, i, i, i, i, vp, vp, vp, vp, vp, vp]
-        lib.vppx_rsgm_dev.argtypes = [vp, pr, i, i, i, i, vp, vp, vp, vp, vp, vp]
-        lib.vppx_rsgm_post_dev.argtypes = [vp, i, i, i, vp, vp, i, vp]
-        lib.vppx_rsgm_front_dev.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, vp]
-        lib.vppx_rsgm_guided_rows_dev.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        lib.vppx_rsgm_mid_dev.argtypes = [vp, i, i, i, vp, vp, vp, vp]
-        lib.vppx_vpp_rsgm_dev.argtypes = [vp, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        po = C.POINTER(VppxOccParams)
-        lib.vppx_occ_vpp_rsgm_host.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64)]
-        lib.vppx_occ_params_default.argtypes = [po]
-        lib.vppx_occ_params_default.restype = None
-        lib.vppx_occ_vpp_rsgm_dev.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp]
-        lib.vppx_occ_vpp_rsgm_guided_dev.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.vppx_occ_vpp_rsgm_guided_host.argtypes = [vp, po, pv, pr, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                      C.POINTER(C.c_uint64)]
-        lib.vppx_inputs_ready_event.argtypes = [vp, vp]
-        lib.vppx_u8_to_nchw_dev.argtypes = [vp, i, i, i, i, i, vp, vp, i]
-        lib.vppx_psmnet_cost_volume_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
-        lib.vppx_raft_corr_modulate_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i]
-        lib.vppx_psmnet_cost_volume_dt_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
-        lib.vppx_raft_corr_modulate_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i]
-        lib.vppx_raft_corr_pyramid_cells.argtypes = [C.c_int64, i, i, C.POINTER(C.c_int64)]
-        lib.vppx_raft_corr_pyramid_cells.restype = C.c_int64
-        lib.vppx_raft_corr_pyramid_dt_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i]
-        lib.vppx_raft_corr_fused_dt_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, vp, vp, i]
-        lib.vppx_raft_corr_lookup_dt_dev.argtypes = [vp, vp, vp, vp, C.c_int64, i, i, i, i, i, i, vp, i]
-        lib.vppx_psmnet_readout_dt_dev.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, i]
-        lib.vppx_raft_upsample_dt_dev.argtypes = [vp, vp, C.c_int64, vp, i, i, i, i, i, i, i, i, i, i, i, vp, i]
-        i64 = C.c_int64
-        lib.vppx_raft_gru_assemble_dt_dev.argtypes = [vp, C.POINTER(VppxGruSource), i, i, i, i, vp, i, i]
-        lib.vppx_raft_gru_reset_dt_dev.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, i, i, i, i, i, i]
-        lib.vppx_raft_gru_update_dt_dev.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i, i, i, i, i]
-        lib.vppx_raft_motion_front_dt_dev.argtypes = [vp, vp, vp, vp, i64, vp, i64, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, vp, i64, vp, i64,
-                                                      i, i]
-        lib.vppx_kitti_disp_decode_dev.argtypes = [vp, vp, C.c_int64, vp, vp]
-        lib.vppx_pfm_decode_dev.argtypes = [vp, vp, i, i, i, i, vp]
-        lib.vppx_png_decode_dev.argtypes = [vp, i, vp, C.POINTER(C.c_int64), i, i, i, f, vp, vp, vp, vp]
-        lib.vppx_occlusion_heuristic_host.argtypes = [vp, i, i, i, vp, i, i, d, d, d, d, vp]
-        lib.vppx_occlusion_heuristic_dev.argtypes = [vp, i, i, i, vp, i, i, d, d, d, d, vp]
-        lib.vppx_occlusion_heuristic_full_host.argtypes = [vp, i, i, i, vp, i, i, d, d, d, d, vp, vp]
-        lib.vppx_occlusion_heuristic_full_dev.argtypes = [vp, i, i, i, vp, i, i, d, d, d, d, vp, vp]
-        lib.vppx_set_graph_mode.argtypes = [vp, i]
-        lib.vppx_graph_replays.argtypes = [vp]
-        lib.vppx_graph_replays.restype = C.c_long
-        lib.vppx_time_aggregate.argtypes = [vp, i, C.POINTER(C.c_float)]
-        lib.vppx_agg_kernel_ms.argtypes = [vp, i, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-        lib.vppx_we_kernel_ms.argtypes = [vp, i, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-        lib.vppx_time_aggregate_frames.argtypes = [vp]
-        lib.vppx_time_aggregate_part.argtypes = [vp, i, i, C.POINTER(C.c_float)]
-        lib.vppx_uses_vert.argtypes = [vp]
-        lib.vppx_last_call_parts.argtypes = [vp]
-        lib.vppx_we_last_pieces.argtypes = [vp]
-        lib.vppx_wsum_last_pieces.argtypes = [vp]
-        lib.vppx_wsum_default_route.argtypes = [i, i, i, i, i, i]
-        lib.vppx_last_routes.argtypes = [vp, C.c_char_p, i]
-        lib.vppx_last_front_routes.argtypes = [vp, C.c_char_p, i]
-        lib.vppx_fused_pixels_per_wave.argtypes = [vp]
-        lib.vppx_batch_quantum.argtypes = [vp, i, i, i]
-        lib.vppx_enable_stage_timing.argtypes = [vp, i]
-        lib.vppx_get_stage_ms.argtypes = [vp, C.POINTER(C.c_float), i]
-        lib.vppx_fstream_create.argtypes = [vp, po, pv, pr, i, i, i, i, i, i, i, C.POINTER(vp)]
-        lib.vppx_fstream_destroy.argtypes = [vp]
-        lib.vppx_fstream_destroy.restype = None
-        lib.vppx_fstream_push.argtypes = [vp, vp, vp, vp, vp]
-        lib.vppx_fstream_push_guided.argtypes = [vp, vp, vp, vp, vp, vp]
-        lib.vppx_fstream_flush.argtypes = [vp]
-        lib.vppx_fstream_pop.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
-        ps = C.POINTER(VppxScaleParams)
-        lib.vppx_scale_params_default.argtypes = [ps]
-        lib.vppx_scale_params_default.restype = None
-        pi = C.POINTER(C.c_int)
-        lib.vppx_scaled_shape.argtypes = [i, i, ps, pi, pi, pi, pi]
-        lib.vppx_scale_table_builds.argtypes = [vp]
-        lib.vppx_scale_table_builds.restype = C.c_long
-        lib.vppx_last_front_sets.argtypes = [vp, pi, pi]
-        lib.vppx_occ_vpp_rsgm_scaled_dev.argtypes = [vp, po, pv, pr, ps, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.vppx_occ_vpp_rsgm_scaled_host.argtypes = [vp, po, pv, pr, ps, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                      C.POINTER(C.c_uint64)]
-        lib.vppx_fstream_create_scaled.argtypes = [vp, po, pv, pr, ps, i, i, i, i, i, i, i, C.POINTER(vp)]
-        p64 = C.POINTER(C.c_int64)
-        lib.vppx_fstream_counts.argtypes = [vp, p64, p64, p64, p64]
-        pe = C.POINTER(VppxEvalParams)
-        lib.vppx_eval_params_default.argtypes = [pe]
-        lib.vppx_eval_params_default.restype = None
-        lib.vppx_guided_metrics_dev.argtypes = [vp, pe, i, i, i, vp, i, i, vp, vp, vp, vp]
-        lib.vppx_guided_metrics_host.argtypes = [vp, pe, i, i, i, vp, i, i, vp, vp, vp, vp]
-        lib.vppx_occ_vpp_rsgm_eval_dev.argtypes = [vp, po, pv, pr, ps, pe, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.vppx_fstream_create_eval.argtypes = [vp, po, pv, pr, ps, pe, i, i, i, i, i, i, i, C.POINTER(vp)]
-        lib.vppx_fstream_push_eval.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.vppx_fstream_pop_eval.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(VppxMetrics), C.POINTER(C.c_int)]
-        u = C.c_uint
-        for sfx in ("dev", "host"):
-            getattr(lib, "vppx_error_colors_" + sfx).argtypes = [vp, i, i, i, vp, vp, d, i, i, vp]
-            getattr(lib, "vppx_guided_visualize_" + sfx).argtypes = [vp, i, i, i, vp, vp, vp, d, i, u, vp]
-            getattr(lib, "vppx_colorize_" + sfx).argtypes = [vp, i, i, i, vp, vp, vp, i, vp]
-        lib.vppx_finite_max_dev.argtypes = [vp, i, i, i, vp, vp]
-        pm = C.POINTER(VppxSampleParams)
-        lib.vppx_sample_params_default.argtypes = [pm]
-        lib.vppx_sample_params_default.restype = None
-        lib.vppx_sample_threshold.argtypes = [d]
-        lib.vppx_sample_threshold.restype = C.c_uint32
-        lib.vppx_sample_hints_dev.argtypes = [vp, pm, i, i, i, vp, vp, vp, vp]
-        lib.vppx_sample_hints_host.argtypes = [vp, pm, i, i, i, vp, vp, vp, vp]
-        lib.vppx_occ_vpp_rsgm_sampled_dev.argtypes = [vp, po, pv, pr, ps, pe, pm, i, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                      vp, vp, vp, vp]
-        lib.vppx_fstream_create_sampled.argtypes = [vp, po, pv, pr, ps, pe, pm, i, i, i, i, i, i, i, C.POINTER(vp)]
-        lib.vppx_fstream_push_sampled.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+        for name, (restype, argtypes) in ABI.protos.items():
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise ImportError(f"{LIB_PATH} does not export {name}, which include/vppx.h declares: rebuild the library")
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
 
