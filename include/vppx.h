@@ -890,29 +890,61 @@ int vppx_occlusion_heuristic_full_host(vppx_ctx *ctx, int B, int H, int W, const
 int vppx_occlusion_heuristic_full_dev(vppx_ctx *ctx, int B, int H, int W, const float *hints, int rx, int ry, double l,
                                       double g, double th_conf, double th_filter, float *dmap_out, uint8_t *conf_out);
 
-/* ---- measurement helpers (bench.py) ------------------------------------------------------- */
-/* Time `iters` back-to-back launches of the dominant kernel (8-path aggregation) on the
- * context's stream with hipEvents around the kernel only; returns average ms per launch
- * in *ms_out.  Operates on the workspace state left by the last vppx_rsgm_dev call. */
 /* hipGraph replay of vppx_vpp_rsgm_dev: with the mode on, the second call with identical
  * shapes, parameters, pointers and stream is stream-captured and later identical calls launch the instantiated
  * graph (one launch instead of ~40: matters for small batches).  Needs a non-default stream (vppx_set_stream);
- * where capture is not possible the call silently stays on the eager path.  vppx_graph_replays counts launches. */
+ * where capture is not possible the call silently stays on the eager path.  vppx_graph_replays counts launches.
+ * A call made while stage timing is on (vppx_enable_stage_timing) runs eagerly beside the graph: it is no replay, and it neither
+ * becomes the call a later one is compared with nor destroys the graph, so the identical call behind it is replayed again. */
 int vppx_set_graph_mode(vppx_ctx *ctx, int enable);
 long vppx_graph_replays(vppx_ctx *ctx);
+
+/* ---- measurement helpers (bench.py) ------------------------------------------------------- */
+/* The timing helpers RE-LAUNCH the aggregation stage of the last rSGM-bearing call (vppx_rsgm_dev, vppx_vpp_rsgm_dev,
+ * vppx_occ_vpp_rsgm_*) on the library-owned gray / census images, the penalties and the geometry that call left, into the
+ * call's own path volumes, and time the launches with a hipEvent pair on the context's stream; they synchronise.  They change
+ * nothing a later call can see: its outputs, vppx_uses_vert, vppx_fused_pixels_per_wave, vppx_last_call_parts, the graph of
+ * vppx_set_graph_mode (a helper between two replays costs none) and the list of vppx_last_routes (a re-launch names only
+ * kernels the call named) are what they would be without the helper.  A call that ran in parts is re-launched on its LAST
+ * part, a call split over VPPX_SUBSTREAMS on the part of child 0.  Every launch enters the rings of vppx_agg_kernel_ms /
+ * vppx_we_kernel_ms like a call's.
+ * vppx_time_aggregate: `iters` back-to-back runs of the whole stage -- the one launch of all eight paths, or, in the fused
+ * layout, the lock-step launches and the W/E launch in the call's order and on the call's streams; average ms per run in
+ * *ms_out.
+ * Refused, with nothing launched and *ms_out untouched: iters <= 0 or a NULL ms_out (the message names the argument), no such
+ * call on this context yet, or a 3-channel vppx_aggregate_img since, which writes its gray image where the call's lay and may
+ * move that buffer ("call vppx_rsgm_dev first"), all three VPPX_E_INVALID_ARG; a guided last call -- its launch reads hint
+ * rows that stage entries overwrite, and the census layout would be another kernel on other volumes (VPPX_E_UNSUPPORTED).
+ * After vppx_aggregate / vppx_aggregate_img with one channel, which overwrite the penalty table only, the helper uploads the
+ * call's table again (so a graph of that call, which holds no upload of its own, is replayed by the next identical call). */
 int vppx_time_aggregate(vppx_ctx *ctx, int iters, float *ms_out);
-/* Average duration (ms) of the aggregation kernel over the last `last_n` launches the pipeline made
- * on this context, from hipEvent pairs recorded around every launch on its launch stream (ring of
- * 64).  Call after synchronising.  last_n <= 0 resets the launch counter.  n_used may be NULL. */
+/* Average duration (ms) of the aggregation kernel -- the eight-path launch, or the lock-step launches of the fused layout
+ * (one pair around both where a batch runs as whole rounds + a remainder) -- over the last `last_n` of them on this context,
+ * from hipEvent pairs recorded around every one on its launch stream (ring of 64: at most 64 are averaged).  *n_used is
+ * min(last_n, launches since the last reset, 64): a call adds one per PART it ran in, a timing helper one per iteration, a
+ * graph replay none (event records stay out of a captured graph), a guided call none.  A context made with VPPX_SUBSTREAMS > 1
+ * answers with child 0's ring, which holds child 0's share of every split call and nothing of a call too small to split
+ * (fewer than 2 frames per child).  Call after synchronising.  last_n <= 0 resets the launch counter.  n_used may be NULL. */
 int vppx_agg_kernel_ms(vppx_ctx *ctx, int last_n, float *avg_ms, int *n_used);
-/* The same for the W/E launch of the fused layout (line-parallel kernel; the other launch of its aggregation stage). */
+/* The same for the W/E launch of the fused layout (the other launch of its aggregation stage; also when it makes E only,
+ * next to the route "wsum<12>").  The eight-path layout never adds to it. */
 int vppx_we_kernel_ms(vppx_ctx *ctx, int last_n, float *avg_ms, int *n_used);
-/* Frames per launch that vppx_time_aggregate re-runs: vppx_vpp_rsgm_dev splits a batch over
- * internal sub-streams, and the helper times the launches of one part. */
+/* Frames per launch that the timing helpers re-run: the whole batch, the LAST part of a call that ran in parts, child 0's
+ * share of a call split over VPPX_SUBSTREAMS; 0 where they would refuse with "call vppx_rsgm_dev first". */
 int vppx_time_aggregate_frames(vppx_ctx *ctx);
-/* Same for one part of the stage: 1 = horizontal-path line kernel, 2 = the band launches of the
- * vertical/diagonal paths (fast path only). */
+/* vppx_time_aggregate for one of the two kinds of launch of the FUSED layout (vppx_uses_vert() == 3): part 1 = the W/E launch
+ * alone (we12<..>, or paths<..dirs=11 | 10>), on the context's stream even where the call ran it next to an under-filled
+ * lock-step launch; part 2 = the lock-step launches alone (vert3<..> / vert4<..>), the same launches of the same kernels as
+ * the call's.  Part 1 adds to the ring of vppx_we_kernel_ms only, part 2 to that of vppx_agg_kernel_ms only.  (The band
+ * layout of VPPX_VERT=1: its line launch / its band launches.)  Refusals as vppx_time_aggregate's; and a part other than 1 or
+ * 2 (VPPX_E_INVALID_ARG), and the eight-path layout, whose single launch has no parts (VPPX_E_UNSUPPORTED, the message names
+ * the layout). */
 int vppx_time_aggregate_part(vppx_ctx *ctx, int iters, int part, float *ms_out);
+/* The kernel instantiations the LAST timing-helper call launched (vppx_time_aggregate, vppx_time_aggregate_part), as
+ * vppx_last_routes lists a call's: distinct names in launch order, same names, same calling convention.  Empty before the
+ * first helper and after one that refused.  Asked of a context whose last call was split over VPPX_SUBSTREAMS, it answers for
+ * child 0, where the helpers re-launch. */
+int vppx_timing_last_routes(vppx_ctx *ctx, char *buf, int n);
 /* Aggregation layout of the last fused / rsgm call: 0 = all 8 paths in the line-parallel kernel, 3 = N/NW/NE and
  * S/SW/SE fused three at a time in the lock-step kernel + W and E line-parallel (register-window kernel for D = 128 / 192 /
  * 256) (default for D = 128 / 192 from 3 frames per call on; environment VPPX_VERT = 0 / 3 forces a layout), 1 = the round-1
@@ -949,7 +981,8 @@ int vppx_wsum_default_route(int B, int Hp, int Wp, int dmax, int p2max, int nsim
  * volumes,T,spare|nospare,sw4|nosw4,fast|general,lanes per pixel,fullw|partw> and sum_trap<DPL,T,spare|nospare> (fused
  * sum / WTA), sum_wta<DPL,exact|partial,u8|u16> + wta_right_t (materialised sum, then the right view).  Commas inside
  * <> belong to a name.  The list is cleared at the entry of vppx_rsgm_dev / _host, vppx_vpp_rsgm_dev, vppx_occ_vpp_rsgm_*
- * (guided or not) and vppx_aggregate / _img; the timing helpers re-launch the last call's aggregation and add to it.  A
+ * (guided or not) and vppx_aggregate / _img; the timing helpers re-launch the last call's aggregation and add to it -- kernels
+ * the call named already, so the list stays the call's (vppx_timing_last_routes has the helper's own).  A
  * graph replay (vppx_set_graph_mode) launches nothing from the host and reports the routes of the call it captured.  The
  * children of VPPX_SUBSTREAMS keep lists of their own, which are not merged: a call split over them lists nothing.
  * Writes at most n - 1 characters and a NUL to buf (buf may be NULL when n == 0); returns the length of the whole list. */
@@ -975,9 +1008,17 @@ int vppx_last_routes(vppx_ctx *ctx, char *buf, int n);
 int vppx_last_front_routes(vppx_ctx *ctx, char *buf, int n);
 /* Per-stage hipEvent timing of the last vppx_vpp_rsgm_dev/vppx_rsgm_dev call when stage
  * timing is enabled: fills ms[0..n) and returns the number of stages; names via
- * vppx_stage_name(i). */
+ * vppx_stage_name(i).  While it is on, a call runs without cross-call pipelining, sub-streams and graph replay, with the same
+ * results; every stage closes with a mark (an event on the launch stream) and a stage's time is the sum of the intervals that
+ * end in its marks, over all parts of a call that ran in parts.  The table of marks grows with the call: none is dropped,
+ * however many parts (vppx_stage_marks counts them).  A stage the call did not run is 0. */
 int vppx_enable_stage_timing(vppx_ctx *ctx, int enable);
 int vppx_get_stage_ms(vppx_ctx *ctx, float *ms, int max_n);
+/* Marks the last call recorded while stage timing was on, over all its parts (9 to 11 per part of vppx_vpp_rsgm_dev: one more
+ * with the occlusion heuristic, one more where the sum falls back to sum_wta + wta_right_t; one fewer with
+ * VPPX_METHOD_MAXDIST, which draws no random numbers and so has no vpp_rand stage); 0 while
+ * it is off. */
+int vppx_stage_marks(vppx_ctx *ctx);
 const char *vppx_stage_name(int i);
 
 /* ---- environment ------------------------------------------------------------------------------

@@ -151,7 +151,8 @@ def _env_engine(**env):
 def _vpp_oracle_kw(v):
     """VppxVppParams fields -> the oracle's keywords."""
     return dict(wsize=v["wsize"], left2right=bool(v["direction"]), blending=v["c"], uniform_color=bool(v["uniform_color"]), c_occ=v["c_occ"],
-                discard_occ=bool(v["discard_occluded"]), interpolate=bool(v["interpolate"])) if v else {}
+                discard_occ=bool(v["discard_occluded"]), interpolate=bool(v["interpolate"]),
+                method="maxDistance" if v.get("method") else "rnd") if v else {}
 
 
 def _oracle(s, d, f):

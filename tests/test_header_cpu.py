@@ -129,7 +129,7 @@ def test_constants_are_the_headers():
 
 # entry points that take a handle and return int, by what they answer to a NULL handle with every other argument NULL / zero
 ZERO = {"vppx_uses_vert", "vppx_batch_quantum", "vppx_last_call_parts", "vppx_we_last_pieces", "vppx_wsum_last_pieces",
-        "vppx_fused_pixels_per_wave", "vppx_time_aggregate_frames"}                 # queries: 0 without a context
+        "vppx_fused_pixels_per_wave", "vppx_time_aggregate_frames", "vppx_stage_marks"}                 # queries: 0 without a context
 INVALID_ARG = {"vppx_fstream_push", "vppx_fstream_push_guided", "vppx_fstream_push_eval", "vppx_fstream_push_sampled", "vppx_fstream_flush",
                "vppx_fstream_pop", "vppx_fstream_pop_eval", "vppx_fstream_counts",                       # "stream is NULL"
                "vppx_set_graph_mode", "vppx_enable_stage_timing", "vppx_get_stage_ms", "vppx_last_front_sets",
@@ -141,7 +141,7 @@ def test_null_handle_sweep():
     lib = _lib.load()
     swept = [(name, params) for ret, name, params in DECLARED
              if ret == "int" and re.fullmatch(r"(const )?vppx_ctx \*\w+|vppx_fstream \*\w+", params[0])]
-    assert len(swept) == 99
+    assert len(swept) == 101
     seen = {0: set(), -1: set(), -7: set()}
     for name, _ in swept:
         fn = getattr(lib, name)
@@ -152,7 +152,7 @@ def test_null_handle_sweep():
             assert lib.vppx_last_error(), name
             if rc == -7:
                 assert b"context is NULL" in lib.vppx_last_error(), name
-    assert seen[0] == ZERO and seen[-1] == INVALID_ARG and len(seen[-7]) == 78
+    assert seen[0] == ZERO and seen[-1] == INVALID_ARG and len(seen[-7]) == 79
 
 
 def test_a_function_the_library_lacks_is_named(monkeypatch):

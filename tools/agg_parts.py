@@ -15,5 +15,6 @@ r = torch.from_numpy(np.ascontiguousarray(b["right"][idx])).to(dev)
 h = torch.from_numpy(np.ascontiguousarray(b["hints"][idx])).to(dev)
 eng.vpp_rsgm(l, r, h, rsgm_kw=dict(dmax=D))
 torch.cuda.synchronize()
-print("B", B, "vert", eng.uses_vert(), "all", round(eng.time_aggregate(3), 3), "horiz", round(eng.time_aggregate_part(1, 3), 3),
-      "vert-bands", round(eng.time_aggregate_part(2, 3), 3))
+print("B", B, "vert", eng.uses_vert(), "all", round(eng.time_aggregate(3), 3))
+if eng.uses_vert() == 3:    # only the fused layout has parts (the eight paths are one launch: the library refuses)
+    print("   W/E", round(eng.time_aggregate_part(1, 3), 3), "lock-step", round(eng.time_aggregate_part(2, 3), 3), "launched", eng.timing_last_routes())

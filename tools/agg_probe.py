@@ -15,8 +15,9 @@ out = torch.empty((B, H, W), dtype=torch.float32, device=eng.device)
 for _ in range(2):
     eng.vpp_rsgm(l, r, h, g_occ="occlusion_heuristic", out=out, rsgm_kw=dict(dmax=D))
 torch.cuda.synchronize()
-res = dict(shape=(B, H, W, D), layout=eng.uses_vert(), agg_all=round(eng.time_aggregate(10), 3), we=round(eng.time_aggregate_part(1, 10), 3),
-           vert=round(eng.time_aggregate_part(2, 10), 3))
+res = dict(shape=(B, H, W, D), layout=eng.uses_vert(), agg_all=round(eng.time_aggregate(10), 3))
+if eng.uses_vert() == 3:    # only the fused layout has parts (the eight paths are one launch: the library refuses)
+    res.update(we=round(eng.time_aggregate_part(1, 10), 3), vert=round(eng.time_aggregate_part(2, 10), 3))
 n = 10
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(n):

@@ -43,6 +43,7 @@ void route_note(vppx_ctx *ctx, const char *fmt, ...)
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     note_once(ctx->routes, buf);
+    if (ctx->timing_run) note_once(ctx->timing_routes, buf);
 }
 
 void front_route_note(vppx_ctx *ctx, const char *fmt, ...)
@@ -73,6 +74,11 @@ static int routes_to_buf(const char *who, vppx_ctx *ctx, const std::vector<std::
 }
 
 extern "C" int vppx_last_routes(vppx_ctx *ctx, char *buf, int n) { return routes_to_buf("vppx_last_routes", ctx, &vppx_ctx::routes, buf, n); }
+extern "C" int vppx_timing_last_routes(vppx_ctx *ctx, char *buf, int n)
+{
+    if (ctx && !ctx->have_last && ctx->sub[0] && ctx->sub[0]->have_last) ctx = ctx->sub[0]; // the context the helpers re-launch on
+    return routes_to_buf("vppx_timing_last_routes", ctx, &vppx_ctx::timing_routes, buf, n);
+}
 extern "C" int vppx_last_front_routes(vppx_ctx *ctx, char *buf, int n)
 {
     return routes_to_buf("vppx_last_front_routes", ctx, &vppx_ctx::front_routes, buf, n);
@@ -286,8 +292,7 @@ extern "C" void vppx_destroy(vppx_ctx *ctx)
     }
     for (int i = 0; i < WS_NUM; i++)
         if (ctx->ws[i].p) (void)hipFree(ctx->ws[i].p);
-    if (ctx->ev_created)
-        for (int i = 0; i <= VPPX_MAX_STAGES; i++) (void)hipEventDestroy(ctx->ev[i]);
+    for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
     if (ctx->agg_ev_created)
         for (int j = 0; j < 2; j++)
@@ -470,17 +475,30 @@ static const char *k_stage_names[ST_COUNT] = {"vpp_compact", "vpp_rand", "vpp_ap
 
 extern "C" const char *vppx_stage_name(int i) { return (i >= 0 && i < ST_COUNT) ? k_stage_names[i] : ""; }
 
+// the table of marks grows with the call: events for marks 0..n exist after this (a call in parts makes 10 or 11 marks per part)
+static int stage_events(vppx_ctx *ctx, size_t n)
+{
+    if (ctx->ev.size() > n) return 0; // (the usual mark: nothing to create, no device switch)
+    DevGuard dev_guard_(ctx->device);
+    while (ctx->ev.size() <= n) {
+        hipEvent_t e;
+        VPPX_HIP(hipEventCreate(&e));
+        ctx->ev.push_back(e);
+    }
+    return 0;
+}
+
 extern "C" int vppx_enable_stage_timing(vppx_ctx *ctx, int enable)
 {
+    int rc;
     if (!ctx) return VPPX_E_INVALID_ARG;
-    if (enable && !ctx->ev_created) {
-        for (int i = 0; i <= VPPX_MAX_STAGES; i++) VPPX_HIP(hipEventCreate(&ctx->ev[i]));
-        ctx->ev_created = true;
-    }
+    if (enable && (rc = stage_events(ctx, 32))) return rc;
     ctx->stage_timing = enable != 0;
     ctx->n_stages = 0;
     return 0;
 }
+
+extern "C" int vppx_stage_marks(vppx_ctx *ctx) { return (ctx && ctx->stage_timing) ? ctx->n_stages : 0; }
 
 void stage_begin(vppx_ctx *ctx)
 {
@@ -492,7 +510,9 @@ void stage_begin(vppx_ctx *ctx)
 
 void stage_mark(vppx_ctx *ctx, int stage)
 {
-    if (!ctx->stage_timing || ctx->capturing || ctx->n_stages >= VPPX_MAX_STAGES) return;
+    if (!ctx->stage_timing || ctx->capturing) return;
+    if (stage_events(ctx, (size_t)ctx->n_stages + 1)) return; // (no event, no mark: vppx_last_error has the reason)
+    ctx->stage_id.resize((size_t)ctx->n_stages + 1);
     ctx->stage_id[ctx->n_stages] = stage;
     ctx->n_stages++;
     (void)hipEventRecord(ctx->ev[ctx->n_stages], ctx->stream);
@@ -836,30 +856,35 @@ static int run_aggregation(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeo
             // more than it hides (NOTEBOOK: 6.1 -> 7.1 ms), next to 78 waves on 128 SIMDs it has the idle ones.
             int whole = 0;
             bool rest_under = false;
-            if (which == 0 && ctx->knobs.we_next && st == ctx->stream && !we_launched) rsgm_vert3_plan(ctx, g.B, g.Wp, g.D, &whole, &rest_under);
+            // (which == 2, the timing helper's "lock-step launches only": the same plan, hence the same kernels, without W/E)
+            if (which != 1 && ctx->knobs.we_next && st == ctx->stream && !we_launched) rsgm_vert3_plan(ctx, g.B, g.Wp, g.D, &whole, &rest_under);
             int r;
             if (!rest_under) {
                 r = rsgm_launch_vert3(ctx, st, g.B, g.Hp, g.Wp, g.D, gl, cl, cr, lut_d, p.p1, sv, (u32 *)gst, ctx->vert3_err, err_dev);
             } else {
                 if (whole > 0 &&
                     (r = rsgm_launch_vert3_range(ctx, st, g.B, 0, whole, g.Hp, g.Wp, g.D, gl, cl, cr, lut_d, p.p1, sv, (u32 *)gst, ctx->vert3_err, err_dev, false))) return r;
-                VPPX_HIP(hipEventRecord(ctx->ev_fork, st));
-                VPPX_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                ctx->stream = ctx->stream2;
-                ctx->we_beside_vert = true;
-                r = launch_we();
-                ctx->we_beside_vert = false;
-                ctx->stream = st;
-                if (r) return r;
-                VPPX_HIP(hipEventRecord(ctx->ev_join, ctx->stream2));
+                if (which == 0) {
+                    VPPX_HIP(hipEventRecord(ctx->ev_fork, st));
+                    VPPX_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+                    ctx->stream = ctx->stream2;
+                    ctx->we_beside_vert = true;
+                    r = launch_we();
+                    ctx->we_beside_vert = false;
+                    ctx->stream = st;
+                    if (r) return r;
+                    VPPX_HIP(hipEventRecord(ctx->ev_join, ctx->stream2));
+                }
                 r = rsgm_launch_vert3_range(ctx, st, g.B, whole, g.B - whole, g.Hp, g.Wp, g.D, gl, cl, cr, lut_d, p.p1, sv, (u32 *)gst, ctx->vert3_err, err_dev, true);
                 // the pair closes behind the last lock-step launch, BEFORE the join: it must not contain W/E's tail
                 if (timed) {
                     VPPX_HIP(hipEventRecord(ctx->agg_ev[1][slot], st));
                     ctx->agg_calls++;
                 }
-                VPPX_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-                we_launched = true;
+                if (which == 0) {
+                    VPPX_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
+                    we_launched = true;
+                }
                 return r;
             }
             if (timed) {
@@ -1096,6 +1121,7 @@ static int rsgm_core(vppx_ctx *ctx, const VppxRsgmParams &p, const RsgmGeom &g, 
     }
     stage_mark(ctx, ST_AGGREGATE);
     ctx->last_B = g.B; ctx->last_Hp = g.Hp; ctx->last_Wp = g.Wp; ctx->last_D = g.D; ctx->last_rp = p; ctx->have_last = true;
+    ctx->last_guided = hints && validhints;
 
     float *dl0, *dl1, *dr0, *dr1;
     if ((rc = ws_get(ctx, WS_DISP_L0, npp, &dl0))) return rc;
@@ -2978,6 +3004,9 @@ extern "C" int vppx_aggregate_img(vppx_ctx *ctx, const uint8_t *img, int channel
     if ((rc = upload(ctx, WS_STAGE_A, img, n * channels, &dimg))) return rc;
     if (channels == 3) {
         u8 *gray;
+        // the gray image goes where the last call's may lie (and a larger one moves the buffer): the timing helpers have nothing
+        // to re-launch on until the next rSGM call
+        ctx->have_last = false;
         if ((rc = ws_get(ctx, WS_GRAY_L, n, &gray))) return rc;
         RsgmGeom g1;
         g1.B = 1; g1.H = g1.Hp = h; g1.W = g1.Wp = w; g1.C = 3; g1.D = dmax;
@@ -3059,39 +3088,76 @@ extern "C" int vppx_median3x3(vppx_ctx *ctx, const float *src, float *dst, int w
 // ---------------------------------------------------------------------------------------
 // measurement helper: time the dominant kernel alone with hipEvents on the launch stream
 // ---------------------------------------------------------------------------------------
+// The event pair around `iters` re-launches.  The events it creates are the caller's to destroy, whatever this returns.
+static int timed_relaunches(vppx_ctx *ctx, const RsgmGeom &g, const u16 *lut_d, int maxp2, int iters, int which, hipEvent_t *e0,
+                            hipEvent_t *e1, float *ms_out)
+{
+    VPPX_HIP(hipEventCreate(e0));
+    VPPX_HIP(hipEventCreate(e1));
+    const void *vols[8];
+    int nvol, eb, rc = 0;
+    // what the call decided stays the call's: a re-launch counts as no call of a context that rests after a lost lock step,
+    // and leaves the W route flag, which rsgm_core reads behind its own run_aggregation, as it found it
+    const int rest = ctx->vert3_rest;
+    const bool wsum = ctx->wsum_route;
+    VPPX_HIP(hipEventRecord(*e0, ctx->stream));
+    ctx->timing_run = true;
+    for (int i = 0; i < iters && rc == 0; i++)
+        rc = run_aggregation(ctx, ctx->last_rp, g, ctx->last_gl, ctx->last_cl, ctx->last_cr, lut_d, maxp2, vols, &nvol, &eb, which);
+    ctx->timing_run = false;
+    ctx->vert3_rest = rest;
+    ctx->wsum_route = wsum;
+    if (rc) return rc;
+    float ms = 0.f;
+    VPPX_HIP(hipEventRecord(*e1, ctx->stream));
+    VPPX_HIP(hipEventSynchronize(*e1));
+    VPPX_HIP(hipEventElapsedTime(&ms, *e0, *e1));
+    *ms_out = ms / (float)iters;
+    return 0;
+}
+
+// which: 0 = the whole aggregation stage of the last call, 1 = its W/E launch alone, 2 = its lock-step launches alone (fused
+// layout only).  Re-launches on the images, the penalties and the geometry the last call left (last_gl / last_cl / last_cr,
+// last_rp); everything that could make that another launch than the call's, or a launch on memory that is no longer the
+// call's, is refused BEFORE anything is queued, with *ms_out untouched.
 static int time_aggregation(vppx_ctx *ctx, int iters, int which, float *ms_out)
 {
     int rc;
     VPPX_ENTER(ctx);
     if (!ctx->have_last && ctx->sub[0] && ctx->sub[0]->have_last) ctx = ctx->sub[0]; // batch was split: time one part
-    if (!ctx->have_last || iters <= 0 || !ms_out) { vppx_set_error("vppx_time_aggregate: call vppx_rsgm_dev first"); return VPPX_E_INVALID_ARG; }
+    ctx->timing_routes.clear();
+    if (iters <= 0) { vppx_set_error("vppx_time_aggregate: iters must be positive (got %d)", iters); return VPPX_E_INVALID_ARG; }
+    if (!ms_out) { vppx_set_error("vppx_time_aggregate: ms_out is NULL"); return VPPX_E_INVALID_ARG; }
+    if (!ctx->have_last) { vppx_set_error("vppx_time_aggregate: call vppx_rsgm_dev first"); return VPPX_E_INVALID_ARG; }
+    if (ctx->last_guided) {
+        // the guided launch reads the hint rows from WS_DSI / WS_GUIDED_MAP, which the stage entries overwrite, and the census
+        // layout is another kernel on other volumes: nothing here would be the call's aggregation
+        vppx_set_error("vppx_time_aggregate: the last call was guided (eight u16 path volumes from the hint rows): its aggregation is not re-launched");
+        return VPPX_E_UNSUPPORTED;
+    }
+    if (which != 0 && ctx->last_vert == 0) {
+        vppx_set_error("vppx_time_aggregate_part: the last call ran the eight-path layout (one launch of all eight paths): it has no part %d", which);
+        return VPPX_E_UNSUPPORTED;
+    }
     const VppxRsgmParams &p = ctx->last_rp;
-    u16 lut_h[256];
-    int maxp2;
-    p2_lut_host(p, lut_h, &maxp2);
+    // the penalty table of the last call: vppx_aggregate / vppx_aggregate_img upload their own (the hot path's rule, rsgm_core)
+    u16 *lut_d;
+    if ((rc = ws_get(ctx, WS_P2LUT, 256, &lut_d))) return rc;
+    if (!ctx->lut_valid || ctx->lut_p2min != p.p2min || ctx->lut_gamma != p.gamma || ctx->lut_alpha != p.alpha) {
+        p2_lut_host(p, ctx->lut_host, &ctx->lut_maxp2);
+        VPPX_HIP(hipMemcpyAsync(lut_d, ctx->lut_host, sizeof(ctx->lut_host), hipMemcpyHostToDevice, ctx->stream));
+        ctx->lut_p2min = p.p2min; ctx->lut_gamma = p.gamma; ctx->lut_alpha = p.alpha;
+        ctx->lut_valid = true;
+    }
+    const int maxp2 = ctx->lut_maxp2;
     RsgmGeom g;
     g.B = ctx->last_B; g.Hp = ctx->last_Hp; g.Wp = ctx->last_Wp; g.D = ctx->last_D;
     g.H = g.Hp; g.W = g.Wp; g.C = 1; g.pad_l = g.pad_r = g.pad_t = g.pad_b = 0;
-    hipEvent_t e0, e1;
-    VPPX_HIP(hipEventCreate(&e0));
-    VPPX_HIP(hipEventCreate(&e1));
-    const u32 *cr = ctx->last_cr;
-    const void *vols[8];
-    int nvol, eb;
-    VPPX_HIP(hipEventRecord(e0, ctx->stream));
-    for (int i = 0; i < iters; i++) {
-        rc = run_aggregation(ctx, p, g, ctx->last_gl, ctx->last_cl, cr,
-                             (const u16 *)ctx->ws[WS_P2LUT].p, maxp2, vols, &nvol, &eb, which);
-        if (rc) return rc;
-    }
-    VPPX_HIP(hipEventRecord(e1, ctx->stream));
-    VPPX_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    VPPX_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *ms_out = ms / (float)iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    rc = timed_relaunches(ctx, g, lut_d, maxp2, iters, which, &e0, &e1, ms_out);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
 }
 
 #ifdef VPPX_EXPERIMENT
@@ -3157,7 +3223,11 @@ extern "C" int vppx_time_aggregate(vppx_ctx *ctx, int iters, float *ms_out) { re
 // part: 1 = horizontal line kernel only, 2 = vertical band launches only
 extern "C" int vppx_time_aggregate_part(vppx_ctx *ctx, int iters, int part, float *ms_out)
 {
-    if (part != 1 && part != 2) { vppx_set_error("part must be 1 or 2"); return VPPX_E_INVALID_ARG; }
+    if (part != 1 && part != 2) {
+        if (ctx) ((!ctx->have_last && ctx->sub[0] && ctx->sub[0]->have_last) ? ctx->sub[0] : ctx)->timing_routes.clear(); // (nothing launched)
+        vppx_set_error("part must be 1 or 2");
+        return VPPX_E_INVALID_ARG;
+    }
     return time_aggregation(ctx, iters, part, ms_out);
 }
 // Average duration of the aggregation kernel over the last `last_n` launches made by the pipeline

@@ -145,7 +145,6 @@ enum WsSlot {
     WS_NUM
 };
 
-#define VPPX_MAX_STAGES 96
 #define VPPX_MAX_DEVICES 64 // power of two: per-device one-time initialisations are indexed by device id
 
 struct vppx_ctx {
@@ -189,6 +188,9 @@ struct vppx_ctx {
     // entry of every such call, appended to by the launchers where the template arguments are known
     std::vector<std::string> routes;
     std::vector<std::string> graph_routes; // those of the captured call: a replay launches nothing from the host and restores them
+    // the names the LAST timing helper launched (vppx_timing_last_routes): its launches are noted here as well as in `routes`
+    std::vector<std::string> timing_routes;
+    bool timing_run = false;       // a timing helper is re-launching the aggregation (route_note)
     // the same for the front stage (occlusion heuristic, VPP, bilateral filling: vppx_last_front_routes), a list of its own so
     // that vppx_last_routes keeps its content: cleared at the entry of every call that can launch a front-stage kernel
     std::vector<std::string> front_routes;
@@ -270,6 +272,7 @@ struct vppx_ctx {
     int last_B = 0, last_Hp = 0, last_Wp = 0, last_D = 0;
     VppxRsgmParams last_rp;
     bool have_last = false;
+    bool last_guided = false;      // ... and it was a guided aggregation (rows and row map in WS_DSI / WS_GUIDED_MAP): the helpers refuse
     // hipEvent pairs around the aggregation kernel of the most recent pipeline calls (ring), recorded
     // on the launch stream: vppx_agg_kernel_ms averages them after the caller's synchronize
     static const int AGG_RING = 64;
@@ -308,10 +311,9 @@ struct vppx_ctx {
     // stage timing
     bool stage_timing = false;
     bool stage_append = false;     // the running call is a later part of a split batch: its marks follow the earlier parts'
-    int n_stages = 0;
-    hipEvent_t ev[VPPX_MAX_STAGES + 1];
-    bool ev_created = false;
-    int stage_id[VPPX_MAX_STAGES];
+    int n_stages = 0;              // marks of the last call (vppx_stage_marks); ev holds n_stages + 1 events or more
+    std::vector<hipEvent_t> ev;    // grows with the marks: a call in many parts loses none (stage_mark)
+    std::vector<int> stage_id;
     size_t total_bytes = 0;
     std::vector<long long> png_offs_host; // kept alive for the asynchronous upload
     // --iscale / --oscale (vppx_occ_vpp_rsgm_scaled_*): shape the tables in WS_SCALE_TAB were computed for, and which set of

@@ -1024,6 +1024,11 @@ class Engine:
         _lib.check(self.lib.vppx_time_aggregate_part(self.ctx.handle, int(iters), int(part), C.byref(ms)))
         return float(ms.value)
 
+    def timing_last_routes(self):
+        """The kernel instantiations the last timing helper (`time_aggregate`, `time_aggregate_part`) launched, named as in
+        `last_routes` (vppx_timing_last_routes); empty after a helper that refused."""
+        return _lib._route_list(self.lib.vppx_timing_last_routes, self.ctx.handle)
+
     def uses_vert(self):
         """Aggregation layout of the last call: 0 = eight line-parallel paths, 1 = band marching (experiment),
         3 = W/E line-parallel + the fused three-path vertical kernel (default from 8 frames per launch on)."""
@@ -1063,6 +1068,10 @@ class Engine:
 
     def enable_stage_timing(self, on=True):
         _lib.check(self.lib.vppx_enable_stage_timing(self.ctx.handle, int(bool(on))))
+
+    def stage_marks(self):
+        """Marks the last call recorded while stage timing was on, over all its parts (vppx_stage_marks)."""
+        return int(self.lib.vppx_stage_marks(self.ctx.handle))
 
     def stage_ms(self):
         arr = (C.c_float * 32)()
