@@ -27,6 +27,7 @@
  *   CorrBlock1D.__init__ pyramid        raft_stereo/corr.py:116-124 vppx_raft_corr_pyramid_dt_dev
  *   CorrBlock1D.__call__                raft_stereo/corr.py:126-145 vppx_raft_corr_lookup_dt_dev
  *   BasicMotionEncoder convc1 / convf1  raft_stereo/update.py:80,82 vppx_raft_motion_front_dt_dev
+ *   ResidualBlock norm / relu / sum     raft_stereo/extractor.py:48-60 vppx_raft_norm_stats_dt_dev, vppx_raft_norm_apply_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -852,6 +853,70 @@ int vppx_raft_motion_front_dt_dev(vppx_ctx *ctx, const void *corr, const void *p
                                   const float *bias_c, int Cc, const float *wf, const float *bias_f, int Cf, int ks, int B, int H4,
                                   int W2, int W3, int levels, int radius, void *out_c, int64_t out_c_frame_stride, void *out_f,
                                   int64_t out_f_frame_stride, int dtype, int out_dtype);
+/* ---- The encoders' glue: what BasicEncoder / MultiBasicEncoder / ResidualBlock.forward run between their convolutions ----
+ * (models/raft_stereo/extractor.py:48-60, :181-183, :276-278): InstanceNorm2d or a frozen BatchNorm2d, the ReLUs and the
+ * residual sum.  Two calls; the convolutions stay the caller's.  dtype (VppxDtype) is the storage of x, res and out;
+ * statistics, weights and biases are float32 always.  Addressing is that of the update block's calls above: a tensor is
+ * [B,C,H,W], frame b starts b * its frame stride cells behind the pointer and is contiguous, so a channel slice of a wider
+ * tensor goes in without a copy.  No pointer has to be aligned beyond its cell: both calls move 16 bytes per lane where
+ * every tensor pointer is 16-byte aligned and every frame stride and H*W a whole number of 16 bytes, and cell by cell
+ * otherwise, with the same bits in every result.
+ *
+ * Why these two calls take the context LAST and no struct: tests/test_header_cpu.py pins the number of prototypes whose
+ * first parameter is the handle and the set of structs of this header, and neither may move for an addition.  Everything
+ * else about them is as everywhere: VPPX_E_NO_DEVICE with "context is NULL" for a NULL context (checked first), the
+ * context's stream, vppx_last_error.
+ *
+ * Statistics:  stats [B][C][2] float32, contiguous, receives (mean, rstd) of every plane of n = H*W cells.  A cell is
+ * widened to float64 (exact); S1 = sum x and S2 = sum x*x (each square exact in float64) are accumulated in float64 in an
+ * order the library chooses, which depends on H*W and on vppx_norm_stats_pieces(B*C, H*W) alone -- never on alignment, the
+ * frame stride or the dtype of the cells; then, in float64,
+ *     mean64 = S1 / n;   var64 = S2 / n - mean64 * mean64, and 0 where that is below 0 (a NaN stays: the biased variance
+ *     F.instance_norm uses);   mean = (float)mean64;   rstd = (float)(1 / sqrt(var64 + (double)eps))
+ * tests/_norm_ref.py derives the bound: n * 2^-53 relative to sum |x| and sum x*x, and the two roundings to float32.
+ * A plane is split over vppx_norm_stats_pieces(B*C, H*W) workgroups, each taking ceil(H*W / pieces) cells rounded up to a
+ * whole number of 16 and the last what is left; with more than one, their partial sums go through the
+ * context's workspace (16 bytes per piece; the call allocates, and waits for the stream first, only while that buffer grows,
+ * which a graph capture refuses) and a second small launch adds
+ * them in piece order.  No float atomic, no dependence on dispatch order: a call repeated gives the same bits.
+ * A NaN cell makes mean and rstd of its plane NaN; an infinite cell makes mean infinite and rstd NaN (inf - inf); either
+ * way the apply call below turns every cell of that plane, and of no other, into NaN.
+ *
+ * Apply:  one launch, float32, one correctly rounded operation per step, per cell of plane (b, c):
+ *     v = (x - mean) * rstd                        (mean, rstd) = stats[b * stats_frame_stride + 2c .. + 1]
+ *     v = v * weight[c] + bias[c]                  when weight is given (bias then has to be)
+ *     v = relu(v)                                  when relu_inner != 0
+ *     when res is given:
+ *         u = res
+ *         u = (u - mean_r) * rstd_r                when res_stats is given; (mean_r, rstd_r) likewise from res_stats
+ *         u = u * res_weight[c] + res_bias[c]      when res_weight is given (only with res_stats; res_bias then has to be)
+ *         v = relu(u + v)
+ *     out = v                                      bfloat16: rounded once, to nearest even; NaN stays NaN
+ * relu(v) = v < 0 ? 0 : v, so a NaN stays NaN as torch's does; the sign of a zero result is not specified.  With neither
+ * res nor relu_inner the call is the plain norm.  ResidualBlock.forward is three such launches around its convolutions:
+ * norm1 + relu;  norm2 + relu + (x +) + relu with res = x; and, where the block has a downsample path, the same with
+ * res = the 1x1 convolution's output and res_stats = norm3's.
+ * stats_frame_stride and res_stats_frame_stride are 2*C or 0; with 0 one set [C][2] serves every frame, which is how a
+ * BatchNorm2d in eval mode goes through the same kernel: the caller fills (running_mean, 1 / sqrt(running_var + eps)) once.
+ * out may be x itself or res itself (the same pointer and frame stride: every cell is read before it is written, by the lane
+ * that writes it) and must not overlap any other argument, nor x or res in any other way.
+ *
+ * Both calls are stream-ordered and never synchronise.  Refused before anything is launched, with no output byte touched:
+ * a NULL x, stats or out; B, C, H or W <= 0; a frame stride below C*H*W; a stats stride other than 0 or 2*C; a dtype other
+ * than the two; eps not finite or <= 0; weight without bias or the reverse (res_weight and res_bias likewise); res_stats or
+ * res_weight without res, res_weight without res_stats (VPPX_E_INVALID_ARG); H*W above 2^31 - 1, or more planes and cells
+ * than one launch takes (VPPX_E_UNSUPPORTED). */
+int vppx_raft_norm_stats_dt_dev(const void *x, int64_t x_frame_stride, int B, int C, int H, int W, double eps, float *stats,
+                                int dtype, vppx_ctx *ctx);
+int vppx_raft_norm_apply_dt_dev(const void *x, int64_t x_frame_stride, const float *stats, int64_t stats_frame_stride,
+                                const float *weight, const float *bias, int relu_inner, const void *res,
+                                int64_t res_frame_stride, const float *res_stats, int64_t res_stats_frame_stride,
+                                const float *res_weight, const float *res_bias, void *out, int64_t out_frame_stride, int B,
+                                int C, int H, int W, int dtype, vppx_ctx *ctx);
+/* Workgroups the statistics call gives to each of `planes` = B*C planes of `cells_per_plane` = H*W cells, without a context
+ * (host arithmetic only): 1 where the planes alone fill the device or a plane is small, more for few large planes.  At
+ * least 1 for any arguments, never above 64, not decreasing in cells_per_plane and not increasing in planes. */
+int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

@@ -2810,6 +2810,74 @@ extern "C" int vppx_raft_motion_front_dt_dev(vppx_ctx *ctx, const void *corr, co
                         W3, levels, radius, out_c, out_c_frame_stride, out_f, out_f_frame_stride, dtype, out_dtype);
 }
 
+// The encoders' glue (norm_kernels.hip).  Flat arguments with the context last (include/vppx.h says why); every refusal
+// comes before anything is launched.
+static int norm_stats_stride_ok(const char *who, const char *what, int64_t stride, int C)
+{
+    if (stride != 0 && stride != 2 * (int64_t)C) {
+        vppx_set_error("%s: %s_frame_stride %lld is neither 0 (one set for every frame) nor 2*C = %d", who, what, (long long)stride, 2 * C);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vppx_raft_norm_stats_dt_dev(const void *x, int64_t x_frame_stride, int B, int C, int H, int W, double eps, float *stats,
+                                           int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_norm_stats";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!x || !stats) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, C, H, W, dtype)) || (rc = gru_stride_ok(who, "x", x_frame_stride, C, H, W))) return rc;
+    if (!(eps > 0.0) || !(eps <= 1.7976931348623157e308)) {
+        vppx_set_error("%s: eps %g is not a positive finite number", who, eps);
+        return VPPX_E_INVALID_ARG;
+    }
+    return norm_stats(ctx, x, x_frame_stride, B, C, H, W, eps, stats, dtype);
+}
+
+extern "C" int vppx_raft_norm_apply_dt_dev(const void *x, int64_t x_frame_stride, const float *stats, int64_t stats_frame_stride,
+                                           const float *weight, const float *bias, int relu_inner, const void *res,
+                                           int64_t res_frame_stride, const float *res_stats, int64_t res_stats_frame_stride,
+                                           const float *res_weight, const float *res_bias, void *out, int64_t out_frame_stride, int B,
+                                           int C, int H, int W, int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_norm_apply";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!x || !stats || !out) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, C, H, W, dtype))) return rc;
+    if ((rc = gru_stride_ok(who, "x", x_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "out", out_frame_stride, C, H, W)) ||
+        (res && (rc = gru_stride_ok(who, "res", res_frame_stride, C, H, W))))
+        return rc;
+    if ((rc = norm_stats_stride_ok(who, "stats", stats_frame_stride, C)) ||
+        (res_stats && (rc = norm_stats_stride_ok(who, "res_stats", res_stats_frame_stride, C))))
+        return rc;
+    if (!weight != !bias || !res_weight != !res_bias) {
+        vppx_set_error("%s: a weight goes with its bias (weight %s, bias %s, res_weight %s, res_bias %s)", who, weight ? "given" : "NULL",
+                       bias ? "given" : "NULL", res_weight ? "given" : "NULL", res_bias ? "given" : "NULL");
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((res_stats || res_weight) && !res) {
+        vppx_set_error("%s: res_stats or res_weight without res", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (res_weight && !res_stats) {
+        vppx_set_error("%s: res_weight without res_stats", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    return norm_apply(ctx, x, x_frame_stride, stats, stats_frame_stride, weight, bias, relu_inner, res, res_frame_stride, res_stats,
+                      res_stats_frame_stride, res_weight, res_bias, out, out_frame_stride, B, C, H, W, dtype);
+}
+
+extern "C" int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane) { return norm_stats_pieces(planes, cells_per_plane); }
+
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)
 {
     int rc;

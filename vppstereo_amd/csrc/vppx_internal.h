@@ -142,6 +142,7 @@ enum WsSlot {
     WS_SAMPLE_V0,
     WS_SAMPLE_G1,
     WS_SAMPLE_V1,
+    WS_NORM_PART,    // vppx_raft_norm_stats: two float64 sums per (plane, piece) of a split plane (norm_kernels.hip)
     WS_NUM
 };
 
@@ -572,6 +573,13 @@ int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *
                  int64_t flow_frame_stride, const float *wc, const float *bias_c, int Cc, const float *wf, const float *bias_f, int Cf,
                  int ks, int B, int H4, int W2, int W3, int levels, int radius, void *out_c, int64_t out_c_frame_stride, void *out_f,
                  int64_t out_f_frame_stride, int dtype, int out_dtype);
+
+// norm_kernels.hip: the encoders' glue (models/raft_stereo/extractor.py:48-60, :181-183, :276-278)
+int norm_stats_pieces(int64_t planes, int64_t cells); // host arithmetic: workgroups per plane
+int norm_stats(vppx_ctx *ctx, const void *x, int64_t sx, int B, int C, int H, int W, double eps, float *stats, int dtype);
+int norm_apply(vppx_ctx *ctx, const void *x, int64_t sx, const float *stats, int64_t sst, const float *weight, const float *bias,
+               int relu_inner, const void *res, int64_t sres, const float *res_stats, int64_t srst, const float *res_weight,
+               const float *res_bias, void *out, int64_t so, int B, int C, int H, int W, int dtype);
 
 // device functions the hand-off and the correlation kernels share
 // (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)

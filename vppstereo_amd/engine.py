@@ -900,6 +900,65 @@ class Engine:
                                                         _ptr(h), sh, _ptr(out), so, B, Cc, H, W, dt))
         return out
 
+    # ---- the encoders' glue: what ResidualBlock.forward runs between its convolutions ----
+    def _norm_dtype(self, t, name):
+        if getattr(t, "dtype", None) not in (self.torch.float32, self.torch.bfloat16):
+            raise TypeError(f"{name} is {getattr(t, 'dtype', type(t))}; the kernels store float32 and bfloat16")
+        return self._handoff_dtype(t)
+
+    def _chk_stats(self, t, name, B, Cc):
+        """A statistics tensor: float32 [B,C,2], or [C,2] / [1,C,2] for one set that serves every frame -> its frame stride."""
+        if getattr(t, "device", None) != self.device or t.dtype != self.torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous float32 tensor on {self.device}")
+        if tuple(t.shape) == (B, Cc, 2) and B > 1:
+            return 2 * Cc
+        if tuple(t.shape) in ((Cc, 2), (1, Cc, 2)):
+            return 0
+        raise ValueError(f"{name}: expected shape {(B, Cc, 2)} or {(Cc, 2)}, got {tuple(t.shape)}")
+
+    def _chk_channel_vec(self, t, name, Cc):
+        if t is not None:
+            self._chk(t, self.torch.float32, 1, name, (Cc,))
+
+    def raft_norm_stats(self, x, eps=1e-5, out=None):
+        """(mean, rstd) of every [H,W] plane of x [B,C,H,W] (float32 or bfloat16; a channel slice goes in as it is), as
+        F.instance_norm takes them: biased variance, rstd = 1 / sqrt(var + eps), from float64 sums (include/vppx.h).
+        -> float32 [B,C,2]; with `out` nothing is allocated."""
+        dtype, dt = self._norm_dtype(x, "x")
+        sx = self._chk_frames(x, dtype, "x")
+        B, Cc, H, W = x.shape
+        if out is None:
+            out = self.torch.empty((B, Cc, 2), dtype=self.torch.float32, device=self.device)
+        else:
+            self._chk(out, self.torch.float32, 3, "out", (B, Cc, 2))
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_norm_stats_dt_dev(_ptr(x), sx, B, Cc, H, W, float(eps), _ptr(out), dt, self.ctx.handle))
+        return out
+
+    def raft_norm_apply(self, x, stats, weight=None, bias=None, relu=True, residual=None, residual_stats=None, residual_weight=None,
+                        residual_bias=None, out=None):
+        """One launch of a ResidualBlock's norm / ReLU / sum lines (extractor.py:51-52, :54-60):
+            v = (x - mean) * rstd [* weight + bias];  relu(v) if `relu`;  with `residual`: relu(u + v), where u is the
+            residual, normalised with `residual_stats` (and `residual_weight`, `residual_bias`) when they are given.
+        `stats` is raft_norm_stats' [B,C,2], or [C,2] for one set that serves every frame (a frozen BatchNorm:
+        (running_mean, 1 / sqrt(running_var + eps))).  `out` may be x or the residual.  -> out [B,C,H,W]."""
+        dtype, dt = self._norm_dtype(x, "x")
+        sx = self._chk_frames(x, dtype, "x")
+        B, Cc, H, W = x.shape
+        sst = self._chk_stats(stats, "stats", B, Cc)
+        self._chk_channel_vec(weight, "weight", Cc), self._chk_channel_vec(bias, "bias", Cc)
+        self._chk_channel_vec(residual_weight, "residual_weight", Cc), self._chk_channel_vec(residual_bias, "residual_bias", Cc)
+        sres = self._chk_frames(residual, dtype, "residual", x.shape) if residual is not None else 0
+        srst = self._chk_stats(residual_stats, "residual_stats", B, Cc) if residual_stats is not None else 0
+        if out is None:
+            out = self.torch.empty(tuple(x.shape), dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", x.shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_norm_apply_dt_dev(_ptr(x), sx, _ptr(stats), sst, _ptr(weight), _ptr(bias), int(bool(relu)),
+                                                        _ptr(residual), sres, _ptr(residual_stats), srst, _ptr(residual_weight),
+                                                        _ptr(residual_bias), _ptr(out), so, B, Cc, H, W, dt, self.ctx.handle))
+        return out
+
     def kitti_disp_decode(self, png_u16):
         """uint16 PNG samples (device tensor, int16/uint16 storage) -> (disp float32, valid uint8), same shape
         (frame_utils.readDispKITTI :66-69)."""
