@@ -48,28 +48,11 @@ from types import SimpleNamespace
 import numpy as np
 
 import _readout_ref as R
-from _handoff_bf16_ref import rne64
+from _referee import (SECOND_ORDER, TINY, U, _ns, _und, band, bf16_bits, bf16_widen, classes, compare, compare_bf16, misses,  # noqa: F401
+                      to_bf16)
 
 F32, F64 = np.float32, np.float64
-U = R.U
-SECOND_ORDER = R.SECOND_ORDER
-TINY = 2.0 ** -126
-classes, compare, bf16_bits, bf16_widen = R.classes, R.compare, R.bf16_bits, R.bf16_widen
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gru_cases.npz")
-
-
-def _und(x):
-    with np.errstate(invalid="ignore"):
-        return np.where(np.abs(x) < TINY, TINY, 0.0)
-
-
-def _ns(value, limit):
-    return SimpleNamespace(value=value, limit=limit)
-
-
-def to_bf16(a):
-    """float32 array -> the nearest bfloat16 values, as float32."""
-    return bf16_widen(bf16_bits(a)).reshape(np.shape(a))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -192,34 +175,6 @@ def update(az, cz, aq, cq, h, exp_ulps=1.0, swap_z=False, q_gate="tanh"):
         v = p1 + p2
         lim = (np.abs(h) + np.abs(q)) * lz + z * lq + U * (2 * np.abs(p1) + np.abs(p2) + np.abs(v)) + _und(p1) + _und(p2) + _und(v)
     return _ns(v, lim * SECOND_ORDER)
-
-
-# ---------------------------------------------------------------------------------------------------
-# comparison of bfloat16 results
-# ---------------------------------------------------------------------------------------------------
-def band(ref):
-    with np.errstate(invalid="ignore", over="ignore"):
-        return rne64(ref.value - ref.limit), rne64(ref.value + ref.limit)
-
-
-def compare_bf16(got32, ref):
-    """got32: the bfloat16 cells as float32 -> (cells outside the band, cells of another class)."""
-    got = np.asarray(got32, F32)
-    lo, hi = band(ref)
-    cg, cr = classes(got), classes(ref.value)
-    fin = cr == 0
-    with np.errstate(invalid="ignore"):
-        # a finite value next to the largest bfloat16 may round to infinity: the band says so
-        miss = fin & ~((got >= lo) & (got <= hi))
-    return int(miss.sum()), int((~fin & (cg != cr)).sum())
-
-
-def misses(got, ref, dtype="float32"):
-    """Cells beyond the limit (outside the band) plus cells of another class."""
-    if dtype == "bfloat16":
-        return sum(compare_bf16(got, ref))
-    _, beyond, other = compare(got, ref)
-    return beyond + other
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ relu(got) lies within the same limit of relu(value).  A padding cell of the flow
 zeros.
 
 bfloat16 outputs: the float32 result is rounded once and rounding is monotone, so a cell lies in
-[rne(value - limit), rne(value + limit)]: band(), as in tests/_gru_ref.py.
+[rne(value - limit), rne(value + limit)]: band() of tests/_referee.py.
 
 Non-finite input follows the arithmetic (numpy's IEEE semantics) and a test compares the class of such a cell.
 """
@@ -30,18 +30,12 @@ from types import SimpleNamespace
 import numpy as np
 
 import _corr_ref as C
-import _gru_ref as G
 import _handoff_bf16_ref as BR
+from _referee import SECOND_ORDER, TINY, U, _ns, band, classes, compare, compare_bf16, misses, to_bf16  # noqa: F401
 
 F32, F64 = np.float32, np.float64
-U, SECOND_ORDER, TINY = G.U, G.SECOND_ORDER, G.TINY
-classes, compare, compare_bf16, band, misses, to_bf16 = G.classes, G.compare, G.compare_bf16, G.band, G.misses, G.to_bf16
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "motion_cases.npz")
 PLANTED = ("tap_order", "flipped", "replicate", "flow_swapped", "no_bias", "no_relu", "taps_bf16")
-
-
-def _ns(value, limit):
-    return SimpleNamespace(value=value, limit=limit)
 
 
 def _relu(v):

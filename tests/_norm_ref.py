@@ -33,33 +33,20 @@ becomes U in the statistics, and the apply's roundings are bounded against the e
 evaluation of x r w - m r w + b in at most 8 operations lies within 8 U ((|x| + |m|) r |w| + |b|) of it.
 
 bfloat16 storage: the inputs are bfloat16 values held as float32, the float32 result is rounded once, and rounding is
-monotone, so a cell lies in [rne(value - limit), rne(value + limit)]: band(), as in tests/_gru_ref.py.
+monotone, so a cell lies in [rne(value - limit), rne(value + limit)]: band() of tests/_referee.py.
 """
 import os
 from types import SimpleNamespace
 
 import numpy as np
 
-import _readout_ref as R
-from _gru_ref import band, compare_bf16, misses, to_bf16  # noqa: F401  (the same comparisons)
+from _referee import (SECOND_ORDER, TINY, U, _ns, _und, band, bf16_bits, bf16_widen, classes, compare, compare_bf16, misses,  # noqa: F401
+                      to_bf16)
 
 F32, F64, LD = np.float32, np.float64, np.longdouble
-U = R.U
 U64 = 2.0 ** -53
-SECOND_ORDER = R.SECOND_ORDER
-TINY = 2.0 ** -126
-classes, compare, bf16_bits, bf16_widen = R.classes, R.compare, R.bf16_bits, R.bf16_widen
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "extractor_cases.npz")
 EPS = 1e-5
-
-
-def _und(x):
-    with np.errstate(invalid="ignore"):
-        return np.where(np.abs(x) < TINY, TINY, 0.0)
-
-
-def _ns(value, limit, **kw):
-    return SimpleNamespace(value=value, limit=limit, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -43,24 +43,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from _referee import SECOND_ORDER, U, bf16_bits, bf16_widen, classes, compare  # noqa: F401
+
 F32, F64 = np.float32, np.float64
-U = 2.0 ** -24
-SECOND_ORDER = 1 + 2.0 ** -10
-
-
-# ---------------------------------------------------------------------------------------------------
-# bfloat16 (the upper 16 bits of a float32), round to nearest even
-# ---------------------------------------------------------------------------------------------------
-def bf16_bits(a):
-    """float32 array -> uint16 bits of the nearest bfloat16 (ties to even; NaN quieted)."""
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    nan = (u & 0x7FFFFFFF) > 0x7F800000
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-    return np.where(nan, ((u >> 16) | 0x40).astype(np.uint16), r)
-
-
-def bf16_widen(bits):
-    return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << 16).view(F32)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -228,29 +213,6 @@ def raft_upsample(flow, mask, f, negate=False, channels=None, crop=None, exp_ulp
     if negate:
         E = -E
     return SimpleNamespace(value=E, limit=lim, z=z, p=p)
-
-
-# ---------------------------------------------------------------------------------------------------
-# comparison
-# ---------------------------------------------------------------------------------------------------
-def classes(a):
-    """0 finite, 1 NaN, 2 +inf, 3 -inf."""
-    a = np.asarray(a)
-    return np.where(np.isnan(a), 1, np.where(np.isposinf(a), 2, np.where(np.isneginf(a), 3, 0)))
-
-
-def compare(got, ref):
-    """-> (worst |got - value| / limit over the finite cells, cells beyond the limit, cells of another class)."""
-    got = np.asarray(got).astype(F64)
-    assert got.shape == ref.value.shape, (got.shape, ref.value.shape)
-    cg, cr = classes(got), classes(ref.value)
-    fin = cr == 0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        dist = np.abs(got - ref.value)
-        beyond = fin & (cg == 0) & ~(dist <= ref.limit)
-        ratio = np.where(fin & (cg == 0) & (ref.limit > 0), dist / np.where(ref.limit > 0, ref.limit, 1.0), 0.0)
-        ratio = np.where(fin & (cg == 0) & (ref.limit == 0) & (dist > 0), np.inf, ratio)
-    return float(ratio.max(initial=0.0)), int(beyond.sum()), int((cg != cr).sum())
 
 
 # ---------------------------------------------------------------------------------------------------

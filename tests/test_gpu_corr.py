@@ -14,13 +14,11 @@ import pytest
 import _corr_ref as CR
 import _handoff_bf16_ref as BR
 import _handoff_ref as R
+from _cells import DTYPES, GUARD, SENTINEL16 as S16, SENTINEL32 as S32
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
-S32, S16 = 0x7FA5A5A5, BR.SENTINEL16         # NaN patterns no kernel here produces
-GUARD = 8
-DTYPES = ["float32", "bfloat16"]
 HERE = os.path.dirname(os.path.abspath(__file__))
 _CASES = {}
 

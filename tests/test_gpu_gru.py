@@ -13,15 +13,13 @@ import numpy as np
 import pytest
 
 import _gru_ref as R
+from _cells import DTYPES, INVALID, SENTINEL16, SENTINEL32, UNSUPPORTED
+from _cells import bits as _bits, dev as _dev, guarded as _guarded, guards_intact as _guards_intact, hold, host as _host, tdtype as _tdtype
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
 DEVICE_EXP_ULPS = 1.0
-SENTINEL32, SENTINEL16 = 0x7FA5A5A5, 0x7FA5      # NaN patterns no kernel here produces
-GUARD = 8                                        # cells in front of and behind an output
-INVALID, UNSUPPORTED = -1, -10
-DTYPES = ("float32", "bfloat16")
 _REFS = {}
 
 
@@ -31,58 +29,6 @@ def eng():
     from vppstereo_amd.engine import Engine
     assert torch.cuda.is_available()
     return Engine()
-
-
-def _tdtype(dtype):
-    import torch
-    return torch.bfloat16 if dtype == "bfloat16" else torch.float32
-
-
-def _dev(eng, a, dtype="float32"):
-    """A host float32 array on the device in the storage type `dtype` (a bfloat16 case holds bfloat16 values)."""
-    import torch
-    a = np.array(a, dtype=F32, order="C", copy=True)
-    if dtype == "bfloat16":
-        assert (a.view(np.uint32) & 0xFFFF == 0).all()
-        return torch.from_numpy((a.view(np.uint32) >> 16).astype(np.uint16).view(np.int16)).to(eng.device).view(torch.bfloat16)
-    return torch.from_numpy(a).to(eng.device)
-
-
-def _host(t):
-    """A device tensor of either dtype as float32 (exact)."""
-    return t.float().cpu().numpy()
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32).cpu().numpy()
-
-
-def _guarded(eng, shape, dtype, shift=0):
-    """(buffer of sentinel cells, view of `shape` that starts GUARD + shift cells into it)."""
-    import torch
-    n = int(np.prod(shape))
-    it, val = (torch.int16, SENTINEL16) if dtype == "bfloat16" else (torch.int32, SENTINEL32)
-    buf = torch.full((n + 2 * GUARD + shift,), val, dtype=it, device=eng.device)
-    return buf, buf[GUARD + shift:GUARD + shift + n].view(_tdtype(dtype)).view(*shape)
-
-
-def _guards_intact(buf, n, shift=0):
-    raw = buf.cpu().numpy()
-    val = SENTINEL16 if raw.dtype == np.int16 else SENTINEL32
-    return bool((raw[:GUARD + shift] == val).all() and (raw[GUARD + shift + n:] == val).all())
-
-
-def _hold(got, ref, what, dtype="float32"):
-    if dtype == "bfloat16":
-        beyond, other = R.compare_bf16(got, ref)
-        worst = float("nan")
-    else:
-        worst, beyond, other = R.compare(got, ref)
-    print(f"{what} [{dtype}]: {got.size} cells ({int((R.classes(ref.value) != 0).sum())} not finite), worst |got - value| / limit "
-          f"{worst:.3f}, {beyond} beyond, {other} of another class")
-    assert other == 0, f"{what}: {other} cells are not of the referee's class"
-    assert beyond == 0, f"{what}: {beyond} cells beyond the limit"
 
 
 # ---- the assembly of hx -------------------------------------------------------------------------------------------------
@@ -128,7 +74,7 @@ def test_assemble_equals_the_referee(eng, name, dtype):
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr() and got.dtype == _tdtype(dtype)
     host = _host(got)
-    _hold(host[:, :c.channels], ref, f"assemble {name}", dtype)
+    hold(R, host[:, :c.channels], ref, f"assemble {name}", dtype)
     assert _guards_intact(buf, int(np.prod(shape)))
     bits = _bits(got)
     if c.hx_channels > c.channels:      # channels behind the sources' are not written
@@ -197,7 +143,7 @@ def test_reset_and_update_equal_the_referee(eng, name, dtype):
     x_before = _bits(hx[:, Cc:])
     assert eng.raft_gru_reset(ar, cr, h, hx) is hx
     torch.cuda.synchronize()
-    _hold(_host(hx[:, :Cc]), ref_r, f"reset {name}", dtype)
+    hold(R, _host(hx[:, :Cc]), ref_r, f"reset {name}", dtype)
     assert np.array_equal(_bits(hx[:, Cc:]), x_before), "reset touched the x part of hx"
     assert _guards_intact(buf, int(np.prod(shape)))
     assert np.array_equal(_bits(h), _bits(d(c.h))), "reset wrote h"
@@ -207,7 +153,7 @@ def test_reset_and_update_equal_the_referee(eng, name, dtype):
     got = eng.raft_gru_update(az, cz, aq, cq, h, out=out)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr()
-    _hold(_host(got), ref_u, f"update {name}", dtype)
+    hold(R, _host(got), ref_u, f"update {name}", dtype)
     assert _guards_intact(buf_o, c.h.size)
     update_bits = _bits(got)
     cls = R.classes(_host(got))
@@ -392,7 +338,7 @@ class _Replay:
         def conv(x):
             import torch
             assert x.dtype == torch.float32 and x.is_contiguous()
-            _hold(_host(x), self.refs[_ref_key(name)], f"{self.call}: the input of {name}")
+            hold(R, _host(x), self.refs[_ref_key(name)], f"{self.call}: the input of {name}")
             self.seen.append(name)
             return _dev(self.eng, self.G[f"{self.call}_{name}_out"])
         return conv
@@ -429,7 +375,7 @@ def test_fused_update_replays_the_recording(eng):
             if f"net{i}" in blk.refs:
                 ref = blk.refs[f"net{i}"]
                 got = _host(net_out[i])
-                _hold(got, ref, f"{call}: net[{i}]")
+                hold(R, got, ref, f"{call}: net[{i}]")
                 assert (np.abs(got.astype(F64) - G[f"{call}_net{i}_out"]) <= 2 * ref.limit).all()   # both lie within the limit of one value
                 assert net_out[i].data_ptr() != net_in[i].data_ptr()
             else:
@@ -505,10 +451,10 @@ def test_fused_update_through_changing_shapes(eng, n_gru_layers):
             hx, rhx, h_new = R.gru_ref(net_h[i], sources, cz, cr, cq, seen[f"{tag}.convz"][1], seen[f"{tag}.convr"][1], seen[f"{tag}.convq"][1],
                                        DEVICE_EXP_ULPS)
             what = f"step {step} {tag}"
-            _hold(seen[f"{tag}.convz"][0], hx, f"{what}: hx", dtype)
+            hold(R, seen[f"{tag}.convz"][0], hx, f"{what}: hx", dtype)
             assert np.array_equal(seen[f"{tag}.convr"][0], seen[f"{tag}.convz"][0])
-            _hold(seen[f"{tag}.convq"][0], rhx, f"{what}: [r*h, x]", dtype)
-            _hold(new[i], h_new, f"{what}: the new state", dtype)
+            hold(R, seen[f"{tag}.convq"][0], rhx, f"{what}: [r*h, x]", dtype)
+            hold(R, new[i], h_new, f"{what}: the new state", dtype)
         assert np.array_equal(seen["flow_head"][0], new[0]) and np.array_equal(seen["mask"][0], new[0])
         assert np.array_equal(_host(delta), seen["flow_head"][1])
         assert np.array_equal(_host(mask), _host((0.25 * _dev(eng, seen["mask"][1], dtype))))
@@ -528,7 +474,7 @@ def test_fused_gru_alone(eng):
     cz, cr, cq = _dev(eng, c.c).split(c.C, dim=1)
     h, x = _dev(eng, c.h), _dev(eng, c.x)
     got = fused_gru(gru, h, cz, cr, cq, x)
-    _hold(_host(got), ref_u, "fused_gru")
+    hold(R, _host(got), ref_u, "fused_gru")
     assert np.array_equal(log[0].view(np.uint32), np.concatenate([c.h, c.x], axis=1).view(np.uint32))
-    _hold(log[1][:, :c.C], R.reset(c.ar, c.cr, c.h, DEVICE_EXP_ULPS), "fused_gru: r*h")
+    hold(R, log[1][:, :c.C], R.reset(c.ar, c.cr, c.h, DEVICE_EXP_ULPS), "fused_gru: r*h")
     assert np.array_equal(log[1][:, c.C:], c.x)

@@ -8,11 +8,11 @@ import pytest
 
 import _handoff_bf16_ref as BR
 import _handoff_ref as R
+from _cells import SENTINEL16 as S16
 
 pytestmark = pytest.mark.gpu
 
 DEVICE_EXP_ULPS = 1.0           # tests/test_gpu_handoff_ref.py's figure, justified there
-S16 = BR.SENTINEL16
 _REFS = {}
 
 

@@ -17,12 +17,12 @@ import numpy as np
 import pytest
 
 import _handoff_ref as R
+from _cells import SENTINEL32 as SENTINEL, sentinels
 
 pytestmark = pytest.mark.gpu
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "frontend_cases.npz"))
 DEVICE_EXP_ULPS = 1.0
-SENTINEL = 0x7FA5A5A5          # a NaN pattern no kernel here produces
 
 
 @pytest.fixture(scope="module")
@@ -36,11 +36,6 @@ def eng():
 def _dev(eng, a):
     import torch
     return torch.from_numpy(np.array(a, order="C", copy=True)).to(eng.device)
-
-
-def _sentinel_words(eng, n):
-    import torch
-    return torch.full((n,), SENTINEL, dtype=torch.int32, device=eng.device)
 
 
 def _hold(got, ref, what):
@@ -161,7 +156,7 @@ def test_psm_volume_equals_the_referee(eng, name):
     # the other kernel at the same W4: a cost pointer one float into a larger buffer takes the scalar kernel
     n = ref.out.size
     for with_hints, want in ((True, got), (False, plain)):
-        buf = _sentinel_words(eng, n + 9)
+        buf = sentinels(eng, n + 9, "float32")
         assert buf.data_ptr() % 16 == 0
         _psm_through_lib(eng, c, buf.data_ptr() + 4, with_hints)
         words = buf.cpu().numpy()
@@ -210,7 +205,7 @@ def test_pfm_payload_one_byte_into_a_tensor_is_refused(eng):
     with pytest.raises(VppxError, match="payload 4-byte aligned") as e:
         eng.pfm_decode(raw[1:], 2, 3, 1, True)
     assert e.value.code == -1
-    out = _sentinel_words(eng, 6)
+    out = sentinels(eng, 6, "float32")
     eng._bind_stream()
     rc = eng.lib.vppx_pfm_decode_dev(eng.ctx.handle, raw.data_ptr() + 1, 2, 3, 1, 1, out.data_ptr())
     eng.torch.cuda.synchronize()
@@ -226,7 +221,7 @@ def test_kitti_decode_sizes_values_and_no_valid(eng, n):
     assert np.array_equal(d.cpu().numpy(), want_d) and np.array_equal(v.cpu().numpy(), want_v)
     # valid = NULL (allowed by the header), outputs one word longer than n
     src = torch.from_numpy(np.concatenate([u16, np.array([7], np.uint16)]).view(np.int16)).to(eng.device)
-    disp = _sentinel_words(eng, n + 1)
+    disp = sentinels(eng, n + 1, "float32")
     eng._bind_stream()
     assert eng.lib.vppx_kitti_disp_decode_dev(eng.ctx.handle, src.data_ptr(), n, disp.data_ptr(), None) == 0
     words = disp.cpu().numpy()
@@ -293,7 +288,7 @@ def _refusal_table(p):
 def test_every_argument_check_of_the_library_refuses_and_writes_nothing(eng):
     from types import SimpleNamespace
     inp = _dev(eng, np.full(4096, 1.0, np.float32))
-    out, out2 = _sentinel_words(eng, 4096), _sentinel_words(eng, 4096)
+    out, out2 = sentinels(eng, 4096, "float32"), sentinels(eng, 4096, "float32")
     rows = _refusal_table(SimpleNamespace(inp=inp.data_ptr(), out=out.data_ptr(), out2=out2.data_ptr()))
     assert len(rows) == 7 + 11 + 8 + 3 + 7
     eng._bind_stream()

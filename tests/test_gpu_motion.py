@@ -13,14 +13,13 @@ import pytest
 import _corr_ref as CR
 import _gru_ref as G
 import _motion_ref as R
+from _cells import DTYPES, INVALID, SENTINEL16, SENTINEL32, UNSUPPORTED
+from _cells import bits as _bits, dev as _dev, guarded as _guarded, guards_intact as _guards_intact, hold, host as _host
+from _cells import tdtype as _tdtype
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
-SENTINEL32, SENTINEL16 = 0x7FA5A5A5, 0x7FA5      # NaN patterns no kernel here produces
-GUARD = 8                                        # cells in front of and behind an output
-INVALID, UNSUPPORTED = -1, -10
-DTYPES = ("float32", "bfloat16")
 _REFS = {}
 
 
@@ -30,44 +29,6 @@ def eng():
     from vppstereo_amd.engine import Engine
     assert torch.cuda.is_available()
     return Engine()
-
-
-def _tdtype(dtype):
-    import torch
-    return torch.bfloat16 if dtype == "bfloat16" else torch.float32
-
-
-def _dev(eng, a):
-    import torch
-    return torch.from_numpy(np.array(a, dtype=F32, order="C", copy=True)).to(eng.device)
-
-
-def _host(t):
-    return t.float().cpu().numpy()
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32).cpu().numpy()
-
-
-def _sentinels(eng, n, dtype):
-    import torch
-    it, val = (torch.int16, SENTINEL16) if dtype == "bfloat16" else (torch.int32, SENTINEL32)
-    return torch.full((n,), val, dtype=it, device=eng.device)
-
-
-def _guarded(eng, shape, dtype, shift=0):
-    """(buffer of sentinel cells, view of `shape` that starts GUARD + shift cells into it)."""
-    n = int(np.prod(shape))
-    buf = _sentinels(eng, n + 2 * GUARD + shift, dtype)
-    return buf, buf[GUARD + shift:GUARD + shift + n].view(_tdtype(dtype)).view(*shape)
-
-
-def _guards_intact(buf, n, shift=0):
-    raw = buf.cpu().numpy()
-    val = SENTINEL16 if raw.dtype == np.int16 else SENTINEL32
-    return bool((raw[:GUARD + shift] == val).all() and (raw[GUARD + shift + n:] == val).all())
 
 
 def _pyramid(eng, levels, shift=0):
@@ -92,18 +53,6 @@ def _pyramid(eng, levels, shift=0):
         pyr[off[i]:off[i] + N * Wi].copy_(up(levels[i]).reshape(-1))
         out.append(pyr[off[i]:off[i] + N * Wi].view(N, 1, 1, Wi))
     return out
-
-
-def _hold(got, ref, what, dtype="float32"):
-    if dtype == "bfloat16":
-        beyond, other = R.compare_bf16(got, ref)
-        worst = float("nan")
-    else:
-        worst, beyond, other = R.compare(got, ref)
-    print(f"{what} [{dtype}]: {got.size} cells ({int((R.classes(ref.value) != 0).sum())} not finite), worst |got - value| / limit "
-          f"{worst:.3f}, {beyond} beyond, {other} of another class")
-    assert other == 0, f"{what}: {other} cells are not of the referee's class"
-    assert beyond == 0, f"{what}: {beyond} cells beyond the limit"
 
 
 def _ref(name, pdtype, nonfinite=False):
@@ -141,8 +90,8 @@ def test_front_equals_the_referee(eng, name, pdtype, odtype):
     got = eng.raft_motion_front(pyr, coords, flow, *w, radius=c.radius, out=(out_c, out_f))
     torch.cuda.synchronize()
     assert got[0].data_ptr() == out_c.data_ptr() and got[1].data_ptr() == out_f.data_ptr() and got[0].dtype == _tdtype(odtype)
-    _hold(_host(out_c), ref_c, f"{name} cor1 (pyramid {pdtype})", odtype)
-    _hold(_host(out_f), ref_f, f"{name} flo1 (pyramid {pdtype})", odtype)
+    hold(R, _host(out_c), ref_c, f"{name} cor1 (pyramid {pdtype})", odtype)
+    hold(R, _host(out_f), ref_f, f"{name} flo1 (pyramid {pdtype})", odtype)
     assert _guards_intact(buf_c, int(np.prod(sc))) and _guards_intact(buf_f, int(np.prod(sf)))
     bits_c, bits_f = _bits(out_c), _bits(out_f)
     # a pixel whose taps are all +0 (a coordinate far outside, infinite or NaN) gives relu(bias) exactly
@@ -220,8 +169,8 @@ def test_front_replays_the_recording(eng, pdtype, odtype):
     got_c, got_f = eng.raft_motion_front(_pyramid(eng, levels), _dev(eng, c.coords2), _dev(eng, c.flow), _dev(eng, c.wc), _dev(eng, c.bias_c),
                                          _dev(eng, c.wf), _dev(eng, c.bias_f), radius=4, out_dtype=_tdtype(odtype))
     torch.cuda.synchronize()
-    _hold(_host(got_c), ref_c, "recording cor1", odtype)
-    _hold(_host(got_f), ref_f, "recording flo1", odtype)
+    hold(R, _host(got_c), ref_c, "recording cor1", odtype)
+    hold(R, _host(got_f), ref_f, "recording flo1", odtype)
     # against the recording itself: both lie within the limit of one value.  flo1 does not depend on the pyramid.
     pairs = [(got_f, flo1, ref_f)] + ([(got_c, cor1, ref_c)] if pdtype == "float32" else [])
     for got, rec, ref in pairs:
@@ -240,8 +189,8 @@ def test_a_nan_and_an_inf_in_the_flow_stay_in_their_windows(eng, odtype):
     got_c, got_f = eng.raft_motion_front(_pyramid(eng, levels), _coords(eng, c), _dev(eng, c.flow), *_weights(eng, c), radius=c.radius,
                                          out_dtype=_tdtype(odtype))
     torch.cuda.synchronize()
-    _hold(_host(got_c), ref_c, "nonfinite flow: cor1", odtype)
-    _hold(_host(got_f), ref_f, "nonfinite flow: flo1", odtype)      # classes: NaN, +inf; -inf is cut by the ReLU
+    hold(R, _host(got_c), ref_c, "nonfinite flow: cor1", odtype)
+    hold(R, _host(got_f), ref_f, "nonfinite flow: flo1", odtype)      # classes: NaN, +inf; -inf is cut by the ReLU
     b, _, y, x = R.NONFINITE_FLOW["nan"]
     nan = np.isnan(_host(got_f))
     want = np.zeros_like(nan)
@@ -341,8 +290,8 @@ def test_one_context_through_changing_shapes(eng):
         h = eng.raft_gru_update(*(_dev(eng, a) for a in (gc.az, gc.cz, gc.aq, gc.cq, gc.h)))
         torch.cuda.synchronize()
         assert CR.same_bits(_host(look), CR.channels_first(R.taps_of(levels, c.coords, c.radius), c.B, c.H4, c.W2)) == 0
-        _hold(_host(got_c), ref_c, f"step {step} {name} cor1", odtype)
-        _hold(_host(got_f), ref_f, f"step {step} {name} flo1", odtype)
+        hold(R, _host(got_c), ref_c, f"step {step} {name} cor1", odtype)
+        hold(R, _host(got_f), ref_f, f"step {step} {name} flo1", odtype)
         assert G.misses(_host(h), gref) == 0
         if step == 0:
             first = (_bits(got_c), _bits(got_f))
@@ -383,7 +332,7 @@ def test_fused_update_with_the_motion_front_replays_the_recording(eng):
         def check(x):
             assert x.dtype == torch.float32 and x.is_contiguous()
             seen[name] = _host(x)
-            _hold(seen[name], ref, f"the input of {name}")
+            hold(R, seen[name], ref, f"the input of {name}")
             assert (np.abs(seen[name].astype(F64) - rec) <= 2 * ref.limit).all()
         return check
 

@@ -13,14 +13,12 @@ import numpy as np
 import pytest
 
 import _norm_ref as N
+from _cells import DTYPES, INVALID, SENTINEL32, UNSUPPORTED
+from _cells import bits as _bits, dev as _dev, guarded as _guarded, guards_intact as _guards_intact, hold, host as _host
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
-SENTINEL32, SENTINEL16 = 0x7FA5A5A5, 0x7FA5      # NaN patterns no kernel here produces
-GUARD = 8
-INVALID, UNSUPPORTED = -1, -10
-DTYPES = ("float32", "bfloat16")
 SPLIT = (1, 2, 200, 201)                         # two planes of 40200 cells: three pieces of 13408, the last with 13384
 
 
@@ -30,54 +28,6 @@ def eng():
     from vppstereo_amd.engine import Engine
     assert torch.cuda.is_available()
     return Engine()
-
-
-def _tdtype(dtype):
-    import torch
-    return torch.bfloat16 if dtype == "bfloat16" else torch.float32
-
-
-def _dev(eng, a, dtype="float32"):
-    import torch
-    a = np.array(a, dtype=F32, order="C", copy=True)
-    if dtype == "bfloat16":
-        assert (a.view(np.uint32) & 0xFFFF == 0).all()
-        return torch.from_numpy((a.view(np.uint32) >> 16).astype(np.uint16).view(np.int16)).to(eng.device).view(torch.bfloat16)
-    return torch.from_numpy(a).to(eng.device)
-
-
-def _host(t):
-    return t.float().cpu().numpy()
-
-
-def _bits(t):
-    import torch
-    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32).cpu().numpy()
-
-
-def _guarded(eng, shape, dtype, shift=0):
-    import torch
-    n = int(np.prod(shape))
-    it, val = (torch.int16, SENTINEL16) if dtype == "bfloat16" else (torch.int32, SENTINEL32)
-    buf = torch.full((n + 2 * GUARD + shift,), val, dtype=it, device=eng.device)
-    return buf, buf[GUARD + shift:GUARD + shift + n].view(_tdtype(dtype)).view(*shape)
-
-
-def _guards_intact(buf, n, shift=0):
-    raw = buf.cpu().numpy()
-    val = SENTINEL16 if raw.dtype == np.int16 else SENTINEL32
-    return bool((raw[:GUARD + shift] == val).all() and (raw[GUARD + shift + n:] == val).all())
-
-
-def _hold(got, ref, what, dtype="float32"):
-    if dtype == "bfloat16":
-        beyond, other = N.compare_bf16(got, ref)
-        worst = float("nan")
-    else:
-        worst, beyond, other = N.compare(got, ref)
-    print(f"{what} [{dtype}]: {got.size} cells, worst |got - value| / limit {worst:.3f}, {beyond} beyond, {other} of another class")
-    assert other == 0, f"{what}: {other} cells are not of the referee's class"
-    assert beyond == 0, f"{what}: {beyond} cells beyond the limit"
 
 
 def _case(name, dtype):
@@ -133,7 +83,7 @@ def test_statistics_and_the_norm_equal_the_referee(eng, name, dtype):
     s = N.stats(x)
     xd = _dev(eng, x, dtype)
     st = _stats(eng, xd)
-    _hold(_host(st), N.stats_value(s), f"stats {name}", "float32")
+    hold(N, _host(st), N.stats_value(s), f"stats {name}", "float32")
     if name == "one":
         assert _host(st)[0, 0, 0] == 3.0 and _host(st)[0, 0, 1] == F32(1 / np.sqrt(1e-5))     # the variance is 0 exactly
     if name == "cancel":
@@ -144,7 +94,7 @@ def test_statistics_and_the_norm_equal_the_referee(eng, name, dtype):
         eng.raft_norm_apply(xd, st, relu=relu, out=out)
         torch.cuda.synchronize()
         assert _guards_intact(buf, x.size)
-        _hold(_host(out), N.apply(x, s, relu_inner=relu), f"apply {name} relu={relu}", dtype)
+        hold(N, _host(out), N.apply(x, s, relu_inner=relu), f"apply {name} relu={relu}", dtype)
     if name in ("nan", "inf"):                 # the whole plane and no other
         got = _host(out)
         bad = np.isnan(got).all(axis=(2, 3))
@@ -200,7 +150,7 @@ def test_split_planes_leave_nothing_behind(eng):
     other = _case("split", "bfloat16")[:, :, :150] * F32(-2)
     assert _pieces(other.shape) not in (1, pieces)
     od = _dev(eng, other, "bfloat16")
-    _hold(_host(_stats(eng, od)), N.stats_value(N.stats(other)), "stats between", "float32")
+    hold(N, _host(_stats(eng, od)), N.stats_value(N.stats(other)), "stats between", "float32")
     _stats(eng, _dev(eng, _case("odd", "float32")))
     assert np.array_equal(_bits(_stats(eng, xd)), first)
 
@@ -252,7 +202,7 @@ def test_apply_every_option(eng, shape, dtype):
         torch.cuda.synchronize()
         assert _guards_intact(buf, a.x.size)
         what = f"apply {shape} affine={affine} relu={relu} residual={rmode} shared={shared}"
-        _hold(_host(out), N.apply(a.x, _given(st), relu_inner=relu, **rkw), what, dtype)
+        hold(N, _host(out), N.apply(a.x, _given(st), relu_inner=relu, **rkw), what, dtype)
         if rmode >= 1 and not shared:
             for target in ("x", "res"):        # out = x, out = res: every cell is read before it is written
                 xs, rs = d.x.clone(), d.res.clone()
@@ -373,6 +323,6 @@ def test_one_context_through_unlike_calls(eng):
         eng.raft_norm_apply(yd, sy, residual=rd, residual_stats=sr, out=out)
         torch.cuda.synchronize()
         assert _guards_intact(buf, y.size)
-        _hold(_host(out), N.apply(y, N.stats(y), res=r, res_stats=N.stats(r, eps=1e-3)), f"plan {k} {shape}", dtype)
+        hold(N, _host(out), N.apply(y, N.stats(y), res=r, res_stats=N.stats(r, eps=1e-3)), f"plan {k} {shape}", dtype)
         seen.add(_pieces(shape))
     assert len(seen) >= 3                      # one piece, and two different splits

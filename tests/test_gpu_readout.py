@@ -12,16 +12,14 @@ import numpy as np
 import pytest
 
 import _readout_ref as R
+from _cells import INVALID, SENTINEL32, UNSUPPORTED, dev as _dev, guarded, guards_intact as _guards_intact, hold
 import synth
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
 DEVICE_EXP_ULPS = 1.0
-SENTINEL = 0x7FA5A5A5          # a NaN pattern no kernel here produces
-GUARD = 8                      # words: the output starts 32 bytes into its buffer
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "readout_cases.npz"))
-INVALID, UNSUPPORTED = -1, -10
 _REFS = {}
 
 
@@ -31,29 +29,6 @@ def eng():
     from vppstereo_amd.engine import Engine
     assert torch.cuda.is_available()
     return Engine()
-
-
-def _dev(eng, a, dtype="float32"):
-    """A host float32 array on the device, in the storage type of the case (the bfloat16 cases hold bfloat16 values)."""
-    import torch
-    a = np.array(a, order="C", copy=True)
-    if dtype == "bfloat16":
-        assert (a.view(np.uint32) & 0xFFFF == 0).all()
-        return torch.from_numpy((a.view(np.uint32) >> 16).astype(np.uint16).view(np.int16)).to(eng.device).view(torch.bfloat16)
-    return torch.from_numpy(a).to(eng.device)
-
-
-def _guarded(eng, shape, shift=0):
-    """(buffer of sentinel words, float32 view of `shape` that starts GUARD + shift words into it)."""
-    import torch
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * GUARD + shift,), SENTINEL, dtype=torch.int32, device=eng.device)
-    return buf, buf[GUARD + shift:GUARD + shift + n].view(torch.float32).view(*shape)
-
-
-def _guards_intact(buf, n, shift=0):
-    raw = buf.cpu().numpy()
-    return bool((raw[:GUARD + shift] == SENTINEL).all() and (raw[GUARD + shift + n:] == SENTINEL).all())
 
 
 def _psm_ref(name):
@@ -68,15 +43,6 @@ def _raft_ref(name):
         c = R.raft_case(name)
         _REFS["raft", name] = (c, R.raft_upsample(c.flow, c.mask, c.f, c.negate, c.channels, c.crop, exp_ulps=DEVICE_EXP_ULPS))
     return _REFS["raft", name]
-
-
-def _hold(got, ref, what):
-    worst, beyond, other = R.compare(got, ref)
-    cls = R.classes(ref.value)
-    print(f"{what}: {got.size} cells ({int((cls != 0).sum())} not finite), worst |got - value| / limit {worst:.3f}, {beyond} beyond, "
-          f"{other} of another class; largest limit {np.nanmax(ref.limit):.2e}")
-    assert other == 0, f"{what}: {other} cells are not of the referee's class"
-    assert beyond == 0, f"{what}: {beyond} cells beyond the limit"
 
 
 def _same(a, b):
@@ -99,11 +65,11 @@ def _raft(eng, c, out=None):
 def test_psm_readout_equals_the_referee(eng, name):
     import torch
     c, ref = _psm_ref(name)
-    buf, out = _guarded(eng, ref.value.shape)
+    buf, out = guarded(eng, ref.value.shape, "float32")
     got = _psm(eng, c, out=out)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr() and got.dtype == torch.float32
-    _hold(got.cpu().numpy(), ref, f"psm {name}")
+    hold(R, got.cpu().numpy(), ref, f"psm {name}")
     assert _guards_intact(buf, ref.value.size)
     # a fresh output and the five-dimensional cost3 give the same bits
     five = _dev(eng, c.cost, c.dtype).unsqueeze(1)
@@ -139,7 +105,7 @@ def test_psm_golden_through_engine_and_drop_in(eng, tag):
     ref = R.psm_readout(cost3[:, 0], D, H, W, exp_ulps=DEVICE_EXP_ULPS)
     assert R.compare(G[f"psm_{tag}_pred"], ref)[1:] == (0, 0)
     got = eng.psmnet_disparity(_dev(eng, cost3), D, (H, W)).cpu().numpy()
-    _hold(got, ref, f"psm golden {tag}")
+    hold(R, got, ref, f"psm golden {tag}")
     drop = psmnet_regress(_dev(eng, cost3), D, (H, W))
     assert drop.shape == G[f"psm_{tag}_pred"].shape and _same(drop.cpu().numpy(), got)
     dist = np.abs(got.astype(F64) - G[f"psm_{tag}_pred"])
@@ -152,15 +118,15 @@ def test_psm_golden_through_engine_and_drop_in(eng, tag):
 def test_raft_upsample_equals_the_referee(eng, name):
     import torch
     c, ref = _raft_ref(name)
-    buf, out = _guarded(eng, ref.value.shape)
+    buf, out = guarded(eng, ref.value.shape, "float32")
     got = _raft(eng, c, out=out)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr()
     host = got.cpu().numpy()
-    _hold(host, ref, f"raft {name}")
+    hold(R, host, ref, f"raft {name}")
     assert _guards_intact(buf, ref.value.size)
     # an output 4 bytes further into a larger buffer takes the float-by-float stores: the same bits
-    buf1, out1 = _guarded(eng, ref.value.shape, shift=1)
+    buf1, out1 = guarded(eng, ref.value.shape, "float32", shift=1)
     assert out1.data_ptr() % 16 == 4
     _raft(eng, c, out=out1)
     torch.cuda.synchronize()
@@ -195,7 +161,7 @@ def test_raft_non_finite_cells_stay_in_their_pixels(eng):
     assert cls[1, 0, 4 + 1, 4 + 2] == 1 and cls[1, 1, 4 * 2, 4 * 3] == 1 and cls[1, 0, 3, 19] == 0
     assert (cls[1] == 1).sum() == 4 and (cls[0, 0] == 0).all() and (cls[0, 1] != 0).sum() == 9 * f * f
     got = eng.raft_upsample(_dev(eng, flow), _dev(eng, mask), 2).cpu().numpy()
-    _hold(got, ref, "raft non-finite")
+    hold(R, got, ref, "raft non-finite")
 
 
 @pytest.mark.parametrize("tag", ["a", "b", "c", "d", "e"])
@@ -206,7 +172,7 @@ def test_raft_golden_through_engine_and_drop_in(eng, tag):
     ref = R.raft_upsample(flow, mask, 2 ** n, exp_ulps=DEVICE_EXP_ULPS)
     assert R.compare(up, ref)[1:] == (0, 0)
     got = eng.raft_upsample(_dev(eng, flow), _dev(eng, mask), n).cpu().numpy()
-    _hold(got, ref, f"raft golden {tag}")
+    hold(R, got, ref, f"raft golden {tag}")
     drop = upsample_flow(_dev(eng, flow), _dev(eng, mask), n_downsample=n)
     assert drop.shape == up.shape and _same(drop.cpu().numpy(), got)
     assert (np.abs(got.astype(F64) - up) <= 2 * ref.limit).all()
@@ -218,7 +184,7 @@ def test_refusals_leave_every_byte_alone(eng):
     from vppstereo_amd._lib import VppxError
     lib, ctx = eng.lib, eng.ctx.handle
     inp = torch.full((8192,), 1.0, dtype=torch.float32, device=eng.device)
-    out = torch.full((8192,), SENTINEL, dtype=torch.int32, device=eng.device)
+    out = torch.full((8192,), SENTINEL32, dtype=torch.int32, device=eng.device)
     p, o = inp.data_ptr(), out.data_ptr()
     eng._bind_stream()
 
@@ -263,13 +229,13 @@ def test_refusals_leave_every_byte_alone(eng):
         text = lib.vppx_last_error().decode()
         assert rc == code and msg in text, (n, rc, code, msg, text)
     torch.cuda.synchronize()
-    assert (out.cpu().numpy() == SENTINEL).all() and (inp.cpu().numpy() == 1.0).all()
+    assert (out.cpu().numpy() == SENTINEL32).all() and (inp.cpu().numpy() == 1.0).all()
     # what is allowed: the smallest of everything, and a window of one pixel in the last corner
     assert psm(D4=1, H4=1, W4=1, maxdisp=1, H=1, W=1, Hout=1, Wout=1) == 0
     assert raft(f=1, mc=9, H4=1, W4=1, stride=1, Hout=1, Wout=1) == 0
     assert raft(top=3, left=5, Hout=1, Wout=1, sign=-1) == 0
     torch.cuda.synchronize()
-    assert (inp.cpu().numpy() == 1.0).all() and (out.cpu().numpy()[1:] == SENTINEL).all()
+    assert (inp.cpu().numpy() == 1.0).all() and (out.cpu().numpy()[1:] == SENTINEL32).all()
 
     # through Engine
     f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=eng.device)            # noqa: E731

@@ -13,7 +13,6 @@ once) and the rate that implies, and for the fused call the matrix rate its time
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -21,29 +20,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vppstereo_amd.engine import Engine  # noqa: E402
-
-
-def timeit(fn, iters, warm=1):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds, iters):
-    for fn in variants.values():
-        timeit(fn, iters=2, warm=2)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+from tools._timing import alternate  # noqa: E402
 
 
 def row(stat, nbytes, flop=None):
@@ -78,7 +55,7 @@ def main():
                         "block": lambda: eng.raft_corr_pyramid(eng.raft_corr(f2, f3), hints, valid, L)}
             if dtype == torch.float32:
                 variants["einsum"] = lambda: torch.einsum('aijk,aijh->ajkh', f2, f3)
-            st = alternate(variants, args.rounds, args.iters)
+            st = alternate(variants, args.rounds, args.iters, warm_iters=2, warm=2)
             feat = (f2.numel() + f3.numel()) * size
             vol = N * W3 * size
             pooled = sum(N * (W3 >> i) for i in range(1, L)) * size

@@ -13,7 +13,6 @@ tensor read or written once) and the rate that implies.  Prints one JSON line.""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -21,29 +20,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vppstereo_amd.engine import Engine  # noqa: E402
-
-
-def timeit(fn, iters, warm=1):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds, iters):
-    for fn in variants.values():
-        timeit(fn, iters=2, warm=2)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+from tools._timing import alternate  # noqa: E402
 
 
 def row(stat, nbytes):
@@ -106,7 +83,7 @@ def main():
                     lv = F.avg_pool2d(lv, [1, 2], stride=[1, 2])
                     pyr.append(lv)
                 return pyr
-            st = alternate({"fused": fused, "modulate_then_avg_pool2d": separate}, args.rounds, args.iters)
+            st = alternate({"fused": fused, "modulate_then_avg_pool2d": separate}, args.rounds, args.iters, warm_iters=2, warm=2)
             vol = N * W3 * size
             case = {"rows_with_a_hint": rows, "rows": N}
             # fused: level 0 read once, hinted rows written back, levels 1..3 written
@@ -121,7 +98,7 @@ def main():
             res = torch.empty((B, L * taps, H4, W2), dtype=torch.float32, device=dev)
             variants = {"kernel": lambda: eng.raft_corr_lookup(pyr, coords, R, out=res)}
             variants["torch_composition"] = lambda: torch_lookup(pyr, coords, R)
-            st = alternate(variants, args.rounds, args.iters)
+            st = alternate(variants, args.rounds, args.iters, warm_iters=2, warm=2)
             # what one lookup has to move: per pixel and level the 128-byte lines its 2r+2 cells lie in (one or two),
             # the coordinate, and the float32 result
             window = sum(min((taps + 1) * size + 64, (W3 >> i) * size) for i in range(L))

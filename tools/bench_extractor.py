@@ -21,7 +21,6 @@ slowest.  Prints one JSON line and writes it to profiles/extractor.json with --w
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -29,32 +28,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from vppstereo_amd.engine import Engine  # noqa: E402
+from tools._timing import alternate  # noqa: E402
 from vppstereo_amd.extractor import FusedEncoder  # noqa: E402
 
 H, W = 544, 960
-
-
-def timeit(fn, iters, warm=1):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds, iters):
-    for fn in variants.values():
-        timeit(fn, iters=2, warm=2)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
 
 
 def row(stat, frames, nbytes=None):
@@ -225,7 +202,7 @@ def main():
                     diff = max(float((p - q).abs().max().item()) for p, q in zip(a, b))
                     del a, b
                     Stand.fresh = False
-                    st = alternate({"fused": lambda: fused(x), "torch_composition": lambda: torch_forward(enc, x)}, args.rounds, args.iters)
+                    st = alternate({"fused": lambda: fused(x), "torch_composition": lambda: torch_forward(enc, x)}, args.rounds, args.iters, warm_iters=2, warm=2)
                 cells, launches = fused_passes(enc, kind == "instance")
                 case = {"images": n, "fused": row(st["fused"], B, cells * size), "torch_composition": row(st["torch_composition"], B),
                         "fused_launches": launches, "torch_MB_counted_not_measured": round(torch_passes(enc, kind == "instance") * size / 1e6, 1),

@@ -19,7 +19,6 @@ multiplied by 32, not a measurement of its own.  Prints one JSON line and writes
 import argparse
 import json
 import os
-import statistics
 import sys
 from types import SimpleNamespace
 
@@ -29,32 +28,10 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from vppstereo_amd.engine import Engine  # noqa: E402
+from tools._timing import alternate  # noqa: E402
 from vppstereo_amd.update import GruGlue  # noqa: E402
 
 ITERS_PER_FRAME = 32
-
-
-def timeit(fn, iters, warm=1):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds, iters):
-    for fn in variants.values():
-        timeit(fn, iters=2, warm=2)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
 
 
 def row(stat, nbytes=None):
@@ -137,7 +114,7 @@ def main():
             variants = {"fused": lambda: fused_iteration(glue, grus, net, inp, enc_out, flow),
                         "torch_composition": lambda: torch_iteration(grus, net, inp, enc_out, flow)}
             with torch.no_grad():
-                st = alternate(variants, args.rounds, args.iters)
+                st = alternate(variants, args.rounds, args.iters, warm_iters=2, warm=2)
                 a, b = fused_iteration(glue, grus, net, inp, enc_out, flow), torch_iteration(grus, net, inp, enc_out, flow)
             case = {"fused": row(st["fused"], fused_bytes(B, C, sizes, size)), "torch_composition": row(st["torch_composition"]),
                     "torch_over_fused": round(st["torch_composition"][0] / st["fused"][0], 2),

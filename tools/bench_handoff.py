@@ -8,7 +8,6 @@ conditions on the bfloat16 kernel are reported.  Prints one JSON line."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -16,31 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vppstereo_amd.engine import Engine  # noqa: E402
-
-
-def timeit(fn, iters=10, warm=2):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds=9, iters=40):
-    """variants: name -> callable.  Every round times each of them in turn, so that a change of the machine's state
-    falls on all of them; -> name -> (median ms, min ms, max ms) over the rounds."""
-    for fn in variants.values():
-        timeit(fn, iters=3, warm=2)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters, warm=1))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+from tools._timing import alternate, timeit  # noqa: E402
 
 
 def row(stat, bytes_written, **more):
@@ -72,7 +47,7 @@ def main():
         variants["bfloat16"] = lambda: eng.psmnet_cost_volume(fl16, fr16, maxdisp, hints, valid)
     if f32 and bf16:
         variants["float32_then_cast"] = lambda: eng.psmnet_cost_volume(fl, fr, maxdisp, hints, valid).to(torch.bfloat16)
-    stats = alternate(variants)
+    stats = alternate(variants, rounds=9, iters=40, warm_iters=3, warm=2)
     written = {"float32": 4 * cells, "bfloat16": 2 * cells, "float32_then_cast": 6 * cells}
     psm = out["psmnet_cost_volume"] = {"frames": B, "shape": [B, 2 * C, maxdisp // 4, H4, W4], "rounds": 9, "iters_per_round": 40}
     for k, st in stats.items():
@@ -117,7 +92,7 @@ def main():
         variants["float32"] = lambda: eng.raft_corr_modulate_(corr, hints, valid)
     if bf16:
         variants["bfloat16"] = lambda: eng.raft_corr_modulate_(corr16, hints, valid)
-    stats = alternate(variants)
+    stats = alternate(variants, rounds=9, iters=40, warm_iters=3, warm=2)
     rows = int((torch.nn.functional.interpolate(valid, size=[H4, W4], mode="nearest") != 0).sum().item())
     raft = out["raft_corr_modulate"] = {"frames": B, "rows_with_a_hint": rows, "rows": B * H4 * W4,
                                         "note": "in place, only rows with a hint are touched"}
@@ -127,7 +102,7 @@ def main():
     if f32:
         raft.update(ms=raft["float32"]["ms"], volume_GB=raft["float32"]["volume_GB"])
     png = torch.randint(0, 65536, (64, 375, 1242), generator=g).to(torch.int16).to(dev)
-    ms = timeit(lambda: eng.kitti_disp_decode(png))
+    ms = timeit(lambda: eng.kitti_disp_decode(png), iters=10, warm=2)
     nb = png.numel() * (2 + 4 + 1)
     out["kitti_disp_decode"] = {"ms": round(ms, 4), "GBps": round(nb / ms / 1e6, 1), "frames": 64}
     # cfg 4: VPP only -> network tensors, device resident (17 B/pixel: latency bound)
@@ -142,7 +117,7 @@ def main():
         def vpp_to_net():
             lv, rv = eng.vpp(lt, rt, ht, seed=1)
             return eng.to_network_input(lv, torch.bfloat16), eng.to_network_input(rv, torch.bfloat16)
-        ms = timeit(vpp_to_net)
+        ms = timeit(vpp_to_net, iters=10, warm=2)
         out[f"vpp_to_bf16_nchw_B{Bv}"] = {"ms": round(ms, 4), "us_per_frame": round(ms * 1e3 / Bv, 1)}
     out["device"] = eng.ctx.device_name
     print(json.dumps(out))

@@ -16,7 +16,6 @@ two ranges (max - min).  Writes one JSON document to --out and prints it."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -25,29 +24,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from vppstereo_amd.engine import Engine  # noqa: E402
-
-
-def timeit(fn, iters, warm=3):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds, iters):
-    for fn in variants.values():
-        timeit(fn, iters=5, warm=5)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+from tools._timing import alternate  # noqa: E402
 
 
 def row(stat, nbytes, launches):
@@ -107,7 +84,8 @@ def main():
                 def lookup_alone():
                     return eng.raft_corr_lookup(pyr, coords, R, out=look)
 
-                st = alternate({"fused": fused, "composition": composition, "lookup_alone": lookup_alone}, args.rounds, args.iters)
+                st = alternate({"fused": fused, "composition": composition, "lookup_alone": lookup_alone}, args.rounds, args.iters, warm_iters=5,
+                               warm=5, round_warm=3)
                 # per pixel and level the 128-byte lines the 2r+2 cells lie in (one or two), and the coordinate
                 window = sum(min((taps + 1) * psize + 64, (W3 >> i) * psize) for i in range(L)) + 4
                 chunks = (N + 127) // 128

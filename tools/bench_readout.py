@@ -14,7 +14,6 @@ is reported as such and not timed.  Prints one JSON line and writes it to profil
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -23,29 +22,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from vppstereo_amd.engine import Engine  # noqa: E402
-
-
-def timeit(fn, iters, warm=1):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternate(variants, rounds, iters):
-    for fn in variants.values():
-        timeit(fn, iters=1, warm=1)
-    ms = {k: [] for k in variants}
-    for _ in range(rounds):
-        for k, fn in variants.items():
-            ms[k].append(timeit(fn, iters=iters[k]))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+from tools._timing import alternate  # noqa: E402
 
 
 def row(stat, nbytes=None):
@@ -110,7 +87,7 @@ def main():
             except torch.OutOfMemoryError:
                 case["psmnet_torch_composition"] = "out of memory"
             torch.cuda.empty_cache()
-            st = alternate(variants, args.rounds, iters)
+            st = alternate(variants, args.rounds, iters, warm_iters=1, warm=1)
             case["psmnet_fused"] = row(st["fused"], cost.numel() * size + res.numel() * 4)
             if "torch_composition" in st:
                 case["psmnet_torch_composition"] = row(st["torch_composition"])
@@ -123,7 +100,7 @@ def main():
             up = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=dev)
             variants = {"fused": lambda: eng.raft_upsample(flow, mask, 2, negate=True, channels=1, crop=crop, out=up),
                         "torch_composition": lambda: torch_raft(flow, mask, 2, crop)}
-            st = alternate(variants, args.rounds, {"fused": args.iters, "torch_composition": args.iters})
+            st = alternate(variants, args.rounds, {"fused": args.iters, "torch_composition": args.iters}, warm_iters=1, warm=1)
             case["raft_fused"] = row(st["fused"], (mask.numel() + flow.numel() // 2) * size + up.numel() * 4)
             case["raft_torch_composition"] = row(st["torch_composition"])
             case["raft_speedup"] = round(st["torch_composition"][0] / st["fused"][0], 2)

@@ -17,7 +17,7 @@
 //   float32:  v_mfma_f32_16x16x4_f32 takes A[l & 15][k = l >> 4], one 4-byte LDS read per fragment, no transpose.
 //   bfloat16: v_mfma_f32_16x16x32_bf16 takes 8 consecutive k of one x per lane: eight 2-byte LDS reads down a column.
 // The accumulators start at +0 and are float32; the order of the sum is the matrix cores'.
-#include "vppx_internal.h"
+#include "corr_shared.h"
 
 #include <math.h>
 #include <type_traits>
@@ -85,8 +85,7 @@ __device__ __forceinline__ void cg_put(T *s, const uint4 (&q)[KS * COLS * (int)s
 }
 
 // The lane's eight consecutive cells c[] of level 0 from cell k0 of `row` on, already divided: the modulation, the store
-// and the pooled levels, step for step raft_pyramid_kernel's (a pooled cell past the end of its level is made from cells
-// that are not the row's and is never stored).
+// and the pooled levels, which are raft_pyramid_kernel's own code (corr_pool_levels).
 template <bool BF16>
 __device__ __forceinline__ void cg_emit(float *c, size_t row, int k0, int W3, int levels, bool mod, float v, float h,
                                         void *__restrict__ corr_, void *__restrict__ pyr_, const CorrLevels &lv)
@@ -107,43 +106,7 @@ __device__ __forceinline__ void cg_emit(float *c, size_t row, int k0, int W3, in
         store_cells<4>(p, c, valid, vec0);
         store_cells<4>(p + 4, c + 4, valid - 4, vec0);
     }
-    float l1[4], l2[2], l3[1];
-#pragma unroll
-    for (int j = 0; j < 4; j++) l1[j] = pool2(c[2 * j], c[2 * j + 1]);
-    if (levels > 1) {
-        const int W = W3 >> 1, k = k0 >> 1;
-        if (BF16) {
-            u32 b[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) b[j] = bf16_rne(l1[j]), l1[j] = bf16_widen(b[j]);
-            store_cells<4>((u16 *)pyr_ + lv.off[1] + row * (size_t)W + k, b, W - k, lv.vec & 2u);
-        } else {
-            store_cells<4>((float *)pyr_ + lv.off[1] + row * (size_t)W + k, l1, W - k, lv.vec & 2u);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; j++) l2[j] = pool2(l1[2 * j], l1[2 * j + 1]);
-    if (levels > 2) {
-        const int W = W3 >> 2, k = k0 >> 2;
-        if (BF16) {
-            u32 b[2];
-#pragma unroll
-            for (int j = 0; j < 2; j++) b[j] = bf16_rne(l2[j]), l2[j] = bf16_widen(b[j]);
-            store_cells<2>((u16 *)pyr_ + lv.off[2] + row * (size_t)W + k, b, W - k, lv.vec & 4u);
-        } else {
-            store_cells<2>((float *)pyr_ + lv.off[2] + row * (size_t)W + k, l2, W - k, lv.vec & 4u);
-        }
-    }
-    l3[0] = pool2(l2[0], l2[1]);
-    if (levels > 3) {
-        const int W = W3 >> 3, k = k0 >> 3;
-        if (BF16) {
-            u32 b[1] = {bf16_rne(l3[0])};
-            store_cells<1>((u16 *)pyr_ + lv.off[3] + row * (size_t)W + k, b, W - k, false);
-        } else {
-            store_cells<1>((float *)pyr_ + lv.off[3] + row * (size_t)W + k, l3, W - k, false);
-        }
-    }
+    corr_pool_levels<BF16>(c, row, k0, W3, levels, pyr_, lv);
 }
 
 // grid: (x3 chunks * x2 chunks, H4, B).  invec bit 0 / 1: fmap2 / fmap3 may be read with 16-byte loads.

@@ -3,12 +3,12 @@
 //   * the lookup:  2r+1 bilinear taps per level around coords / 2^i, all levels in one launch                  corr.py:126-145
 // Every arithmetic step is one correctly rounded float32 operation in the order include/vppx.h writes down: the results
 // are the reference's bit for bit, so nothing here may be reassociated or contracted.
-#include "vppx_internal.h"
+#include "corr_shared.h"
 
 #include <math.h>
 
-// CorrLevels, pool2, store_cells and corr_levels are shared with corr_gemm_kernels.hip, corr_tap (one tap of the lookup) with
-// motion_kernels.hip: vppx_internal.h
+// CorrLevels, store_cells, corr_pool_levels and corr_levels are shared with corr_gemm_kernels.hip, corr_tap (one tap of the
+// lookup) with motion_kernels.hip: corr_shared.h
 
 // One 64-lane wave per (b, y, x2) row, four rows per workgroup; a lane owns 8 consecutive cells of level 0 per trip of
 // 512, which are 4, 2 and 1 cells of levels 1, 2 and 3: every pooled cell is made in the lane's registers from the
@@ -67,44 +67,7 @@ __global__ void __launch_bounds__(256) raft_pyramid_kernel(void *__restrict__ co
                 store_cells<4>(p + 4, c + 4, valid - 4, vec0);
             }
         }
-        // cells past the end of a level are made from zeros and never stored
-        float l1[4], l2[2], l3[1];
-#pragma unroll
-        for (int j = 0; j < 4; j++) l1[j] = pool2(c[2 * j], c[2 * j + 1]);
-        if (levels > 1) {
-            const int W = W3 >> 1, k = k0 >> 1;
-            if (BF16) {
-                u32 b[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) b[j] = bf16_rne(l1[j]), l1[j] = bf16_widen(b[j]);
-                store_cells<4>((u16 *)pyr_ + lv.off[1] + row * (size_t)W + k, b, W - k, lv.vec & 2u);
-            } else {
-                store_cells<4>((float *)pyr_ + lv.off[1] + row * (size_t)W + k, l1, W - k, lv.vec & 2u);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; j++) l2[j] = pool2(l1[2 * j], l1[2 * j + 1]);
-        if (levels > 2) {
-            const int W = W3 >> 2, k = k0 >> 2;
-            if (BF16) {
-                u32 b[2];
-#pragma unroll
-                for (int j = 0; j < 2; j++) b[j] = bf16_rne(l2[j]), l2[j] = bf16_widen(b[j]);
-                store_cells<2>((u16 *)pyr_ + lv.off[2] + row * (size_t)W + k, b, W - k, lv.vec & 4u);
-            } else {
-                store_cells<2>((float *)pyr_ + lv.off[2] + row * (size_t)W + k, l2, W - k, lv.vec & 4u);
-            }
-        }
-        l3[0] = pool2(l2[0], l2[1]);
-        if (levels > 3) {
-            const int W = W3 >> 3, k = k0 >> 3;
-            if (BF16) {
-                u32 b[1] = {bf16_rne(l3[0])};
-                store_cells<1>((u16 *)pyr_ + lv.off[3] + row * (size_t)W + k, b, W - k, false);
-            } else {
-                store_cells<1>((float *)pyr_ + lv.off[3] + row * (size_t)W + k, l3, W - k, false);
-            }
-        }
+        corr_pool_levels<BF16>(c, row, k0, W3, levels, pyr_, lv);
     }
 }
 

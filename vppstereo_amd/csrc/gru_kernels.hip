@@ -9,77 +9,10 @@
 // Every tensor is [B,C,H,W] with a frame stride of its own: a lane owns V consecutive cells of one frame (16 bytes: 4 float32,
 // 8 bfloat16) and moves them as one vector where the launcher found every base 16-byte aligned and every frame stride a
 // multiple of V; otherwise the same kernels run with V = 1.
-#include "vppx_internal.h"
+#include "cells.h"
 
 #include <math.h>
 #include <string.h>
-
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-
-template <bool BF16, int V>
-__device__ __forceinline__ void load_cells(const void *p, size_t at, float *c)
-{
-    if (BF16) {
-        const u16 *q = (const u16 *)p + at;
-        if (V == 8) {
-            const u16x8 v = *(const u16x8 *)q;
-#pragma unroll
-            for (int j = 0; j < 8; j++) c[j] = bf16_widen(v[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; j++) c[j] = bf16_widen(q[j]);
-        }
-    } else {
-        const float *q = (const float *)p + at;
-        if (V == 4) {
-            const float4 v = *(const float4 *)q;
-            c[0] = v.x, c[1] = v.y, c[2] = v.z, c[3] = v.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; j++) c[j] = q[j];
-        }
-    }
-}
-
-template <bool BF16, int V>
-__device__ __forceinline__ void store_group(void *p, size_t at, const float *c)
-{
-    if (BF16) {
-        u16 *q = (u16 *)p + at;
-        if (V == 8) {
-            u16x8 v;
-#pragma unroll
-            for (int j = 0; j < 8; j++) v[j] = (u16)bf16_rne(c[j]);
-            *(u16x8 *)q = v;
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; j++) q[j] = (u16)bf16_rne(c[j]);
-        }
-    } else {
-        float *q = (float *)p + at;
-        if (V == 4) {
-            *(float4 *)q = make_float4(c[0], c[1], c[2], c[3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; j++) q[j] = c[j];
-        }
-    }
-}
-
-template <bool BF16>
-__device__ __forceinline__ float load_cell(const void *p, size_t i)
-{
-    return BF16 ? bf16_widen(((const u16 *)p)[i]) : ((const float *)p)[i];
-}
-
-template <bool BF16>
-__device__ __forceinline__ void store_cell(void *p, size_t i, float v)
-{
-    if (BF16)
-        ((u16 *)p)[i] = (u16)bf16_rne(v);
-    else
-        ((float *)p)[i] = v;
-}
 
 // 1 / (1 + exp(-v)): +inf -> 1 / (1 + 0) = 1, -inf -> 1 / inf = 0
 __device__ __forceinline__ float gru_sigmoid(float v) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v))); }
@@ -100,9 +33,9 @@ __global__ void __launch_bounds__(256) gru_reset_kernel(const void *ar, long lon
     const long long at = (long long)(i - b * (size_t)G) * V;
     float a[V], c[V], hh[V], o[V];
     if (at + V <= n) {
-        load_cells<BF16, V>(ar, b * sar + at, a);
-        load_cells<BF16, V>(cr, b * scr + at, c);
-        load_cells<BF16, V>(h, b * sh + at, hh);
+        load_cells<BF16, (V > 1), V>(ar, b * sar + at, a);
+        load_cells<BF16, (V > 1), V>(cr, b * scr + at, c);
+        load_cells<BF16, (V > 1), V>(h, b * sh + at, hh);
 #pragma unroll
         for (int j = 0; j < V; j++) o[j] = __fmul_rn(gru_sigmoid(__fadd_rn(a[j], c[j])), hh[j]);
         store_group<BF16, V>(hx, b * shx + at, o);
@@ -133,11 +66,11 @@ __global__ void __launch_bounds__(256) gru_update_kernel(const void *az, long lo
     const long long at = (long long)(i - b * (size_t)G) * V;
     float vaz[V], vcz[V], vaq[V], vcq[V], hh[V], o[V];
     if (at + V <= n) {
-        load_cells<BF16, V>(az, b * saz + at, vaz);
-        load_cells<BF16, V>(cz, b * scz + at, vcz);
-        load_cells<BF16, V>(aq, b * saq + at, vaq);
-        load_cells<BF16, V>(cq, b * scq + at, vcq);
-        load_cells<BF16, V>(h, b * sh + at, hh);
+        load_cells<BF16, (V > 1), V>(az, b * saz + at, vaz);
+        load_cells<BF16, (V > 1), V>(cz, b * scz + at, vcz);
+        load_cells<BF16, (V > 1), V>(aq, b * saq + at, vaq);
+        load_cells<BF16, (V > 1), V>(cq, b * scq + at, vcq);
+        load_cells<BF16, (V > 1), V>(h, b * sh + at, hh);
 #pragma unroll
         for (int j = 0; j < V; j++) o[j] = gru_blend(vaz[j], vcz[j], vaq[j], vcq[j], hh[j]);
         store_group<BF16, V>(out, b * so + at, o);
@@ -240,7 +173,7 @@ __global__ void __launch_bounds__(256) gru_assemble_kernel(GruAsm a, int H, int 
     const long long end = k + 1 < a.n ? a.s[k + 1].first : n;
     float c[V];
     if (V > 1 && at + V <= end && a.s[k].mode == VPPX_GRU_COPY && a.s[k].vec) {
-        load_cells<BF16, V>(a.s[k].p, b * (size_t)a.s[k].stride + (size_t)(at - a.s[k].first), c);
+        load_cells<BF16, (V > 1), V>(a.s[k].p, b * (size_t)a.s[k].stride + (size_t)(at - a.s[k].first), c);
         store_group<BF16, V>(hx, b * shx + at, c);
         return;
     }
@@ -279,8 +212,6 @@ __global__ void __launch_bounds__(256) gru_assemble_kernel(GruAsm a, int H, int 
 // ---------------------------------------------------------------------------------------
 // launchers (every argument has been checked by vppx_api.hip)
 // ---------------------------------------------------------------------------------------
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 static int gru_grid(const char *who, int B, long long n, int V, long long *G, size_t *total, unsigned *blocks)
 {
     *G = (n + V - 1) / V;
@@ -318,14 +249,9 @@ int gru_assemble(vppx_ctx *ctx, const VppxGruSource *src, int n_src, int B, int 
     unsigned blocks;
     int rc;
     if ((rc = gru_grid("vppx_raft_gru_assemble", B, n, V, &G, &total, &blocks))) return rc;
-    if (bf16 && V == 8)
-        gru_assemble_kernel<true, 8><<<dim3(blocks), 256, 0, ctx->stream>>>(a, H, W, hx, shx, n, G, total);
-    else if (bf16)
-        gru_assemble_kernel<true, 1><<<dim3(blocks), 256, 0, ctx->stream>>>(a, H, W, hx, shx, n, G, total);
-    else if (V == 4)
-        gru_assemble_kernel<false, 4><<<dim3(blocks), 256, 0, ctx->stream>>>(a, H, W, hx, shx, n, G, total);
-    else
-        gru_assemble_kernel<false, 1><<<dim3(blocks), 256, 0, ctx->stream>>>(a, H, W, hx, shx, n, G, total);
+#define GRU_ASSEMBLE_LAUNCH(BF, VV) gru_assemble_kernel<BF, VV><<<dim3(blocks), 256, 0, ctx->stream>>>(a, H, W, hx, shx, n, G, total)
+    CELLS_LAUNCH(bf16, V > 1, GRU_ASSEMBLE_LAUNCH);
+#undef GRU_ASSEMBLE_LAUNCH
     VPPX_CHECK_LAUNCH();
     return 0;
 }
@@ -346,14 +272,7 @@ int gru_reset(vppx_ctx *ctx, const void *ar, int64_t sar, const void *cr, int64_
     if ((rc = gru_grid("vppx_raft_gru_reset", B, n, V, &G, &total, &blocks))) return rc;
 #define GRU_RESET_LAUNCH(BF, VV) \
     gru_reset_kernel<BF, VV><<<dim3(blocks), 256, 0, ctx->stream>>>(ar, (long long)sar, cr, (long long)scr, h, (long long)sh, hx, (long long)shx, n, G, total)
-    if (bf16 && vec)
-        GRU_RESET_LAUNCH(true, 8);
-    else if (bf16)
-        GRU_RESET_LAUNCH(true, 1);
-    else if (vec)
-        GRU_RESET_LAUNCH(false, 4);
-    else
-        GRU_RESET_LAUNCH(false, 1);
+    CELLS_LAUNCH(bf16, vec, GRU_RESET_LAUNCH);
 #undef GRU_RESET_LAUNCH
     VPPX_CHECK_LAUNCH();
     return 0;
@@ -376,14 +295,7 @@ int gru_update(vppx_ctx *ctx, const void *az, int64_t saz, const void *cz, int64
 #define GRU_UPDATE_LAUNCH(BF, VV)                                                                                                        \
     gru_update_kernel<BF, VV><<<dim3(blocks), 256, 0, ctx->stream>>>(az, (long long)saz, cz, (long long)scz, aq, (long long)saq, cq,      \
                                                                      (long long)scq, h, (long long)sh, out, (long long)so, n, G, total)
-    if (bf16 && vec)
-        GRU_UPDATE_LAUNCH(true, 8);
-    else if (bf16)
-        GRU_UPDATE_LAUNCH(true, 1);
-    else if (vec)
-        GRU_UPDATE_LAUNCH(false, 4);
-    else
-        GRU_UPDATE_LAUNCH(false, 1);
+    CELLS_LAUNCH(bf16, vec, GRU_UPDATE_LAUNCH);
 #undef GRU_UPDATE_LAUNCH
     VPPX_CHECK_LAUNCH();
     return 0;

@@ -3,7 +3,7 @@
 //   * RAFT-Stereo all-pairs correlation modulation    models/raft_stereo/corr.py:160-178
 //   * disparity file payload decoders                 dataloaders/frame_utils.py:34-69
 // All of them are HBM streaming kernels (write-bound volume fill; sparse in-place row scaling).
-#include "vppx_internal.h"
+#include "corr_shared.h"
 
 #include <math.h>
 

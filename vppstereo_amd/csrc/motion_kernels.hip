@@ -17,7 +17,7 @@
 // chunk of the workgroup; rows are MF_SW cells apart so that the four k rows of one fragment read start in different banks.
 // What a step's k means (level and tap, or channel, dy and dx) is looked up in a table made once per workgroup.
 // The flow window is read from memory as it is (two channels of a frame are 0.26 MB at 544x960 and stay in the caches).
-#include "vppx_internal.h"
+#include "corr_shared.h"
 
 #include <math.h>
 
@@ -36,9 +36,6 @@ struct MotionArgs {
     int H4, W2, W3, levels, radius, Cc, Cf, ks, Kc, Kf, KcP, KfP; // K*: levels*(2r+1) and 2*ks*ks; K*P: padded to 4
     unsigned vec; // bit 0 / 1: out_c / out_f may be written with 16-byte stores
 };
-
-// relu as torch's: a NaN stays NaN
-__device__ __forceinline__ float mf_relu(float v) { return v < 0.0f ? 0.0f : v; }
 
 // The eight cells c[] of channel m from flat pixel n0 on.  vec: the base and the frame stride are whole 16-byte groups and
 // so is a plane, so a group of 4 float32 (8 bfloat16) cells lies inside one frame, wholly inside the tensor or wholly outside.
@@ -90,7 +87,7 @@ __device__ __forceinline__ void mf_emit(const mf_f32x4 (&acc)[2][4], int ntiles,
         const float bias = sBias[m];
         float c[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) c[j] = mf_relu(__fadd_rn(acc[j >> 2][n][j & 3], bias));
+        for (int j = 0; j < 8; j++) c[j] = relu_nan(__fadd_rn(acc[j >> 2][n][j & 3], bias));
         mf_store8<OBF16>(out, stride, plane, n0, n_pix, m, c, vec);
     }
 }

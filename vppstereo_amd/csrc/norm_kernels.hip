@@ -6,7 +6,7 @@
 // Storage is float32 or bfloat16 (widened on load, rounded once on store); include/vppx.h has the arithmetic,
 // tests/_norm_ref.py the float64 referee and its bound.  Both are bound by their passes over the tensor: the statistics
 // read x once, the apply reads x (and res) once and writes once.
-#include "vppx_internal.h"
+#include "cells.h"
 
 #include <math.h>
 
@@ -32,46 +32,6 @@ static long long norm_stats_chunk(long long cells, int pieces)
 {
     const long long c = (cells + pieces - 1) / pieces;
     return (c + NS_TRIP - 1) / NS_TRIP * NS_TRIP;
-}
-
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-
-// N cells from cell `at` of p on, widened; VEC: as 16-byte loads (the caller has checked the alignment)
-template <bool BF16, bool VEC, int N>
-__device__ __forceinline__ void norm_load(const void *p, size_t at, float *c)
-{
-    if (BF16) {
-        const u16 *q = (const u16 *)p + at;
-        if (VEC) {
-#pragma unroll
-            for (int g = 0; g < N / 8; g++) {
-                const u16x8 v = *(const u16x8 *)(q + 8 * g);
-#pragma unroll
-                for (int j = 0; j < 8; j++) c[8 * g + j] = bf16_widen(v[j]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < N; j++) c[j] = bf16_widen(q[j]);
-        }
-    } else {
-        const float *q = (const float *)p + at;
-        if (VEC) {
-#pragma unroll
-            for (int g = 0; g < N / 4; g++) {
-                const float4 v = *(const float4 *)(q + 4 * g);
-                c[4 * g] = v.x, c[4 * g + 1] = v.y, c[4 * g + 2] = v.z, c[4 * g + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < N; j++) c[j] = q[j];
-        }
-    }
-}
-
-template <bool BF16>
-__device__ __forceinline__ float norm_load1(const void *p, size_t i)
-{
-    return BF16 ? bf16_widen(((const u16 *)p)[i]) : ((const float *)p)[i];
 }
 
 // (mean, rstd) from the sums of a plane of n cells, in float64 (include/vppx.h)
@@ -104,7 +64,7 @@ __global__ void __launch_bounds__(NS_THREADS) norm_stats_kernel(const void *x, l
     for (long long i0 = lo + (long long)threadIdx.x * NS_TRIP; i0 < hi; i0 += (long long)NS_THREADS * NS_TRIP) {
         float v[NS_TRIP];
         if (i0 + NS_TRIP <= hi) {
-            norm_load<BF16, VEC, NS_TRIP>(x, base + (size_t)i0, v);
+            load_cells<BF16, VEC, NS_TRIP>(x, base + (size_t)i0, v);
 #pragma unroll
             for (int k = 0; k < NS_TRIP; k++) {
                 const double d = (double)v[k];
@@ -113,7 +73,7 @@ __global__ void __launch_bounds__(NS_THREADS) norm_stats_kernel(const void *x, l
             }
         } else {
             for (long long k = i0; k < hi; k++) {
-                const double d = (double)norm_load1<BF16>(x, base + (size_t)k);
+                const double d = (double)load_cell<BF16>(x, base + (size_t)k);
                 s1 += d;
                 s2 += d * d;
             }
@@ -172,45 +132,18 @@ struct NormPlane {
     bool has_w, relu_inner, has_res, has_rs, has_rw;
 };
 
-__device__ __forceinline__ float norm_relu(float v) { return v < 0.0f ? 0.0f : v; } // a NaN stays
-
 __device__ __forceinline__ float norm_cell(const NormPlane &p, float x, float r)
 {
     float v = __fmul_rn(__fsub_rn(x, p.mean), p.rstd);
     if (p.has_w) v = __fadd_rn(__fmul_rn(v, p.w), p.b);
-    if (p.relu_inner) v = norm_relu(v);
+    if (p.relu_inner) v = relu_nan(v);
     if (p.has_res) {
         float u = r;
         if (p.has_rs) u = __fmul_rn(__fsub_rn(u, p.mean_r), p.rstd_r);
         if (p.has_rw) u = __fadd_rn(__fmul_rn(u, p.rw), p.rb);
-        v = norm_relu(__fadd_rn(u, v));
+        v = relu_nan(__fadd_rn(u, v));
     }
     return v;
-}
-
-template <bool BF16, int V>
-__device__ __forceinline__ void norm_store(void *p, size_t at, const float *c)
-{
-    if (BF16) {
-        u16 *q = (u16 *)p + at;
-        if (V == 8) {
-            u16x8 v;
-#pragma unroll
-            for (int j = 0; j < 8; j++) v[j] = (u16)bf16_rne(c[j]);
-            *(u16x8 *)q = v;
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; j++) q[j] = (u16)bf16_rne(c[j]);
-        }
-    } else {
-        float *q = (float *)p + at;
-        if (V == 4) {
-            *(float4 *)q = make_float4(c[0], c[1], c[2], c[3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; j++) q[j] = c[j];
-        }
-    }
 }
 
 template <bool BF16, int V>
@@ -234,14 +167,14 @@ __global__ void __launch_bounds__(256) norm_apply_kernel(NormApply a)
     for (int t = 0; t < NA_TRIPS; t++) {
         const long long at = first + (long long)t * 256 * V;
         if (at + V <= a.hw) {
-            norm_load<BF16, (V > 1), V>(a.x, bx + (size_t)at, xv[t]);
-            if (p.has_res) norm_load<BF16, (V > 1), V>(a.res, br + (size_t)at, rv[t]);
+            load_cells<BF16, (V > 1), V>(a.x, bx + (size_t)at, xv[t]);
+            if (p.has_res) load_cells<BF16, (V > 1), V>(a.res, br + (size_t)at, rv[t]);
         } else {
 #pragma unroll
             for (int j = 0; j < V; j++) {
                 if (at + j < a.hw) {
-                    xv[t][j] = norm_load1<BF16>(a.x, bx + (size_t)(at + j));
-                    if (p.has_res) rv[t][j] = norm_load1<BF16>(a.res, br + (size_t)(at + j));
+                    xv[t][j] = load_cell<BF16>(a.x, bx + (size_t)(at + j));
+                    if (p.has_res) rv[t][j] = load_cell<BF16>(a.res, br + (size_t)(at + j));
                 }
             }
         }
@@ -253,13 +186,13 @@ __global__ void __launch_bounds__(256) norm_apply_kernel(NormApply a)
         if (at + V <= a.hw) {
 #pragma unroll
             for (int j = 0; j < V; j++) o[j] = norm_cell(p, xv[t][j], p.has_res ? rv[t][j] : 0.0f);
-            norm_store<BF16, V>(a.out, bo + (size_t)at, o);
+            store_group<BF16, V>(a.out, bo + (size_t)at, o);
         } else {
 #pragma unroll
             for (int j = 0; j < V; j++) {
                 if (at + j < a.hw) {
                     o[0] = norm_cell(p, xv[t][j], p.has_res ? rv[t][j] : 0.0f);
-                    norm_store<BF16, 1>(a.out, bo + (size_t)(at + j), o);
+                    store_group<BF16, 1>(a.out, bo + (size_t)(at + j), o);
                 }
             }
         }
@@ -269,8 +202,6 @@ __global__ void __launch_bounds__(256) norm_apply_kernel(NormApply a)
 // ---------------------------------------------------------------------------------------
 // launchers (every argument has been checked by vppx_api.hip)
 // ---------------------------------------------------------------------------------------
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 int norm_stats(vppx_ctx *ctx, const void *x, int64_t sx, int B, int C, int H, int W, double eps, float *stats, int dtype)
 {
     const bool bf16 = dtype == VPPX_DT_BF16;
@@ -288,16 +219,9 @@ int norm_stats(vppx_ctx *ctx, const void *x, int64_t sx, int B, int C, int H, in
     // every plane and every piece starts on a 16-byte boundary: chunk is a whole number of trips
     const bool vec = aligned16(x) && sx % VF == 0 && hw % VF == 0;
     const unsigned blocks = (unsigned)(planes * pieces);
-#define NORM_STATS_LAUNCH(BF, VEC) \
-    norm_stats_kernel<BF, VEC><<<dim3(blocks), NS_THREADS, 0, ctx->stream>>>(x, (long long)sx, C, hw, chunk, pieces, part, stats, eps)
-    if (bf16 && vec)
-        NORM_STATS_LAUNCH(true, true);
-    else if (bf16)
-        NORM_STATS_LAUNCH(true, false);
-    else if (vec)
-        NORM_STATS_LAUNCH(false, true);
-    else
-        NORM_STATS_LAUNCH(false, false);
+#define NORM_STATS_LAUNCH(BF, VV) \
+    norm_stats_kernel<BF, (VV > 1)><<<dim3(blocks), NS_THREADS, 0, ctx->stream>>>(x, (long long)sx, C, hw, chunk, pieces, part, stats, eps)
+    CELLS_LAUNCH(bf16, vec, NORM_STATS_LAUNCH);
 #undef NORM_STATS_LAUNCH
     VPPX_CHECK_LAUNCH();
     if (pieces > 1) {
@@ -331,14 +255,9 @@ int norm_apply(vppx_ctx *ctx, const void *x, int64_t sx, const float *stats, int
     }
     a.bpp = (unsigned)bpp;
     const dim3 grid((unsigned)nb);
-    if (bf16 && vec)
-        norm_apply_kernel<true, 8><<<grid, 256, 0, ctx->stream>>>(a);
-    else if (bf16)
-        norm_apply_kernel<true, 1><<<grid, 256, 0, ctx->stream>>>(a);
-    else if (vec)
-        norm_apply_kernel<false, 4><<<grid, 256, 0, ctx->stream>>>(a);
-    else
-        norm_apply_kernel<false, 1><<<grid, 256, 0, ctx->stream>>>(a);
+#define NORM_APPLY_LAUNCH(BF, VV) norm_apply_kernel<BF, VV><<<grid, 256, 0, ctx->stream>>>(a)
+    CELLS_LAUNCH(bf16, vec, NORM_APPLY_LAUNCH);
+#undef NORM_APPLY_LAUNCH
     VPPX_CHECK_LAUNCH();
     return 0;
 }

@@ -6,7 +6,7 @@
 //                    (models/raft_stereo/raft_stereo.py:69-81,153-154, test.py:237-245)
 // Neither is bit-equal to the torch composition: both are held to the float64 referee of tests/_readout_ref.py, whose
 // limit() is what any float32 association of the same arithmetic can reach.  include/vppx.h has the arithmetic.
-#include "vppx_internal.h"
+#include "cells.h"
 
 #include <math.h>
 
@@ -21,12 +21,6 @@ __device__ __forceinline__ void lin_src(float scale, int dst, int n_in, int &i0,
     i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
     l1 = __fsub_rn(src, (float)i0);
     l0 = __fsub_rn(1.0f, l1);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float cell(const void *p, size_t i)
-{
-    return BF16 ? bf16_widen(((const u16 *)p)[i]) : ((const float *)p)[i];
 }
 
 struct PsmTap { // one output disparity: the two source planes (as offsets into the lane's column of LDS) and their weights
@@ -79,8 +73,8 @@ __global__ void __launch_bounds__(256) psm_readout_kernel(const void *__restrict
         float *mine = p + threadIdx.x;
         for (int k = 0; k < D4; k++) {
             const size_t o = (size_t)k * plane;
-            const float r0 = __fmaf_rn(lx1, cell<BF16>(cost, a01 + o), __fmul_rn(lx0, cell<BF16>(cost, a00 + o)));
-            const float r1 = __fmaf_rn(lx1, cell<BF16>(cost, a11 + o), __fmul_rn(lx0, cell<BF16>(cost, a10 + o)));
+            const float r0 = __fmaf_rn(lx1, load_cell<BF16>(cost, a01 + o), __fmul_rn(lx0, load_cell<BF16>(cost, a00 + o)));
+            const float r1 = __fmaf_rn(lx1, load_cell<BF16>(cost, a11 + o), __fmul_rn(lx0, load_cell<BF16>(cost, a10 + o)));
             mine[(size_t)k * T] = __fmaf_rn(ly1, r1, __fmul_rn(ly0, r0));
         }
     }
@@ -130,7 +124,7 @@ __global__ void __launch_bounds__(256) raft_upsample_kernel(const void *__restri
         float z[9], m = -INFINITY;
 #pragma unroll
         for (int k = 0; k < 9; k++) {
-            z[k] = cell<BF16>(mask, mbase + (size_t)(k * F * F + j) * plane);
+            z[k] = load_cell<BF16>(mask, mbase + (size_t)(k * F * F + j) * plane);
             m = fmaxf(m, z[k]);
         }
         den[j] = 0.0f;
@@ -148,7 +142,7 @@ __global__ void __launch_bounds__(256) raft_upsample_kernel(const void *__restri
         for (int k = 0; k < 9; k++) {
             const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
             const bool in = yy >= 0 && yy < H4 && xx >= 0 && xx < W4;
-            fl[k] = in ? __fmul_rn((float)F, cell<BF16>(flow, fbase + (size_t)yy * W4 + xx)) : 0.0f;
+            fl[k] = in ? __fmul_rn((float)F, load_cell<BF16>(flow, fbase + (size_t)yy * W4 + xx)) : 0.0f;
         }
         float r[F];
 #pragma unroll

@@ -2471,10 +2471,10 @@ extern "C" int vppx_u8_to_nchw_dev(vppx_ctx *ctx, int B, int H, int W, int C, in
 // ---------------------------------------------------------------------------------------
 // hand-off rows: PSMNet volume, RAFT correlation modulation, payload decoders
 // ---------------------------------------------------------------------------------------
-static bool handoff_dtype_ok(const char *who, int dtype)
+static bool handoff_dtype_ok(const char *who, int dtype, const char *what = "dtype")
 {
     if (dtype == VPPX_DT_F32 || dtype == VPPX_DT_BF16) return true;
-    vppx_set_error("%s: dtype %d is neither VPPX_DT_F32 (0) nor VPPX_DT_BF16 (1)", who, dtype);
+    vppx_set_error("%s: %s %d is neither VPPX_DT_F32 (0) nor VPPX_DT_BF16 (1)", who, what, dtype);
     return false;
 }
 
@@ -2579,6 +2579,25 @@ extern "C" int vppx_raft_corr_fused_dt_dev(vppx_ctx *ctx, const void *fmap2, con
     return corr_fused(ctx, fmap2, fmap3, hints, validhints, B, D, H4, W2, W3, H, W, levels, corr, pyr, dtype);
 }
 
+// a frame stride holds at least the frame
+static int gru_stride_ok(const char *who, const char *what, int64_t stride, int C, int H, int W)
+{
+    if (stride < (int64_t)C * H * W) {
+        vppx_set_error("%s: %s_frame_stride %lld is less than %d planes of %dx%d", who, what, (long long)stride, C, H, W);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
+static int coords_stride_ok(const char *who, int64_t stride, int H4, int W2)
+{
+    if (stride < (int64_t)H4 * W2) {
+        vppx_set_error("%s: coords_frame_stride %lld is less than one %dx%d plane", who, (long long)stride, H4, W2);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
 extern "C" int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x,
                                             int64_t coords_frame_stride, int B, int H4, int W2, int W3, int levels, int radius,
                                             float *out, int dtype)
@@ -2590,10 +2609,7 @@ extern "C" int vppx_raft_corr_lookup_dt_dev(vppx_ctx *ctx, const void *corr, con
         return VPPX_E_INVALID_ARG;
     }
     if ((rc = corr_shape_ok("vppx_raft_corr_lookup", B, H4, W2, W3, levels, radius, dtype))) return rc;
-    if (coords_frame_stride < (int64_t)H4 * W2) {
-        vppx_set_error("vppx_raft_corr_lookup: coords_frame_stride %lld is less than one %dx%d plane", (long long)coords_frame_stride, H4, W2);
-        return VPPX_E_INVALID_ARG;
-    }
+    if ((rc = coords_stride_ok("vppx_raft_corr_lookup", coords_frame_stride, H4, W2))) return rc;
     return corr_lookup(ctx, corr, pyr, coords_x, coords_frame_stride, B, H4, W2, W3, levels, radius, out, dtype);
 }
 
@@ -2663,15 +2679,6 @@ static int gru_shape_ok(const char *who, int B, int C, int H, int W, int dtype)
     if ((int64_t)H * W > 0x7FFFFFFF) {
         vppx_set_error("%s: a %dx%d map is more than the call takes", who, H, W);
         return VPPX_E_UNSUPPORTED;
-    }
-    return 0;
-}
-
-static int gru_stride_ok(const char *who, const char *what, int64_t stride, int C, int H, int W)
-{
-    if (stride < (int64_t)C * H * W) {
-        vppx_set_error("%s: %s_frame_stride %lld is less than %d planes of %dx%d", who, what, (long long)stride, C, H, W);
-        return VPPX_E_INVALID_ARG;
     }
     return 0;
 }
@@ -2785,14 +2792,8 @@ extern "C" int vppx_raft_motion_front_dt_dev(vppx_ctx *ctx, const void *corr, co
         return VPPX_E_INVALID_ARG;
     }
     if ((rc = corr_shape_ok(who, B, H4, W2, W3, levels, radius, dtype))) return rc;
-    if (coords_frame_stride < (int64_t)H4 * W2) {
-        vppx_set_error("%s: coords_frame_stride %lld is less than one %dx%d plane", who, (long long)coords_frame_stride, H4, W2);
-        return VPPX_E_INVALID_ARG;
-    }
-    if (out_dtype != VPPX_DT_F32 && out_dtype != VPPX_DT_BF16) {
-        vppx_set_error("%s: out_dtype %d is neither VPPX_DT_F32 (0) nor VPPX_DT_BF16 (1)", who, out_dtype);
-        return VPPX_E_INVALID_ARG;
-    }
+    if ((rc = coords_stride_ok(who, coords_frame_stride, H4, W2))) return rc;
+    if (!handoff_dtype_ok(who, out_dtype, "out_dtype")) return VPPX_E_INVALID_ARG;
     if (Cc <= 0 || Cf <= 0 || ks < 1 || ks % 2 == 0) {
         vppx_set_error("%s: %d and %d output channels and a %dx%d window: the channels must be positive and the window odd", who, Cc, Cf, ks,
                        ks);

@@ -581,106 +581,6 @@ int norm_apply(vppx_ctx *ctx, const void *x, int64_t sx, const float *stats, int
                int relu_inner, const void *res, int64_t sres, const float *res_stats, int64_t srst, const float *res_weight,
                const float *res_bias, void *out, int64_t so, int B, int C, int H, int W, int dtype);
 
-// device functions the hand-off and the correlation kernels share
-// (1 - v) + (v * height) * exp(-(d - h)^2 / two_w2)     (psmnet.py:197, corr.py:178)
-__device__ __forceinline__ float modulation(float v, float h, float d, float two_w2)
-{
-    const float diff = __fsub_rn(d, h);
-    const float e = expf(__fdiv_rn(-__fmul_rn(diff, diff), two_w2));
-    return __fadd_rn(__fsub_rn(1.0f, v), __fmul_rn(__fmul_rn(v, 10.0f), e));
-}
-
-__device__ __forceinline__ float bf16_widen(u32 bits) { return __uint_as_float(bits << 16); }
-
-// round-to-nearest-even; NaN stays NaN (quieted, sign and upper payload kept), beyond the largest bf16 -> infinity
-__device__ __forceinline__ u32 bf16_rne(float f)
-{
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
-__device__ __forceinline__ u32 bf16_scale(u32 bits, float mod) { return bf16_rne(__fmul_rn(bf16_widen(bits), mod)); }
-
-// what corr_kernels.hip and corr_gemm_kernels.hip share: where the levels lie, how a level is pooled, how a lane stores its cells
-struct CorrLevels {
-    long long off[VPPX_CORR_MAX_LEVELS]; // first cell of level i inside pyr (off[0] unused: level 0 is corr)
-    unsigned vec;                        // bit i: a lane's group of 8 >> i cells of level i may go as one aligned store
-};
-
-// ((+0 + a) + b) / 2: the sum starts at +0 as avg_pool2d's accumulator does, so two -0 cells pool to +0
-__device__ __forceinline__ float pool2(float a, float b) { return __fdiv_rn(__fadd_rn(__fadd_rn(0.0f, a), b), 2.0f); }
-
-// N consecutive cells of one level, the first `valid` of them inside the row; `vec`: p is aligned to the N cells
-template <int N>
-__device__ __forceinline__ void store_cells(float *p, const float *c, int valid, bool vec)
-{
-    if (N == 4 && vec && valid >= 4) {
-        *(float4 *)p = make_float4(c[0], c[1], c[2], c[3]);
-    } else if (N == 2 && vec && valid >= 2) {
-        *(float2 *)p = make_float2(c[0], c[1]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            if (j < valid) p[j] = c[j];
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void store_cells(u16 *p, const u32 *c, int valid, bool vec)
-{
-    if (N == 8 && vec && valid >= 8) {
-        *(uint4 *)p = make_uint4(c[0] | (c[1] << 16), c[2] | (c[3] << 16), c[4] | (c[5] << 16), c[6] | (c[7] << 16));
-    } else if (N == 4 && vec && valid >= 4) {
-        *(uint2 *)p = make_uint2(c[0] | (c[1] << 16), c[2] | (c[3] << 16));
-    } else if (N == 2 && vec && valid >= 2) {
-        *(u32 *)p = c[0] | (c[1] << 16);
-    } else {
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            if (j < valid) p[j] = (u16)c[j];
-    }
-}
-
-// One tap of the lookup (include/vppx.h has the arithmetic): rf / rb point at row n of the level (float32 / bfloat16), wm1 is
-// (float)(W - 1) of the level, xc = c / 2^i.  Both cells are loaded per position, since floor(ix) of neighbouring positions
-// need not differ by one after the round trip through the normalised coordinate; a cell outside [0, W-1] is +0, compared
-// in float so that 1e30 is outside and not an index; a position that is not finite gives +0.
-template <bool BF16>
-__device__ __forceinline__ float corr_tap(const float *rf, const u16 *rb, float wm1, float xc, int t, int radius)
-{
-    const float x = __fadd_rn((float)(t - radius), xc);
-    const float xg = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, x), wm1), 1.0f);
-    const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(xg, 1.0f), 2.0f), wm1);
-    const float fl = floorf(ix), fl1 = __fadd_rn(fl, 1.0f);
-    const bool in_a = fl >= 0.0f && fl <= wm1, in_b = fl1 >= 0.0f && fl1 <= wm1; // false for NaN
-    float val = 0.0f;
-    if ((in_a || in_b) && isfinite(ix)) {
-        const float wr = __fsub_rn(ix, fl), wl = __fsub_rn(fl1, ix);
-        float a = 0.0f, bb = 0.0f;
-        if (in_a) a = BF16 ? bf16_widen(rb[(int)fl]) : rf[(int)fl];
-        if (in_b) bb = BF16 ? bf16_widen(rb[(int)fl1]) : rf[(int)fl1];
-        val = __fmaf_rn(bb, wr, __fadd_rn(0.0f, __fmul_rn(a, wl)));
-    }
-    return val;
-}
-
-static inline CorrLevels corr_levels(const void *pyr, size_t nrows, int W3, int levels, int dtype, const void *corr)
-{
-    CorrLevels lv = {};
-    int64_t off[VPPX_CORR_MAX_LEVELS];
-    corr_pyramid_offsets((int64_t)nrows, W3, levels, off);
-    const size_t cell = dtype == VPPX_DT_BF16 ? 2 : 4;
-    for (int i = 0; i < levels; i++) {
-        lv.off[i] = off[i];
-        // level 0 goes as 16-byte vectors (4 float32 cells, 8 bf16 cells); level i >= 1 as the lane's whole group of 8 >> i cells
-        const size_t width = i ? (8 >> i) * cell : 16;
-        const uintptr_t first = i ? (uintptr_t)pyr + (size_t)off[i] * cell : (uintptr_t)corr;
-        if (width > cell && first % width == 0 && ((size_t)(W3 >> i) * cell) % width == 0) lv.vec |= 1u << i;
-    }
-    return lv;
-}
-
 // png_kernels.hip
 int handoff_png_decode(vppx_ctx *ctx, int n_files, const u8 *blob_dev, const long long *offs_dev, int H, int W, int C, u8 *zcat,
                        const long long *zoffs_dev, float scale, float *disp, u8 *valid, u8 *out_u8, int *status_dev);
