@@ -28,6 +28,7 @@
  *   CorrBlock1D.__call__                raft_stereo/corr.py:126-145 vppx_raft_corr_lookup_dt_dev
  *   BasicMotionEncoder convc1 / convf1  raft_stereo/update.py:80,82 vppx_raft_motion_front_dt_dev
  *   ResidualBlock norm / relu / sum     raft_stereo/extractor.py:48-60 vppx_raft_norm_stats_dt_dev, vppx_raft_norm_apply_dt_dev
+ *   ConvGRU convz / convr / convq + gates raft_stereo/update.py:19-32 vppx_raft_gru_zr_dt_dev, vppx_raft_gru_q_dt_dev, vppx_raft_conv3x3_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -917,6 +918,71 @@ int vppx_raft_norm_apply_dt_dev(const void *x, int64_t x_frame_stride, const flo
  * (host arithmetic only): 1 where the planes alone fill the device or a plane is small, more for few large planes.  At
  * least 1 for any arguments, never above 64, not decreasing in cells_per_plane and not increasing in planes. */
 int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane);
+/* ---- The 3x3 convolution on the matrix cores, and a ConvGRU as assemble + two launches -------------------------------
+ * (models/raft_stereo/update.py:19-32).  nn.Conv2d(Cin, Cout, 3, padding=1), stride 1: cross-correlation as torch computes
+ * it, not a flipped kernel, with +0 outside the map.  Like the encoders' glue above, these calls take the context LAST and
+ * no struct, for the reason given there.
+ *
+ * Input.  The channel concatenation of up to two sources: x0 [B,C0,H,W] and x1 [B,C1,H,W] (C1 = 0: absent, x1 is not
+ * read), Cin = C0 + C1.  Addressing is that of the update block's calls: frame b of a tensor starts b * its frame stride
+ * cells behind the pointer and is contiguous, so convq reads cat([r*h, x]) as x0 = the r*h buffer and x1 = hx[:, C:]
+ * without a copy.  dtype (VppxDtype) is the storage of every activation and output of a call.
+ *     acc[b][m][y][x] = sum over c < Cin, dy < 3, dx < 3 of w[m][c][dy][dx] * in[b][c][y + dy - 1][x + dx - 1]
+ * VPPX_DT_F32:  the float32 matrix path (v_mfma_f32_16x16x4_f32): every product exact float32 arithmetic, float32
+ *     accumulation.  It runs at 1/16 of the bfloat16 rate of the matrix cores: correct, and the slow one.
+ * VPPX_DT_BF16: v_mfma_f32_16x16x32_bf16.  Activations are bfloat16 as stored; the weights are rounded to bfloat16 once, to
+ *     nearest even, when they are packed, which is what torch does under autocast; every product is then exact in float32
+ *     and the accumulation is float32.
+ * The sum starts at +0 and runs in an order the library chooses and this header does not promise, as in
+ * vppx_raft_corr_fused_dt_dev; tests/_gruconv_ref.py derives how far any float32 evaluation in any order can lie from
+ * the exact value.  K = 9*Cin is padded to the matrix instruction's step by rows whose activation AND weight are both +0:
+ * no cell of the input ever meets a padding weight.  A NaN input cell reaches the 3x3 pixels around it, in every output
+ * channel of its frame, and no other cell; an infinite one likewise (NaN or infinite there).
+ *
+ * Packing.  packed is an opaque device buffer of vppx_raft_conv3x3_packed_bytes(Cout, Cin, dtype) bytes (0 for a shape or
+ * dtype that is not built), 16-byte aligned, written once per module by vppx_raft_conv3x3_pack_dev from weight
+ * [Cout][Cin][3][3] float32 (torch's layout, contiguous, device) and bias [Cout] float32 or NULL (no bias: +0).  Its layout
+ * is the library's; only its size is promised, and that a buffer packed for one (Cout, Cin, dtype) serves any B, H, W and
+ * any split of Cin into C0 + C1.  For the zr call the weights are convz's rows followed by convr's, [2C][Cin][3][3], and
+ * the biases likewise.
+ *
+ * Epilogues, each operation one correctly rounded float32 operation, v = acc + bias[m]:
+ *   conv3x3:  out[b][m] = relu ? (v < 0 ? 0 : v) : v         (a NaN stays NaN; the sign of a zero result is not specified)
+ *   gru_zr (Cout = 2C):   m <  C:  z[b][m]    = sigmoid(v + cz[b][m])
+ *                         m >= C:  rh[b][m-C] = sigmoid(v + cr[b][m-C]) * h[b][m-C]
+ *       rh is a [B,C,H,W] buffer of its own.  It CANNOT be the h part of the hx the call reads, which is where
+ *       vppx_raft_gru_reset_dt_dev writes r*h: other workgroups are still reading those cells as the halo of their tiles.
+ *       z, rh must not overlap any input.
+ *   gru_q (Cout = C):     q = tanh(v + cq[b][m]);   out[b][m] = ((1 - z[b][m]) * h[b][m]) + (z[b][m] * q)
+ *       z is the buffer the zr call wrote.  out may be h itself (the same pointer and frame stride): each cell of h is read
+ *       only by the lane that writes it, and the convolution reads x0 and x1, never h.  out must not overlap x0, x1, cq or z.
+ * sigmoid and tanh are those of the update block's glue above, the same formulas and the same device expf.  The
+ * convolution's sum enters the gate in float32 and is not rounded to bfloat16 first: one rounding fewer per gate input than
+ * the path through vppx_raft_gru_reset_dt_dev / _update_dt_dev.  A bfloat16 result is the float32 result rounded once, to
+ * nearest even (NaN stays NaN).  cz, cr, cq go in as channel slices of the [B,3C,H,W] context tensor by their stride.
+ *
+ * No pointer but packed has to be aligned beyond its cell: outputs (and the gates' inputs) move 16 bytes at a time where every
+ * pointer of the epilogue is 16-byte aligned and every frame stride of it and W are whole numbers of 16 bytes, and cell by
+ * cell otherwise, with the same bits.  All calls are stream-ordered, never synchronise and allocate nothing.
+ * Refused before anything is launched, with no output byte touched: a NULL weight, packed, x0, x1 with C1 > 0, cz, cr, cq, h,
+ * z, rh or out; B, H, W, C0, Cout or C <= 0, C1 < 0; a frame stride below its tensor's size; a dtype other than the two; a
+ * packed pointer that is not 16-byte aligned (VPPX_E_INVALID_ARG); C0, C1, Cout or C not a multiple of 16, C0 + C1 above
+ * VPPX_CONV_MAX_CIN, Cout (2C for the zr call) above VPPX_CONV_MAX_COUT, B*H*W above 2^31 - 1 (VPPX_E_UNSUPPORTED). */
+#define VPPX_CONV_MAX_CIN 512
+#define VPPX_CONV_MAX_COUT 256
+size_t vppx_raft_conv3x3_packed_bytes(int Cout, int Cin, int dtype);
+int vppx_raft_conv3x3_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed, vppx_ctx *ctx);
+int vppx_raft_conv3x3_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                             const void *packed, int Cout, int B, int H, int W, int relu, void *out, int64_t out_frame_stride,
+                             int dtype, vppx_ctx *ctx);
+int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                            const void *packed_zr, const void *cz, int64_t cz_frame_stride, const void *cr, int64_t cr_frame_stride,
+                            const void *h, int64_t h_frame_stride, void *z, int64_t z_frame_stride, void *rh,
+                            int64_t rh_frame_stride, int B, int C, int H, int W, int dtype, vppx_ctx *ctx);
+int vppx_raft_gru_q_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                           const void *packed_q, const void *cq, int64_t cq_frame_stride, const void *z, int64_t z_frame_stride,
+                           const void *h, int64_t h_frame_stride, void *out, int64_t out_frame_stride, int B, int C, int H, int W,
+                           int dtype, vppx_ctx *ctx);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

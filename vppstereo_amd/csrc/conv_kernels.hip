@@ -1,0 +1,357 @@
+// conv_kernels.hip -- gfx950 implicit-GEMM kernel for nn.Conv2d(Cin, Cout, 3, padding=1), stride 1, on the matrix cores, with
+// the gates of ConvGRU.forward (models/raft_stereo/update.py:23-32) as epilogues: include/vppx.h has the arithmetic.
+//   M = pixels, N = output channels, K = 9 * Cin.  bfloat16 storage: v_mfma_f32_16x16x32_bf16; float32 storage:
+//   v_mfma_f32_16x16x4_f32 (exact float32 products, 1/16 of the bfloat16 rate).  Accumulation is float32 either way.
+//
+// Tile.  A workgroup of four waves owns CV_TH x CV_TW = 8 x 32 pixels of one frame and CV_NB = 64 output channels
+// (blockIdx.y counts the channel blocks).  A wave owns two rows of the tile: per row two M tiles of 16 pixels whose rows are
+// interleaved as motion_kernels.hip interleaves its own (row r of tile t is pixel 8 * (r >> 2) + 4 * t + (r & 3) of the 32), so
+// that with the 16x16 C/D map (column = lane & 15 = channel, row = 4 * (lane >> 4) + register) a lane's registers of a tile
+// pair are EIGHT consecutive pixels of one output channel: 16 bytes of bfloat16, two 16-byte groups of float32.  4 M tiles x
+// 4 N tiles = 16 accumulators of 4 registers per lane.
+//
+// K runs in chunks of CK input channels (32 bfloat16, 16 float32: 64 bytes per pixel either way) and, inside a chunk, over the
+// nine taps.  A chunk's activations -- the tile and its one-pixel halo, 10 x 34 pixels, +0 outside the map and for channels
+// beyond Cin -- are staged into LDS TRANSPOSED to [pixel][channel], rows CV_ROWB = 80 bytes apart, so that a lane's A
+// fragment of any tap (8 bfloat16 channels, or 4 float32 channels = the four k-steps of a chunk) is one 16-byte LDS read at the
+// shifted pixel.  A thread reads its 22 four-byte units of the NEXT chunk into registers before the matrix instructions of
+// the current one and writes them to LDS behind the barrier that ends it, so the loads' latency lies under the arithmetic
+// (one LDS image, two barriers per chunk).  The weights come from the packed buffer in fragment order, [chunk][tap][N tile][lane] 16 bytes: a wave's B
+// fragment is 1 KiB of contiguous memory, the same for the four waves of a workgroup, read one step ahead of its use.
+// A packed weight of a channel beyond Cin is +0 and meets only the +0 the staging wrote, never a cell of the input.
+#include "cells.h"
+#include "gru_math.h"
+
+#define CV_TH 8
+#define CV_TW 32
+#define CV_HW (CV_TW + 2)
+#define CV_HALO ((CV_TH + 2) * CV_HW)
+#define CV_ROWB 80
+#define CV_NB 64
+
+enum { CV_PLAIN = 0, CV_ZR = 1, CV_Q = 2 };
+
+typedef float cv_f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 cv_bf16x8 __attribute__((ext_vector_type(8)));
+
+struct ConvArgs {
+    const void *x0, *x1;     // the two sources of the input; x1 is unused where C1 == 0
+    long long s0, s1;        // cells between frames
+    const uint4 *packed;     // [chunk][tap][N tile][lane] fragments
+    const float *bias;       // [Cout], behind the fragments
+    const void *e0, *e1, *e2; // epilogue inputs: zr: cz, cr, h;  q: cq, z, h
+    long long se0, se1, se2;
+    void *o0, *o1;           // plain: out;  zr: z, rh;  q: out
+    long long so0, so1;
+    int C0, Cin, NT, nchunks; // NT = Cout / 16
+    int H, W, tilesX, tilesY;
+    int C, relu, vec;        // C: the hidden size of the gates;  vec: 16-byte groups in the epilogue
+};
+
+// Eight cells of a [B,C,H,W] tensor from cell `at` on, the first `nv` of them inside the row.  vec: every base, stride, plane
+// and row of the call is a whole number of 16-byte groups, so a group of 4 float32 (8 bfloat16) cells is wholly inside or outside.
+template <bool BF16>
+__device__ __forceinline__ void cv_load8(const void *p, size_t at, int nv, bool vec, float *c)
+{
+    if (vec) {
+        if (BF16) {
+            load_cells<true, true, 8>(p, at, c);
+        } else {
+            load_cells<false, true, 4>(p, at, c);
+            if (nv > 4)
+                load_cells<false, true, 4>(p, at + 4, c + 4);
+            else
+                c[4] = c[5] = c[6] = c[7] = 0.0f;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) c[j] = j < nv ? load_cell<BF16>(p, at + j) : 0.0f;
+}
+
+template <bool BF16>
+__device__ __forceinline__ void cv_store8(void *p, size_t at, int nv, bool vec, const float *c)
+{
+    if (vec) {
+        if (BF16) {
+            store_group<true, 8>(p, at, c);
+        } else {
+            store_group<false, 4>(p, at, c);
+            if (nv > 4) store_group<false, 4>(p, at + 4, c + 4);
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        if (j < nv) store_cell<BF16>(p, at + j, c[j]);
+}
+
+template <bool BF16, int EPI>
+__global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
+{
+    constexpr int CK = BF16 ? 32 : 16;
+    __shared__ __attribute__((aligned(16))) unsigned char sA[CV_HALO * CV_ROWB];
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, i = lane & 15;
+    unsigned t = blockIdx.x;
+    const int tx = (int)(t % (unsigned)a.tilesX);
+    t /= (unsigned)a.tilesX;
+    const int ty = (int)(t % (unsigned)a.tilesY);
+    const size_t b = t / (unsigned)a.tilesY;
+    const int x0 = tx * CV_TW, y0 = ty * CV_TH, H = a.H, W = a.W;
+    const size_t plane = (size_t)H * W;
+    const int nb = blockIdx.y, ntl = min(4, a.NT - 4 * nb);
+
+    // The staging.  A pixel's row of a chunk is 16 units of 4 bytes: one float32 channel, or two bfloat16 channels (an even
+    // channel and the next lie in the same source, both below Cin or both not, because C0 and Cin are multiples of 16).
+    // Thread tid stages all 16 units of pixel tid of the 340, and unit tid / 84 + 3 j of pixel 256 + tid % 84 (tid < 252), so
+    // that the 84 pixels beyond the first 256 are spread over the workgroup: 22 units per thread, read into registers one
+    // chunk ahead, while the matrix cores work on the chunk before.
+    const int pB = CV_TH * CV_TW + tid % (CV_HALO - CV_TH * CV_TW), uB = tid / (CV_HALO - CV_TH * CV_TW);
+    int offA, offB; // y * W + x of the two pixels, -1 outside the map
+    {
+        const int ryA = tid / CV_HW, rxA = tid - ryA * CV_HW, gyA = y0 + ryA - 1, gxA = x0 + rxA - 1;
+        offA = gyA >= 0 && gyA < H && gxA >= 0 && gxA < W ? gyA * W + gxA : -1;
+        const int ryB = pB / CV_HW, rxB = pB - ryB * CV_HW, gyB = y0 + ryB - 1, gxB = x0 + rxB - 1;
+        offB = uB < 3 && gyB >= 0 && gyB < H && gxB >= 0 && gxB < W ? gyB * W + gxB : -1;
+    }
+    auto unit = [&](int chunk, int u, int off) -> u32 {
+        const int c = chunk * CK + (BF16 ? 2 * u : u);
+        if (off < 0 || c >= a.Cin) return 0u; // +0 outside the map and for the channels that pad K
+        const bool first = c < a.C0;
+        const size_t at = (first ? b * (size_t)a.s0 + (size_t)c * plane : b * (size_t)a.s1 + (size_t)(c - a.C0) * plane) + (size_t)off;
+        const void *src = first ? a.x0 : a.x1;
+        if (BF16) {
+            const u16 *p = (const u16 *)src + at;
+            return (u32)p[0] | ((u32)p[plane] << 16);
+        }
+        return ((const u32 *)src)[at];
+    };
+    u32 stA[16], stB[6];
+    auto fetch = [&](int chunk) {
+#pragma unroll
+        for (int u = 0; u < 16; u++) stA[u] = unit(chunk, u, offA);
+#pragma unroll
+        for (int j = 0; j < 6; j++) stB[j] = uB + 3 * j < 16 ? unit(chunk, uB + 3 * j, offB) : 0u;
+    };
+    fetch(0);
+
+    cv_f32x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int n = 0; n < 4; n++) acc[m][n] = (cv_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+
+    // byte offset of this lane's A fragment of M tile m = 2 * p + t at tap (0, 0)
+    int la[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) la[m] = ((2 * wave + (m >> 1)) * CV_HW + 8 * (i >> 2) + 4 * (m & 1) + (i & 3)) * CV_ROWB + 16 * g;
+
+    const uint4 *pk = a.packed + (size_t)(4 * nb) * 64 + lane;
+    const size_t step = (size_t)a.NT * 64; // fragments of one (chunk, tap)
+    const int nsteps = a.nchunks * 9;
+    uint4 bcur[4], bnext[4];
+#pragma unroll
+    for (int n = 0; n < 4; n++) bcur[n] = n < ntl ? pk[64 * n] : make_uint4(0, 0, 0, 0);
+
+    for (int chunk = 0; chunk < a.nchunks; chunk++) {
+        __syncthreads(); // the last chunk's fragments have been read
+#pragma unroll
+        for (int k = 0; k < 4; k++) *(uint4 *)(sA + tid * CV_ROWB + 16 * k) = make_uint4(stA[4 * k], stA[4 * k + 1], stA[4 * k + 2], stA[4 * k + 3]);
+        if (uB < 3) {
+#pragma unroll
+            for (int j = 0; j < 6; j++)
+                if (uB + 3 * j < 16) *(u32 *)(sA + pB * CV_ROWB + 4 * (uB + 3 * j)) = stB[j];
+        }
+        __syncthreads();
+        if (chunk + 1 < a.nchunks) fetch(chunk + 1); // in flight during this chunk's matrix instructions
+#pragma unroll
+        for (int tap = 0; tap < 9; tap++) {
+            const int s = chunk * 9 + tap;
+            if (s + 1 < nsteps) {
+#pragma unroll
+                for (int n = 0; n < 4; n++)
+                    if (n < ntl) bnext[n] = pk[(size_t)(s + 1) * step + 64 * n];
+            }
+            const int toff = ((tap / 3) * CV_HW + tap % 3) * CV_ROWB;
+            uint4 fa[4];
+#pragma unroll
+            for (int m = 0; m < 4; m++) fa[m] = *(const uint4 *)(sA + la[m] + toff);
+            if (BF16) {
+#pragma unroll
+                for (int n = 0; n < 4; n++) {
+                    if (n >= ntl) break;
+#pragma unroll
+                    for (int m = 0; m < 4; m++)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cv_bf16x8, fa[m]),
+                                                                            __builtin_bit_cast(cv_bf16x8, bcur[n]), acc[m][n], 0, 0, 0);
+                }
+            } else {
+                // the k-step outermost: consecutive instructions then work on different accumulators
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+#pragma unroll
+                    for (int n = 0; n < 4; n++) {
+                        if (n >= ntl) break;
+#pragma unroll
+                        for (int m = 0; m < 4; m++)
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(cv_f32x4, fa[m])[k],
+                                                                             __builtin_bit_cast(cv_f32x4, bcur[n])[k], acc[m][n], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < 4; n++) bcur[n] = bnext[n];
+        }
+    }
+
+    // the epilogue: per row of the wave and N tile, eight consecutive pixels of one channel
+    const bool vec = a.vec != 0;
+    const int x = x0 + 8 * g, nv = min(8, W - x);
+    if (nv <= 0) return;
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+        const int y = y0 + 2 * wave + p;
+        if (y >= H) break;
+        const size_t pix = (size_t)y * W + x;
+#pragma unroll
+        for (int n = 0; n < 4; n++) {
+            if (n >= ntl) break;
+            const int m = 64 * nb + 16 * n + i;
+            const float bias = a.bias[m];
+            float v[8], o[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) v[j] = __fadd_rn(acc[2 * p + (j >> 2)][n][j & 3], bias);
+            if (EPI == CV_PLAIN) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) o[j] = a.relu ? relu_nan(v[j]) : v[j];
+                cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
+            } else if (EPI == CV_ZR) {
+                float c[8];
+                if (m < a.C) { // uniform over the N tile: C is a multiple of 16
+                    cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * plane + pix, nv, vec, c);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) o[j] = gru_sigmoid(__fadd_rn(v[j], c[j]));
+                    cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
+                } else {
+                    const size_t mm = (size_t)(m - a.C);
+                    float hh[8];
+                    cv_load8<BF16>(a.e1, b * (size_t)a.se1 + mm * plane + pix, nv, vec, c);
+                    cv_load8<BF16>(a.e2, b * (size_t)a.se2 + mm * plane + pix, nv, vec, hh);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) o[j] = __fmul_rn(gru_sigmoid(__fadd_rn(v[j], c[j])), hh[j]);
+                    cv_store8<BF16>(a.o1, b * (size_t)a.so1 + mm * plane + pix, nv, vec, o);
+                }
+            } else {
+                float c[8], z[8], hh[8];
+                cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * plane + pix, nv, vec, c);
+                cv_load8<BF16>(a.e1, b * (size_t)a.se1 + (size_t)m * plane + pix, nv, vec, z);
+                cv_load8<BF16>(a.e2, b * (size_t)a.se2 + (size_t)m * plane + pix, nv, vec, hh); // out may be h: read before the store
+#pragma unroll
+                for (int j = 0; j < 8; j++) o[j] = gru_mix(z[j], gru_tanh(__fadd_rn(v[j], c[j])), hh[j]);
+                cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// the packing: torch's [Cout][Cin][3][3] float32 -> fragment order, channels beyond Cin as +0, the bias behind
+// ---------------------------------------------------------------------------------------
+// fragment f = ((chunk * 9 + tap) * NT + N tile) * 64 + lane holds, for lane = 16 g + i, output channel 16 * tile + i and
+//   bfloat16: element j = input channel 32 * chunk + 8 g + j          (the 16x16x32 B map: k = 8 (lane >> 4) + j)
+//   float32:  element j = input channel 16 * chunk + 4 g + j          (k-step j of the chunk, 16x16x4 B map: k = lane >> 4)
+template <bool BF16>
+__global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, const float *bias, int Cout, int Cin, int nchunks, void *packed)
+{
+    constexpr int E = BF16 ? 8 : 4, CK = BF16 ? 32 : 16;
+    const int NT = Cout / 16;
+    const size_t nfrag = (size_t)nchunks * 9 * NT * 64;
+    const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (f < (size_t)Cout) ((float *)((uint4 *)packed + nfrag))[f] = bias ? bias[f] : 0.0f;
+    if (f >= nfrag) return;
+    const int lane = (int)(f & 63), g = lane >> 4, i = lane & 15;
+    size_t r = f >> 6;
+    const int tile = (int)(r % NT);
+    r /= NT;
+    const int tap = (int)(r % 9), chunk = (int)(r / 9);
+    const int m = 16 * tile + i;
+    float v[E];
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        const int c = CK * chunk + E * g + j;
+        v[j] = c < Cin ? w[((size_t)m * Cin + c) * 9 + tap] : 0.0f;
+    }
+    if (BF16) {
+        u32 h[8];
+#pragma unroll
+        for (int j = 0; j < E; j++) h[j] = bf16_rne(v[j]);
+        ((uint4 *)packed)[f] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4 % E] | (h[5 % E] << 16), h[6 % E] | (h[7 % E] << 16));
+    } else {
+        ((float4 *)packed)[f] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// launchers (every argument has been checked by vppx_api.hip)
+// ---------------------------------------------------------------------------------------
+static int conv_chunks(int Cin, int dtype) { return dtype == VPPX_DT_BF16 ? (Cin + 31) / 32 : (Cin + 15) / 16; }
+
+static size_t conv_weight_bytes(int Cout, int Cin, int dtype) { return (size_t)conv_chunks(Cin, dtype) * 9 * (Cout / 16) * 64 * 16; }
+
+size_t conv3x3_packed_bytes(int Cout, int Cin, int dtype) { return conv_weight_bytes(Cout, Cin, dtype) + (size_t)Cout * sizeof(float); }
+
+int conv3x3_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed)
+{
+    const int nchunks = conv_chunks(Cin, dtype);
+    const size_t nfrag = (size_t)nchunks * 9 * (Cout / 16) * 64;
+    const unsigned blocks = (unsigned)((nfrag + 255) / 256);
+    if (dtype == VPPX_DT_BF16)
+        raft_conv3x3_pack_kernel<true><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, packed);
+    else
+        raft_conv3x3_pack_kernel<false><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, packed);
+    VPPX_CHECK_LAUNCH();
+    return 0;
+}
+
+int conv3x3_run(vppx_ctx *ctx, const char *who, int epi, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
+                const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
+                int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, int dtype)
+{
+    const bool bf16 = dtype == VPPX_DT_BF16;
+    ConvArgs a = {};
+    a.x0 = x0, a.x1 = C1 ? x1 : x0, a.s0 = (long long)s0, a.s1 = C1 ? (long long)s1 : 0;
+    a.C0 = C0, a.Cin = C0 + C1, a.NT = Cout / 16, a.nchunks = conv_chunks(a.Cin, dtype);
+    a.packed = (const uint4 *)packed;
+    a.bias = (const float *)((const unsigned char *)packed + conv_weight_bytes(Cout, a.Cin, dtype));
+    a.e0 = e0, a.e1 = e1, a.e2 = e2, a.se0 = (long long)se0, a.se1 = (long long)se1, a.se2 = (long long)se2;
+    a.o0 = o0, a.o1 = o1, a.so0 = (long long)so0, a.so1 = (long long)so1;
+    a.H = H, a.W = W, a.tilesX = (W + CV_TW - 1) / CV_TW, a.tilesY = (H + CV_TH - 1) / CV_TH;
+    a.C = C, a.relu = relu;
+    const size_t tiles = (size_t)B * a.tilesX * a.tilesY;
+    if (tiles > 0x7FFFFFFFull) {
+        vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, B, H, W, tiles);
+        return VPPX_E_UNSUPPORTED;
+    }
+    const int64_t V = bf16 ? 8 : 4;
+    const void *ptrs[5] = {e0, e1, e2, o0, o1};
+    const int64_t strides[5] = {se0, se1, se2, so0, so1};
+    bool vec = W % V == 0; // then H * W is a whole number of groups as well
+    for (int k = 0; k < 5; k++)
+        if (ptrs[k]) vec = vec && aligned16(ptrs[k]) && strides[k] % V == 0;
+    a.vec = vec;
+    const dim3 grid((unsigned)tiles, (unsigned)((a.NT + 3) / 4));
+#define CONV_LAUNCH(BF, EP) raft_conv3x3_kernel<BF, EP><<<grid, 256, 0, ctx->stream>>>(a)
+    if (bf16) {
+        if (epi == CV_PLAIN) CONV_LAUNCH(true, CV_PLAIN);
+        else if (epi == CV_ZR) CONV_LAUNCH(true, CV_ZR);
+        else CONV_LAUNCH(true, CV_Q);
+    } else {
+        if (epi == CV_PLAIN) CONV_LAUNCH(false, CV_PLAIN);
+        else if (epi == CV_ZR) CONV_LAUNCH(false, CV_ZR);
+        else CONV_LAUNCH(false, CV_Q);
+    }
+#undef CONV_LAUNCH
+    VPPX_CHECK_LAUNCH();
+    return 0;
+}

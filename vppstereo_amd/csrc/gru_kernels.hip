@@ -10,14 +10,10 @@
 // 8 bfloat16) and moves them as one vector where the launcher found every base 16-byte aligned and every frame stride a
 // multiple of V; otherwise the same kernels run with V = 1.
 #include "cells.h"
+#include "gru_math.h"
 
 #include <math.h>
 #include <string.h>
-
-// 1 / (1 + exp(-v)): +inf -> 1 / (1 + 0) = 1, -inf -> 1 / inf = 0
-__device__ __forceinline__ float gru_sigmoid(float v) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-v))); }
-// 1 - 2 / (exp(2v) + 1): +inf -> 1 - 2 / inf = 1, -inf -> 1 - 2 / 1 = -1
-__device__ __forceinline__ float gru_tanh(float v) { return __fsub_rn(1.0f, __fdiv_rn(2.0f, __fadd_rn(expf(__fmul_rn(2.0f, v)), 1.0f))); }
 
 // ---------------------------------------------------------------------------------------
 // the gates.  n = C*H*W cells per frame, G = ceil(n / V) groups per frame, one lane per (frame, group); a last group that
@@ -51,7 +47,7 @@ __device__ __forceinline__ float gru_blend(float az, float cz, float aq, float c
 {
     const float z = gru_sigmoid(__fadd_rn(az, cz));
     const float q = gru_tanh(__fadd_rn(aq, cq));
-    return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, z), h), __fmul_rn(z, q));
+    return gru_mix(z, q, h);
 }
 
 // out may be h: a lane reads its cells of h before it writes the same cells of out, and no other lane touches them

@@ -2879,6 +2879,134 @@ extern "C" int vppx_raft_norm_apply_dt_dev(const void *x, int64_t x_frame_stride
 
 extern "C" int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane) { return norm_stats_pieces(planes, cells_per_plane); }
 
+// The 3x3 convolution and ConvGRU's gates (conv_kernels.hip).  Flat arguments with the context last, as the encoders' glue;
+// every refusal comes before anything is launched.
+static int conv_channels_ok(const char *who, int C0, int C1, int Cout)
+{
+    if (C0 <= 0 || C1 < 0 || Cout <= 0) {
+        vppx_set_error("%s: %d + %d input and %d output channels: C0 and Cout must be positive, C1 not negative", who, C0, C1, Cout);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (C0 % 16 || C1 % 16 || Cout % 16 || (int64_t)C0 + C1 > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT) {
+        vppx_set_error("%s: %d + %d input and %d output channels: multiples of 16 up to %d in and %d out are built", who, C0, C1, Cout,
+                       VPPX_CONV_MAX_CIN, VPPX_CONV_MAX_COUT);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// everything the three calls share: the sources, the packed buffer, the sizes
+static int conv_call_ok(const char *who, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1, const void *packed, int Cout,
+                        int B, int H, int W, int dtype)
+{
+    int rc;
+    if (!x0 || !packed || (C1 > 0 && !x1)) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, 1, H, W, dtype)) || (rc = conv_channels_ok(who, C0, C1, Cout))) return rc;
+    if ((uintptr_t)packed % 16) {
+        vppx_set_error("%s: the packed buffer is not 16-byte aligned", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_stride_ok(who, "x0", s0, C0, H, W)) || (C1 > 0 && (rc = gru_stride_ok(who, "x1", s1, C1, H, W)))) return rc;
+    if ((int64_t)B * H * W > 0x7FFFFFFF) {
+        vppx_set_error("%s: B*H*W = %lld pixels are more than one launch takes", who, (long long)B * H * W);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+extern "C" size_t vppx_raft_conv3x3_packed_bytes(int Cout, int Cin, int dtype)
+{
+    if (Cout <= 0 || Cin <= 0 || Cout % 16 || Cin % 16 || Cin > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT ||
+        (dtype != VPPX_DT_F32 && dtype != VPPX_DT_BF16))
+        return 0;
+    return conv3x3_packed_bytes(Cout, Cin, dtype);
+}
+
+extern "C" int vppx_raft_conv3x3_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_conv3x3_pack";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!weight || !packed) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok(who, dtype)) return VPPX_E_INVALID_ARG;
+    if ((rc = conv_channels_ok(who, Cin, 0, Cout))) return rc;
+    if ((uintptr_t)packed % 16) {
+        vppx_set_error("%s: the packed buffer is not 16-byte aligned", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    return conv3x3_pack(ctx, weight, bias, Cout, Cin, dtype, packed);
+}
+
+extern "C" int vppx_raft_conv3x3_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                        const void *packed, int Cout, int B, int H, int W, int relu, void *out, int64_t out_frame_stride,
+                                        int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_conv3x3";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!out) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, B, H, W, dtype)) ||
+        (rc = gru_stride_ok(who, "out", out_frame_stride, Cout, H, W)))
+        return rc;
+    return conv3x3_run(ctx, who, 0, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
+                       out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, dtype);
+}
+
+extern "C" int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                       const void *packed_zr, const void *cz, int64_t cz_frame_stride, const void *cr,
+                                       int64_t cr_frame_stride, const void *h, int64_t h_frame_stride, void *z, int64_t z_frame_stride,
+                                       void *rh, int64_t rh_frame_stride, int B, int C, int H, int W, int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_gru_zr";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!cz || !cr || !h || !z || !rh || C <= 0) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (C % 16 || C > VPPX_CONV_MAX_COUT / 2) {
+        vppx_set_error("%s: a hidden size of %d makes 2 x %d output channels: multiples of 16 up to %d in all are built", who, C, C,
+                       VPPX_CONV_MAX_COUT);
+        return VPPX_E_UNSUPPORTED;
+    }
+    if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_zr, 2 * C, B, H, W, dtype))) return rc;
+    if ((rc = gru_stride_ok(who, "cz", cz_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "cr", cr_frame_stride, C, H, W)) ||
+        (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "z", z_frame_stride, C, H, W)) ||
+        (rc = gru_stride_ok(who, "rh", rh_frame_stride, C, H, W)))
+        return rc;
+    return conv3x3_run(ctx, who, 1, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_zr, 2 * C, cz, cz_frame_stride, cr,
+                       cr_frame_stride, h, h_frame_stride, z, z_frame_stride, rh, rh_frame_stride, B, C, H, W, 0, dtype);
+}
+
+extern "C" int vppx_raft_gru_q_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                      const void *packed_q, const void *cq, int64_t cq_frame_stride, const void *z, int64_t z_frame_stride,
+                                      const void *h, int64_t h_frame_stride, void *out, int64_t out_frame_stride, int B, int C, int H, int W,
+                                      int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_gru_q";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!cq || !z || !h || !out || C <= 0) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_q, C, B, H, W, dtype))) return rc;
+    if ((rc = gru_stride_ok(who, "cq", cq_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "z", z_frame_stride, C, H, W)) ||
+        (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "out", out_frame_stride, C, H, W)))
+        return rc;
+    return conv3x3_run(ctx, who, 2, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_q, C, cq, cq_frame_stride, z, z_frame_stride, h,
+                       h_frame_stride, out, out_frame_stride, NULL, 0, B, C, H, W, 0, dtype);
+}
+
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)
 {
     int rc;

@@ -574,6 +574,14 @@ int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *
                  int ks, int B, int H4, int W2, int W3, int levels, int radius, void *out_c, int64_t out_c_frame_stride, void *out_f,
                  int64_t out_f_frame_stride, int dtype, int out_dtype);
 
+// conv_kernels.hip: the 3x3 convolution on the matrix cores and ConvGRU's gates as its epilogues (update.py:19-32).
+// epi: 0 plain (o0 = out), 1 zr (e0, e1, e2 = cz, cr, h; o0, o1 = z, rh), 2 q (e0, e1, e2 = cq, z, h; o0 = out)
+size_t conv3x3_packed_bytes(int Cout, int Cin, int dtype);
+int conv3x3_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed);
+int conv3x3_run(vppx_ctx *ctx, const char *who, int epi, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
+                const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
+                int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, int dtype);
+
 // norm_kernels.hip: the encoders' glue (models/raft_stereo/extractor.py:48-60, :181-183, :276-278)
 int norm_stats_pieces(int64_t planes, int64_t cells); // host arithmetic: workgroups per plane
 int norm_stats(vppx_ctx *ctx, const void *x, int64_t sx, int B, int C, int H, int W, double eps, float *stats, int dtype);

@@ -26,6 +26,7 @@ class Engine:
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.ctx = _lib.Context(self.device.index)
         self.lib = _lib.load()
+        self._conv_sizes = {}              # (Cout, Cin, VppxDtype) -> bytes of the packed weights
 
     def _bind_stream(self):
         """Run on torch's current stream, so that library kernels are ordered with the torch work around them.
@@ -898,6 +899,109 @@ class Engine:
         self._bind_stream()
         _lib.check(self.lib.vppx_raft_gru_update_dt_dev(self.ctx.handle, _ptr(az), s[0], _ptr(cz), s[1], _ptr(aq), s[2], _ptr(cq), s[3],
                                                         _ptr(h), sh, _ptr(out), so, B, Cc, H, W, dt))
+        return out
+
+    # ---- the 3x3 convolution on the matrix cores, and ConvGRU's gates as its epilogues ----
+    def raft_conv3x3_pack(self, weight, bias=None, dtype=None):
+        """The weights [Cout,Cin,3,3] (and bias [Cout]) of an nn.Conv2d(Cin, Cout, 3, padding=1) in the layout the convolution
+        kernel reads, for activations stored as `dtype` (torch.float32, the default, or torch.bfloat16: the weights are then
+        rounded to bfloat16 once).  -> an opaque torch.uint8 device tensor; pack once per module, it serves any B, H, W."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"dtype is {dtype}; the kernels store float32 and bfloat16")
+        dt = _lib.DT_BF16 if dtype == torch.bfloat16 else _lib.DT_F32
+        if getattr(weight, "device", None) != self.device or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+            raise ValueError(f"weight: expected a [Cout,Cin,3,3] tensor on {self.device}")
+        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+        weight = weight.detach().to(torch.float32).contiguous()
+        if bias is not None:
+            bias = bias.detach().to(torch.float32).contiguous()
+            self._chk(bias, torch.float32, 1, "bias", (Cout,))
+        size = self._packed_bytes(Cout, Cin, dt)
+        if size == 0:
+            raise ValueError(f"weight: {Cin} -> {Cout} channels: multiples of 16 up to {_lib.CONV_MAX_CIN} in and "
+                             f"{_lib.CONV_MAX_COUT} out are built")
+        packed = torch.empty((size,), dtype=torch.uint8, device=self.device)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_conv3x3_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, dt, _ptr(packed), self.ctx.handle))
+        return packed
+
+    def _packed_bytes(self, cout, cin, dt):
+        """vppx_raft_conv3x3_packed_bytes, asked once per (Cout, Cin, dtype): host arithmetic on constants."""
+        key = (cout, cin, dt)
+        if key not in self._conv_sizes:
+            self._conv_sizes[key] = int(self.lib.vppx_raft_conv3x3_packed_bytes(cout, cin, dt))
+        return self._conv_sizes[key]
+
+    def _chk_conv(self, x0, x1, packed, cout):
+        """The sources and the packed weights of a convolution call -> (dtype, dt, B, H, W, s0, C0, s1, C1)."""
+        torch = self.torch
+        dtype, dt = self._norm_dtype(x0, "x0")
+        s0 = self._chk_frames(x0, dtype, "x0")
+        B, C0, H, W = x0.shape
+        s1, C1 = 0, 0
+        if x1 is not None:
+            s1 = self._chk_frames(x1, dtype, "x1")
+            C1 = x1.shape[1]
+            if (x1.shape[0], x1.shape[2], x1.shape[3]) != (B, H, W):
+                raise ValueError(f"x1: expected [{B},C1,{H},{W}], got {tuple(x1.shape)}")
+        if getattr(packed, "device", None) != self.device or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+            raise ValueError(f"packed: expected what raft_conv3x3_pack returns, a torch.uint8 vector on {self.device}")
+        want = self._packed_bytes(int(cout), C0 + C1, dt)
+        if want == 0 or packed.numel() != want:
+            raise ValueError(f"packed: {packed.numel()} bytes; {C0 + C1} -> {cout} channels of {dtype} take {want or 'no'} bytes "
+                             f"(multiples of 16 up to {_lib.CONV_MAX_CIN} in and {_lib.CONV_MAX_COUT} out are built)")
+        return dtype, dt, B, H, W, s0, C0, s1, C1
+
+    def raft_conv3x3(self, x0, packed, cout, x1=None, relu=False, out=None):
+        """conv(cat([x0, x1], dim=1)) of an nn.Conv2d(C0 + C1, cout, 3, padding=1) whose weights `packed` holds
+        (raft_conv3x3_pack, for the dtype of x0), with its bias and, with `relu`, torch's ReLU.  x0 [B,C0,H,W] and x1
+        [B,C1,H,W] or None are float32 or bfloat16 and may be channel slices of wider tensors.  -> [B,cout,H,W]; with `out`
+        nothing is allocated (include/vppx.h has the arithmetic)."""
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed, cout)
+        if out is None:
+            out = self.torch.empty((B, int(cout), H, W), dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", (B, int(cout), H, W))
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_conv3x3_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), B, H, W, int(bool(relu)),
+                                                     _ptr(out), so, dt, self.ctx.handle))
+        return out
+
+    def raft_gru_zr(self, x0, packed_zr, cz, cr, h, x1=None, z=None, rh=None):
+        """convz and convr of a ConvGRU (update.py:27-28) in one launch with their gates: `packed_zr` holds
+        cat([convz.weight, convr.weight]) and the biases likewise; x0 (and x1) are hx = cat([h, *x]), usually the whole
+        buffer raft_gru_assemble made.  -> (z, rh) = (sigmoid(convz(hx) + cz), sigmoid(convr(hx) + cr) * h), each [B,C,H,W].
+        `rh` must be a buffer of its own, not the h part of hx."""
+        Cc = h.shape[1]
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed_zr, 2 * Cc)
+        shape = (B, Cc, H, W)
+        sh = self._chk_frames(h, dtype, "h", shape)
+        sz, sr = self._chk_frames(cz, dtype, "cz", shape), self._chk_frames(cr, dtype, "cr", shape)
+        if z is None:
+            z = self.torch.empty(shape, dtype=dtype, device=self.device)
+        if rh is None:
+            rh = self.torch.empty(shape, dtype=dtype, device=self.device)
+        soz, sor = self._chk_frames(z, dtype, "z", shape), self._chk_frames(rh, dtype, "rh", shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_gru_zr_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed_zr), _ptr(cz), sz, _ptr(cr), sr,
+                                                    _ptr(h), sh, _ptr(z), soz, _ptr(rh), sor, B, Cc, H, W, dt, self.ctx.handle))
+        return z, rh
+
+    def raft_gru_q(self, x0, packed_q, cq, z, h, x1=None, out=None):
+        """convq of a ConvGRU with the rest of its forward (update.py:29-31): x0 = rh of raft_gru_zr and x1 = the x part of
+        hx (hx[:, C:]) are cat([r*h, x]); -> (1 - z) * h + z * tanh(convq(.) + cq).  `out` may be `h`."""
+        Cc = h.shape[1]
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed_q, Cc)
+        shape = (B, Cc, H, W)
+        sh = self._chk_frames(h, dtype, "h", shape)
+        sq, sz = self._chk_frames(cq, dtype, "cq", shape), self._chk_frames(z, dtype, "z", shape)
+        if out is None:
+            out = self.torch.empty(shape, dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_gru_q_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed_q), _ptr(cq), sq, _ptr(z), sz, _ptr(h),
+                                                   sh, _ptr(out), so, B, Cc, H, W, dt, self.ctx.handle))
         return out
 
     # ---- the encoders' glue: what ResidualBlock.forward runs between its convolutions ----

@@ -15,6 +15,12 @@ that buffer, which convq then reads as cat([r*h, x]), and one launch makes the n
 relu(convc1(lookup)) and relu(convf1(flow)) (`Engine.raft_motion_front`) and the 36-channel tensor between the lookup and
 convc1 is never written; convc2, convf2 and conv stay torch's.  It is opt-in: README.md has what was measured.
 
+`FusedUpdate(block, gru_conv=True)` takes the nine gate convolutions too: a GRU is then the assembly and two launches,
+convz + convr with their gates (`Engine.raft_gru_zr`) and convq with the rest of ConvGRU.forward (`Engine.raft_gru_q`), on the
+matrix cores (bfloat16 MFMA for bfloat16 storage, the float32 matrix path for float32).  The packed weights are kept per GRU and
+made again when a parameter, the dtype or the device changes; a GRU whose channel counts the kernel does not take runs as
+without the flag.  It is opt-in: README.md has what was measured.
+
 Inference only: the hidden state of a level is overwritten inside a buffer that is reused from call to call, which
 autograd cannot follow.  float32 or bfloat16; a tensor of another dtype than the hidden state's (a convolution's output
 under autocast) is converted to it, and a dtype the kernels do not store (float16) is an error.
@@ -41,17 +47,52 @@ class GruGlue:
 
     def __init__(self):
         self._hx = {}                      # level (or the GRU's id) -> the hx buffer of that GRU
+        self._gates = {}                   # (level, "z" / "rh") -> the z and r*h buffers of that GRU (conv=True)
+        self._packed = {}                  # the GRU's id -> (what they were made from, packed convz + convr, packed convq)
 
-    def _buffer(self, level, shape, dtype, device):
-        """The hx buffer of a level: kept from call to call, made again when its shape, dtype or device changes."""
-        buf = self._hx.get(level)
+    def _buffer(self, level, shape, dtype, device, kept=None):
+        """The hx buffer of a level (or a buffer of `kept`): kept from call to call, made again when its shape, dtype or device
+        changes."""
+        kept = self._hx if kept is None else kept
+        buf = kept.get(level)
         if buf is None or tuple(buf.shape) != tuple(shape) or buf.dtype != dtype or buf.device != device:
-            buf = self._hx[level] = torch.empty(tuple(shape), dtype=dtype, device=device)
+            buf = kept[level] = torch.empty(tuple(shape), dtype=dtype, device=device)
         return buf
 
-    def fused_gru(self, gru, h, cz, cr, cq, *x_list, level=None):
+    @staticmethod
+    def _conv_takes(gru, hidden, channels):
+        """Whether the convolution kernel takes this GRU: three plain 3x3 convolutions of `channels` -> `hidden` channels within
+        what include/vppx.h says is built."""
+        from . import _lib
+        if hidden % 16 or channels % 16 or channels > _lib.CONV_MAX_CIN or 2 * hidden > _lib.CONV_MAX_COUT:
+            return False
+        for conv in (gru.convz, gru.convr, gru.convq):
+            pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)        # noqa: E731
+            if (tuple(conv.weight.shape) != (hidden, channels, 3, 3) or pair(getattr(conv, "padding", 1)) != (1, 1)
+                    or pair(getattr(conv, "stride", 1)) != (1, 1) or pair(getattr(conv, "dilation", 1)) != (1, 1)
+                    or getattr(conv, "groups", 1) != 1 or getattr(conv, "padding_mode", "zeros") != "zeros"):
+                return False
+        return True
+
+    def _packed_weights(self, eng, gru, dtype, device):
+        """(packed convz + convr, packed convq) of a GRU: made once, and again when the device, the dtype or a parameter changes."""
+        params = [p for conv in (gru.convz, gru.convr, gru.convq) for p in (conv.weight, conv.bias)]
+        stamp = (device, dtype, tuple(None if p is None else (id(p), p._version) for p in params))
+        kept = self._packed.get(id(gru))
+        if kept is None or kept[0] != stamp:
+            wz, bz, wr, br, wq, bq = params
+            bzr = None if bz is None and br is None else torch.cat([
+                torch.zeros(w.shape[0], dtype=w.dtype, device=w.device) if b is None else b.detach() for w, b in ((wz, bz), (wr, br))])
+            kept = self._packed[id(gru)] = (stamp, eng.raft_conv3x3_pack(torch.cat([wz.detach(), wr.detach()]), bzr, dtype=dtype),
+                                            eng.raft_conv3x3_pack(wq, bq, dtype=dtype))
+        return kept[1], kept[2]
+
+    def fused_gru(self, gru, h, cz, cr, cq, *x_list, level=None, conv=False):
         """One ConvGRU.forward (update.py:23-32).  An entry of x_list is a tensor, taken as it is, or (tensor, "pool2x")
-        / (tensor, "interp"), resampled to h's size on its way into hx.  -> the new hidden state, a new tensor."""
+        / (tensor, "interp"), resampled to h's size on its way into hx.  -> the new hidden state, a new tensor.
+        conv=True: the three convolutions run on the library's kernel with the gates as their epilogues, two launches behind
+        the assembly (`Engine.raft_gru_zr`, `raft_gru_q`); a GRU whose channel counts that kernel does not take runs as with
+        conv=False."""
         dtype = h.dtype
         eng = _engine(h.device)
         h = _as(h, dtype)
@@ -63,6 +104,14 @@ class GruGlue:
         channels = sum(t.shape[1] for t, _ in sources)
         hx = self._buffer(id(gru) if level is None else level, (B, channels, H, W), dtype, h.device)
         eng.raft_gru_assemble(sources, out=hx)
+        hidden = h.shape[1]
+        if conv and dtype in (torch.float32, torch.bfloat16) and self._conv_takes(gru, hidden, channels):
+            key = id(gru) if level is None else level
+            packed_zr, packed_q = self._packed_weights(eng, gru, dtype, h.device)
+            z = self._buffer((key, "z"), h.shape, dtype, h.device, self._gates)
+            rh = self._buffer((key, "rh"), h.shape, dtype, h.device, self._gates)   # not the h part of hx: other tiles read it as halo
+            eng.raft_gru_zr(hx, packed_zr, _as(cz, dtype), _as(cr, dtype), h, z=z, rh=rh)
+            return eng.raft_gru_q(rh, packed_q, _as(cq, dtype), z, h, x1=hx[:, hidden:] if channels > hidden else None)
         az = _as(gru.convz(hx), dtype)
         ar = _as(gru.convr(hx), dtype)
         cz, cr, cq = _as(cz, dtype), _as(cr, dtype), _as(cq, dtype)
@@ -74,20 +123,22 @@ class GruGlue:
 _glue = GruGlue()
 
 
-def fused_gru(gru, h, cz, cr, cq, *x_list):
-    """`gru(h, cz, cr, cq, *x_list)` of a ConvGRU (update.py:23-32) with its glue on the device; see GruGlue.fused_gru."""
+def fused_gru(gru, h, cz, cr, cq, *x_list, conv=False):
+    """`gru(h, cz, cr, cq, *x_list)` of a ConvGRU (update.py:23-32) with its glue on the device, and with conv=True its
+    convolutions as well; see GruGlue.fused_gru."""
     with torch.no_grad():
-        return _glue.fused_gru(gru, h, cz, cr, cq, *x_list)
+        return _glue.fused_gru(gru, h, cz, cr, cq, *x_list, conv=conv)
 
 
 class FusedUpdate(torch.nn.Module, GruGlue):
     """A module, so that it can take the block's place as `self.update_block` of a RAFTStereo; the block is its only child
     (`state_dict` keys gain the prefix `block.`: wrap after the weights are loaded)."""
 
-    def __init__(self, block, motion_front=False):
+    def __init__(self, block, motion_front=False, gru_conv=False):
         torch.nn.Module.__init__(self)
         GruGlue.__init__(self)
         self.motion_front = bool(motion_front)
+        self.gru_conv = bool(gru_conv)
         for name in ("encoder", "gru08", "gru16", "gru32", "flow_head", "mask", "n_gru_layers"):
             if not hasattr(block, name):
                 raise TypeError(f"FusedUpdate: the block has no {name!r}")
@@ -132,14 +183,14 @@ class FusedUpdate(torch.nn.Module, GruGlue):
         blk = self.block
         n = blk.n_gru_layers
         if iter32:                         # reads the old net[1]
-            net[2] = self.fused_gru(blk.gru32, net[2], *(inp[2]), (net[1], "pool2x"), level=32)
+            net[2] = self.fused_gru(blk.gru32, net[2], *(inp[2]), (net[1], "pool2x"), level=32, conv=self.gru_conv)
         if iter16:                         # reads the old net[0] and the new net[2]
             x = [(net[0], "pool2x")] + ([(net[2], "interp")] if n > 2 else [])
-            net[1] = self.fused_gru(blk.gru16, net[1], *(inp[1]), *x, level=16)
+            net[1] = self.fused_gru(blk.gru16, net[1], *(inp[1]), *x, level=16, conv=self.gru_conv)
         if iter08:                         # reads the new net[1]
             out, fl = self._motion(flow, corr)
             x = [out, fl] + ([(net[1], "interp")] if n > 1 else [])
-            net[0] = self.fused_gru(blk.gru08, net[0], *(inp[0]), *x, level=8)
+            net[0] = self.fused_gru(blk.gru08, net[0], *(inp[0]), *x, level=8, conv=self.gru_conv)
         if not update:
             return net
         delta_flow = blk.flow_head(net[0])
