@@ -19,12 +19,17 @@ convc1 is never written; convc2, convf2 and conv stay torch's.  It is opt-in: RE
 convz + convr with their gates (`Engine.raft_gru_zr`) and convq with the rest of ConvGRU.forward (`Engine.raft_gru_q`), on the
 matrix cores (bfloat16 MFMA for bfloat16 storage, the float32 matrix path for float32).  The packed weights are kept per GRU and
 made again when a parameter, the dtype or the device changes; a GRU whose channel counts the kernel does not take runs as
-without the flag.  It is opt-in: README.md has what was measured.
+without the flag.  It is opt-in: README.md has what was measured.  The cache rule: a parameter has changed when it is another
+object, when its storage has moved (`p.data = new`, `.to()`, `load_state_dict(assign=True)`) or when its version counter has
+(`p.copy_()` under no_grad, `load_state_dict`); an entry lives no longer than its GRU.  A write through `p.data`
+(`p.data.copy_()`, `p.data.mul_()`) shows in neither and keeps the old packed weights: call `forget_weights()` after one.
 
 Inference only: the hidden state of a level is overwritten inside a buffer that is reused from call to call, which
 autograd cannot follow.  float32 or bfloat16; a tensor of another dtype than the hidden state's (a convolution's output
 under autocast) is converted to it, and a dtype the kernels do not store (float16) is an error.
 """
+import weakref
+
 import torch
 import torch.nn.functional as F
 
@@ -48,7 +53,8 @@ class GruGlue:
     def __init__(self):
         self._hx = {}                      # level (or the GRU's id) -> the hx buffer of that GRU
         self._gates = {}                   # (level, "z" / "rh") -> the z and r*h buffers of that GRU (conv=True)
-        self._packed = {}                  # the GRU's id -> (what they were made from, packed convz + convr, packed convq)
+        self._packed = {}                  # the GRU's id -> (what they were made from, packed convz + convr, packed convq,
+        #                                    a weak reference to the GRU, the parameter objects)
 
     def _buffer(self, level, shape, dtype, device, kept=None):
         """The hx buffer of a level (or a buffer of `kept`): kept from call to call, made again when its shape, dtype or device
@@ -75,17 +81,41 @@ class GruGlue:
         return True
 
     def _packed_weights(self, eng, gru, dtype, device):
-        """(packed convz + convr, packed convq) of a GRU: made once, and again when the device, the dtype or a parameter changes."""
+        """(packed convz + convr, packed convq) of a GRU: made once, and again when the device, the dtype or a parameter changes.
+        A parameter has changed when it is another object, when its storage lies elsewhere (`p.data = new`, `.to()`,
+        `load_state_dict(assign=True)`: what FusedEncoder._norm_consts looks at too) or when its version counter has moved (an
+        in-place write, `load_state_dict`).  A write THROUGH `p.data` (`p.data.copy_()`, `p.data.mul_()`) moves neither and cannot
+        be seen: call forget_weights() after one.  The entry holds its parameter objects, so their ids cannot come back under
+        other tensors while it lives, and it goes when its GRU does: a later GRU at the same address never meets it."""
         params = [p for conv in (gru.convz, gru.convr, gru.convq) for p in (conv.weight, conv.bias)]
-        stamp = (device, dtype, tuple(None if p is None else (id(p), p._version) for p in params))
-        kept = self._packed.get(id(gru))
+        stamp = (device, dtype, tuple(None if p is None else (id(p), p.data_ptr(), p._version) for p in params))
+        key = id(gru)
+        kept = self._packed.get(key)
+        if kept is not None and kept[3] is not None and kept[3]() is not gru:      # the entry of a GRU that is gone
+            kept = None
         if kept is None or kept[0] != stamp:
             wz, bz, wr, br, wq, bq = params
             bzr = None if bz is None and br is None else torch.cat([
                 torch.zeros(w.shape[0], dtype=w.dtype, device=w.device) if b is None else b.detach() for w, b in ((wz, bz), (wr, br))])
-            kept = self._packed[id(gru)] = (stamp, eng.raft_conv3x3_pack(torch.cat([wz.detach(), wr.detach()]), bzr, dtype=dtype),
-                                            eng.raft_conv3x3_pack(wq, bq, dtype=dtype))
+            store = self._packed
+
+            def gone(ref, key=key, store=store):     # the GRU was freed: its packed weights go with it
+                hit = store.get(key)
+                if hit is not None and hit[3] is ref:
+                    del store[key]
+
+            try:
+                ref = weakref.ref(gru, gone)
+            except TypeError:                        # an object that takes no weak reference: the held parameters still pin the ids
+                ref = None
+            kept = store[key] = (stamp, eng.raft_conv3x3_pack(torch.cat([wz.detach(), wr.detach()]), bzr, dtype=dtype),
+                                 eng.raft_conv3x3_pack(wq, bq, dtype=dtype), ref, tuple(params))
         return kept[1], kept[2]
+
+    def forget_weights(self):
+        """Drop every packed weight: the next call with conv=True packs again.  For the one change _packed_weights cannot see,
+        a write through `p.data` (`p.data.copy_(new)`, `p.data.mul_(2)`)."""
+        self._packed.clear()
 
     def fused_gru(self, gru, h, cz, cr, cq, *x_list, level=None, conv=False):
         """One ConvGRU.forward (update.py:23-32).  An entry of x_list is a tensor, taken as it is, or (tensor, "pool2x")
