@@ -29,6 +29,9 @@
  *   BasicMotionEncoder convc1 / convf1  raft_stereo/update.py:80,82 vppx_raft_motion_front_dt_dev
  *   ResidualBlock norm / relu / sum     raft_stereo/extractor.py:48-60 vppx_raft_norm_stats_dt_dev, vppx_raft_norm_apply_dt_dev
  *   ConvGRU convz / convr / convq + gates raft_stereo/update.py:19-32 vppx_raft_gru_zr_dt_dev, vppx_raft_gru_q_dt_dev, vppx_raft_conv3x3_dt_dev
+ *   BasicMotionEncoder convc2 / convf2 / conv raft_stereo/update.py:81,83,86 vppx_raft_conv_dt_dev
+ *   FlowHead conv1 / conv2              raft_stereo/update.py:34-42 vppx_raft_conv_dt_dev
+ *   BasicMultiUpdateBlock.mask, .25 *   raft_stereo/update.py:113-116,141 vppx_raft_conv_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -967,7 +970,30 @@ int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane);
  * Refused before anything is launched, with no output byte touched: a NULL weight, packed, x0, x1 with C1 > 0, cz, cr, cq, h,
  * z, rh or out; B, H, W, C0, Cout or C <= 0, C1 < 0; a frame stride below its tensor's size; a dtype other than the two; a
  * packed pointer that is not 16-byte aligned (VPPX_E_INVALID_ARG); C0, C1, Cout or C not a multiple of 16, C0 + C1 above
- * VPPX_CONV_MAX_CIN, Cout (2C for the zr call) above VPPX_CONV_MAX_COUT, B*H*W above 2^31 - 1 (VPPX_E_UNSUPPORTED). */
+ * VPPX_CONV_MAX_CIN, Cout (2C for the zr call) above VPPX_CONV_MAX_COUT, B*H*W above 2^31 - 1 (VPPX_E_UNSUPPORTED).
+ *
+ * The update block's other convolutions (update.py:34-42 FlowHead, :81,83,86 convc2 / convf2 / conv, :113-116 mask and the
+ * `.25 *` of :141): vppx_raft_conv_* is the plain call above with three things more.  Everything said above about the input,
+ * the two dtypes, the order of the sum, the padding of K, the alignment routes, stream order and "allocates nothing" holds.
+ *   Cout is any count from 1 to VPPX_CONV_MAX_COUT.  The packing pads the output channels to the next multiple of 16 with rows
+ *     whose weights and bias are +0 and writes every byte of the buffer; the call stores channel m only where m < Cout, so out
+ *     may be channels [0, Cout) of a wider tensor and no cell behind channel Cout - 1 of a frame is written.  For Cout % 16 == 0
+ *     and ksize 3 the size and the packed bytes are those of vppx_raft_conv3x3_*.
+ *   ksize is 3 (as above) or 1: nn.Conv2d(Cin, Cout, 1), weight [Cout][Cin][1][1], acc[b][m][y][x] = sum over c < Cin of
+ *     w[m][c] * in[b][c][y][x].  Nothing outside the map is read.  A NaN or infinite input cell reaches its own pixel, in every
+ *     output channel of its frame, and no other cell; for ksize 3 the 3x3 pixels around it, as above.
+ *   scale:  v = acc + bias[m];  relu: v = v < 0 ? 0 : v (a NaN stays NaN);  out[b][m] = v * scale, one correctly rounded float32
+ *     multiplication; scale == 1.0f gives the bits of the call without it.  A bfloat16 result is that float32 product rounded
+ *     once, to nearest even.  For a power of two (the mask's .25) this equals rounding v and then the product, as torch does,
+ *     except where the product is subnormal.
+ * For ksize 3, Cout % 16 == 0 and scale 1.0f, vppx_raft_conv_dt_dev gives the bits of vppx_raft_conv3x3_dt_dev.
+ * vppx_raft_conv_packed_bytes is 0 for what is not built: Cout outside 1 .. VPPX_CONV_MAX_COUT, Cin not a positive multiple of
+ * 16 up to VPPX_CONV_MAX_CIN, a ksize other than 1 and 3, a dtype other than the two.
+ * Refused before anything is launched, with no output byte touched: a NULL weight, packed, x0, x1 with C1 > 0 or out; B, H, W, C0
+ * or Cout <= 0, C1 < 0; a frame stride below its tensor's size; a scale that is not finite; a dtype other than the two; a packed
+ * pointer that is not 16-byte aligned (VPPX_E_INVALID_ARG); a ksize other than 1 and 3, C0 or C1 not a multiple of 16, C0 + C1
+ * above VPPX_CONV_MAX_CIN, Cout above VPPX_CONV_MAX_COUT, B*H*W above 2^31 - 1 or more tiles than one launch takes
+ * (VPPX_E_UNSUPPORTED). */
 #define VPPX_CONV_MAX_CIN 512
 #define VPPX_CONV_MAX_COUT 256
 size_t vppx_raft_conv3x3_packed_bytes(int Cout, int Cin, int dtype);
@@ -983,6 +1009,11 @@ int vppx_raft_gru_q_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, cons
                            const void *packed_q, const void *cq, int64_t cq_frame_stride, const void *z, int64_t z_frame_stride,
                            const void *h, int64_t h_frame_stride, void *out, int64_t out_frame_stride, int B, int C, int H, int W,
                            int dtype, vppx_ctx *ctx);
+size_t vppx_raft_conv_packed_bytes(int Cout, int Cin, int ksize, int dtype);
+int vppx_raft_conv_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed, vppx_ctx *ctx);
+int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                          const void *packed, int Cout, int ksize, int B, int H, int W, int relu, float scale, void *out,
+                          int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

@@ -19,6 +19,9 @@
 // (one LDS image, two barriers per chunk).  The weights come from the packed buffer in fragment order, [chunk][tap][N tile][lane] 16 bytes: a wave's B
 // fragment is 1 KiB of contiguous memory, the same for the four waves of a workgroup, read one step ahead of its use.
 // A packed weight of a channel beyond Cin is +0 and meets only the +0 the staging wrote, never a cell of the input.
+//
+// The plain epilogue also serves the update block's other convolutions (vppx_raft_conv_*): any Cout >= 1 (the packing pads the
+// output channels to 16 with +0 rows and +0 bias slots, the store skips channel m >= Cout), a 1x1 kernel (TAPS = 1) and a scale.
 #include "cells.h"
 #include "gru_math.h"
 
@@ -43,9 +46,11 @@ struct ConvArgs {
     long long se0, se1, se2;
     void *o0, *o1;           // plain: out;  zr: z, rh;  q: out
     long long so0, so1;
-    int C0, Cin, NT, nchunks; // NT = Cout / 16
+    int C0, Cin, NT, nchunks; // NT = ceil(Cout / 16): the packing pads the output channels with rows of +0
     int H, W, tilesX, tilesY;
     int C, relu, vec;        // C: the hidden size of the gates;  vec: 16-byte groups in the epilogue
+    int Cout;                // plain: channel m is stored where m < Cout (the gates' Cout is NT * 16)
+    float scale;             // plain: out = relu(v) * scale
 };
 
 // Eight cells of a [B,C,H,W] tensor from cell `at` on, the first `nv` of them inside the row.  vec: every base, stride, plane
@@ -86,9 +91,12 @@ __device__ __forceinline__ void cv_store8(void *p, size_t at, int nv, bool vec, 
         if (j < nv) store_cell<BF16>(p, at + j, c[j]);
 }
 
-template <bool BF16, int EPI>
+// TAPS = 9: the 3x3 convolution.  TAPS = 1: a 1x1 convolution as the centre tap of the same staged image; its halo slots are
+// written as +0 without a read, so that nothing but the tile's own pixels is fetched.
+template <bool BF16, int EPI, int TAPS>
 __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 {
+    static_assert(TAPS == 9 || TAPS == 1, "3x3 or 1x1");
     constexpr int CK = BF16 ? 32 : 16;
     __shared__ __attribute__((aligned(16))) unsigned char sA[CV_HALO * CV_ROWB];
 
@@ -111,9 +119,11 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     int offA, offB; // y * W + x of the two pixels, -1 outside the map
     {
         const int ryA = tid / CV_HW, rxA = tid - ryA * CV_HW, gyA = y0 + ryA - 1, gxA = x0 + rxA - 1;
-        offA = gyA >= 0 && gyA < H && gxA >= 0 && gxA < W ? gyA * W + gxA : -1;
+        const bool inA = TAPS == 9 || (ryA >= 1 && ryA <= CV_TH && rxA >= 1 && rxA <= CV_TW);
+        offA = inA && gyA >= 0 && gyA < H && gxA >= 0 && gxA < W ? gyA * W + gxA : -1;
         const int ryB = pB / CV_HW, rxB = pB - ryB * CV_HW, gyB = y0 + ryB - 1, gxB = x0 + rxB - 1;
-        offB = uB < 3 && gyB >= 0 && gyB < H && gxB >= 0 && gxB < W ? gyB * W + gxB : -1;
+        const bool inB = TAPS == 9 || (ryB >= 1 && ryB <= CV_TH && rxB >= 1 && rxB <= CV_TW);
+        offB = inB && uB < 3 && gyB >= 0 && gyB < H && gxB >= 0 && gxB < W ? gyB * W + gxB : -1;
     }
     auto unit = [&](int chunk, int u, int off) -> u32 {
         const int c = chunk * CK + (BF16 ? 2 * u : u);
@@ -149,7 +159,7 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 
     const uint4 *pk = a.packed + (size_t)(4 * nb) * 64 + lane;
     const size_t step = (size_t)a.NT * 64; // fragments of one (chunk, tap)
-    const int nsteps = a.nchunks * 9;
+    const int nsteps = a.nchunks * TAPS;
     uint4 bcur[4], bnext[4];
 #pragma unroll
     for (int n = 0; n < 4; n++) bcur[n] = n < ntl ? pk[64 * n] : make_uint4(0, 0, 0, 0);
@@ -166,14 +176,14 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
         __syncthreads();
         if (chunk + 1 < a.nchunks) fetch(chunk + 1); // in flight during this chunk's matrix instructions
 #pragma unroll
-        for (int tap = 0; tap < 9; tap++) {
-            const int s = chunk * 9 + tap;
+        for (int tap = 0; tap < TAPS; tap++) {
+            const int s = chunk * TAPS + tap;
             if (s + 1 < nsteps) {
 #pragma unroll
                 for (int n = 0; n < 4; n++)
                     if (n < ntl) bnext[n] = pk[(size_t)(s + 1) * step + 64 * n];
             }
-            const int toff = ((tap / 3) * CV_HW + tap % 3) * CV_ROWB;
+            const int toff = (TAPS == 9 ? (tap / 3) * CV_HW + tap % 3 : CV_HW + 1) * CV_ROWB;
             uint4 fa[4];
 #pragma unroll
             for (int m = 0; m < 4; m++) fa[m] = *(const uint4 *)(sA + la[m] + toff);
@@ -218,13 +228,14 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
         for (int n = 0; n < 4; n++) {
             if (n >= ntl) break;
             const int m = 64 * nb + 16 * n + i;
-            const float bias = a.bias[m];
+            const float bias = a.bias[m]; // m < 16 * NT: a padding channel reads the +0 the packing wrote
+            if (EPI == CV_PLAIN && m >= a.Cout) continue; // per lane: neither the 16-byte route nor the cell route stores it
             float v[8], o[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) v[j] = __fadd_rn(acc[2 * p + (j >> 2)][n][j & 3], bias);
             if (EPI == CV_PLAIN) {
 #pragma unroll
-                for (int j = 0; j < 8; j++) o[j] = a.relu ? relu_nan(v[j]) : v[j];
+                for (int j = 0; j < 8; j++) o[j] = __fmul_rn(a.relu ? relu_nan(v[j]) : v[j], a.scale);
                 cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
             } else if (EPI == CV_ZR) {
                 float c[8];
@@ -256,31 +267,32 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 }
 
 // ---------------------------------------------------------------------------------------
-// the packing: torch's [Cout][Cin][3][3] float32 -> fragment order, channels beyond Cin as +0, the bias behind
+// the packing: torch's [Cout][Cin][k][k] float32 (taps = k * k) -> fragment order, input channels beyond Cin and output
+// channels beyond Cout as +0, the bias behind: NT * 16 slots, +0 beyond Cout.  Every fragment and slot is written.
 // ---------------------------------------------------------------------------------------
-// fragment f = ((chunk * 9 + tap) * NT + N tile) * 64 + lane holds, for lane = 16 g + i, output channel 16 * tile + i and
+// fragment f = ((chunk * taps + tap) * NT + N tile) * 64 + lane holds, for lane = 16 g + i, output channel 16 * tile + i and
 //   bfloat16: element j = input channel 32 * chunk + 8 g + j          (the 16x16x32 B map: k = 8 (lane >> 4) + j)
 //   float32:  element j = input channel 16 * chunk + 4 g + j          (k-step j of the chunk, 16x16x4 B map: k = lane >> 4)
 template <bool BF16>
-__global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, const float *bias, int Cout, int Cin, int nchunks, void *packed)
+__global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, const float *bias, int Cout, int Cin, int nchunks, int taps, void *packed)
 {
     constexpr int E = BF16 ? 8 : 4, CK = BF16 ? 32 : 16;
-    const int NT = Cout / 16;
-    const size_t nfrag = (size_t)nchunks * 9 * NT * 64;
+    const int NT = (Cout + 15) / 16;
+    const size_t nfrag = (size_t)nchunks * taps * NT * 64;
     const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (f < (size_t)Cout) ((float *)((uint4 *)packed + nfrag))[f] = bias ? bias[f] : 0.0f;
+    if (f < (size_t)NT * 16) ((float *)((uint4 *)packed + nfrag))[f] = bias && f < (size_t)Cout ? bias[f] : 0.0f; // nfrag >= 64 NT
     if (f >= nfrag) return;
     const int lane = (int)(f & 63), g = lane >> 4, i = lane & 15;
     size_t r = f >> 6;
     const int tile = (int)(r % NT);
     r /= NT;
-    const int tap = (int)(r % 9), chunk = (int)(r / 9);
+    const int tap = (int)(r % taps), chunk = (int)(r / taps);
     const int m = 16 * tile + i;
     float v[E];
 #pragma unroll
     for (int j = 0; j < E; j++) {
         const int c = CK * chunk + E * g + j;
-        v[j] = c < Cin ? w[((size_t)m * Cin + c) * 9 + tap] : 0.0f;
+        v[j] = c < Cin && m < Cout ? w[((size_t)m * Cin + c) * taps + tap] : 0.0f;
     }
     if (BF16) {
         u32 h[8];
@@ -297,33 +309,44 @@ __global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, 
 // ---------------------------------------------------------------------------------------
 static int conv_chunks(int Cin, int dtype) { return dtype == VPPX_DT_BF16 ? (Cin + 31) / 32 : (Cin + 15) / 16; }
 
-static size_t conv_weight_bytes(int Cout, int Cin, int dtype) { return (size_t)conv_chunks(Cin, dtype) * 9 * (Cout / 16) * 64 * 16; }
+static int conv_ntiles(int Cout) { return (Cout + 15) / 16; }
 
-size_t conv3x3_packed_bytes(int Cout, int Cin, int dtype) { return conv_weight_bytes(Cout, Cin, dtype) + (size_t)Cout * sizeof(float); }
-
-int conv3x3_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed)
+static size_t conv_weight_bytes(int Cout, int Cin, int ksize, int dtype)
 {
-    const int nchunks = conv_chunks(Cin, dtype);
-    const size_t nfrag = (size_t)nchunks * 9 * (Cout / 16) * 64;
+    return (size_t)conv_chunks(Cin, dtype) * (ksize * ksize) * conv_ntiles(Cout) * 64 * 16;
+}
+
+// the fragments and one bias slot per PADDED output channel: for Cout % 16 == 0 what it has always been
+size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype)
+{
+    return conv_weight_bytes(Cout, Cin, ksize, dtype) + (size_t)conv_ntiles(Cout) * 16 * sizeof(float);
+}
+
+int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed)
+{
+    const int nchunks = conv_chunks(Cin, dtype), taps = ksize * ksize;
+    const size_t nfrag = (size_t)nchunks * taps * conv_ntiles(Cout) * 64;
     const unsigned blocks = (unsigned)((nfrag + 255) / 256);
     if (dtype == VPPX_DT_BF16)
-        raft_conv3x3_pack_kernel<true><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, packed);
+        raft_conv3x3_pack_kernel<true><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, taps, packed);
     else
-        raft_conv3x3_pack_kernel<false><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, packed);
+        raft_conv3x3_pack_kernel<false><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, taps, packed);
     VPPX_CHECK_LAUNCH();
     return 0;
 }
 
-int conv3x3_run(vppx_ctx *ctx, const char *who, int epi, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
-                const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
-                int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, int dtype)
+// ksize 1 and a Cout that is no multiple of 16 go with the plain epilogue only (vppx_api.hip sees to it)
+int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
+             const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
+             int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, float scale, int dtype)
 {
     const bool bf16 = dtype == VPPX_DT_BF16;
     ConvArgs a = {};
     a.x0 = x0, a.x1 = C1 ? x1 : x0, a.s0 = (long long)s0, a.s1 = C1 ? (long long)s1 : 0;
-    a.C0 = C0, a.Cin = C0 + C1, a.NT = Cout / 16, a.nchunks = conv_chunks(a.Cin, dtype);
+    a.C0 = C0, a.Cin = C0 + C1, a.NT = conv_ntiles(Cout), a.nchunks = conv_chunks(a.Cin, dtype);
+    a.Cout = Cout, a.scale = scale;
     a.packed = (const uint4 *)packed;
-    a.bias = (const float *)((const unsigned char *)packed + conv_weight_bytes(Cout, a.Cin, dtype));
+    a.bias = (const float *)((const unsigned char *)packed + conv_weight_bytes(Cout, a.Cin, ksize, dtype));
     a.e0 = e0, a.e1 = e1, a.e2 = e2, a.se0 = (long long)se0, a.se1 = (long long)se1, a.se2 = (long long)se2;
     a.o0 = o0, a.o1 = o1, a.so0 = (long long)so0, a.so1 = (long long)so1;
     a.H = H, a.W = W, a.tilesX = (W + CV_TW - 1) / CV_TW, a.tilesY = (H + CV_TH - 1) / CV_TH;
@@ -341,15 +364,17 @@ int conv3x3_run(vppx_ctx *ctx, const char *who, int epi, const void *x0, int64_t
         if (ptrs[k]) vec = vec && aligned16(ptrs[k]) && strides[k] % V == 0;
     a.vec = vec;
     const dim3 grid((unsigned)tiles, (unsigned)((a.NT + 3) / 4));
-#define CONV_LAUNCH(BF, EP) raft_conv3x3_kernel<BF, EP><<<grid, 256, 0, ctx->stream>>>(a)
+#define CONV_LAUNCH(BF, EP, TAPS) raft_conv3x3_kernel<BF, EP, TAPS><<<grid, 256, 0, ctx->stream>>>(a)
     if (bf16) {
-        if (epi == CV_PLAIN) CONV_LAUNCH(true, CV_PLAIN);
-        else if (epi == CV_ZR) CONV_LAUNCH(true, CV_ZR);
-        else CONV_LAUNCH(true, CV_Q);
+        if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(true, CV_PLAIN, 1);
+        else if (epi == CV_PLAIN) CONV_LAUNCH(true, CV_PLAIN, 9);
+        else if (epi == CV_ZR) CONV_LAUNCH(true, CV_ZR, 9);
+        else CONV_LAUNCH(true, CV_Q, 9);
     } else {
-        if (epi == CV_PLAIN) CONV_LAUNCH(false, CV_PLAIN);
-        else if (epi == CV_ZR) CONV_LAUNCH(false, CV_ZR);
-        else CONV_LAUNCH(false, CV_Q);
+        if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(false, CV_PLAIN, 1);
+        else if (epi == CV_PLAIN) CONV_LAUNCH(false, CV_PLAIN, 9);
+        else if (epi == CV_ZR) CONV_LAUNCH(false, CV_ZR, 9);
+        else CONV_LAUNCH(false, CV_Q, 9);
     }
 #undef CONV_LAUNCH
     VPPX_CHECK_LAUNCH();

@@ -2881,11 +2881,20 @@ extern "C" int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane) {
 
 // The 3x3 convolution and ConvGRU's gates (conv_kernels.hip).  Flat arguments with the context last, as the encoders' glue;
 // every refusal comes before anything is launched.
-static int conv_channels_ok(const char *who, int C0, int C1, int Cout)
+// any_cout: the calls that take any Cout from 1 on (vppx_raft_conv_*); the others take multiples of 16
+static int conv_channels_ok(const char *who, int C0, int C1, int Cout, bool any_cout = false)
 {
     if (C0 <= 0 || C1 < 0 || Cout <= 0) {
         vppx_set_error("%s: %d + %d input and %d output channels: C0 and Cout must be positive, C1 not negative", who, C0, C1, Cout);
         return VPPX_E_INVALID_ARG;
+    }
+    if (any_cout) {
+        if (C0 % 16 || C1 % 16 || (int64_t)C0 + C1 > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT) {
+            vppx_set_error("%s: %d + %d input and %d output channels: multiples of 16 up to %d in and 1 to %d out are built", who, C0, C1,
+                           Cout, VPPX_CONV_MAX_CIN, VPPX_CONV_MAX_COUT);
+            return VPPX_E_UNSUPPORTED;
+        }
+        return 0;
     }
     if (C0 % 16 || C1 % 16 || Cout % 16 || (int64_t)C0 + C1 > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT) {
         vppx_set_error("%s: %d + %d input and %d output channels: multiples of 16 up to %d in and %d out are built", who, C0, C1, Cout,
@@ -2897,14 +2906,14 @@ static int conv_channels_ok(const char *who, int C0, int C1, int Cout)
 
 // everything the three calls share: the sources, the packed buffer, the sizes
 static int conv_call_ok(const char *who, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1, const void *packed, int Cout,
-                        int B, int H, int W, int dtype)
+                        int B, int H, int W, int dtype, bool any_cout = false)
 {
     int rc;
     if (!x0 || !packed || (C1 > 0 && !x1)) {
         vppx_set_error("%s: bad arguments", who);
         return VPPX_E_INVALID_ARG;
     }
-    if ((rc = gru_shape_ok(who, B, 1, H, W, dtype)) || (rc = conv_channels_ok(who, C0, C1, Cout))) return rc;
+    if ((rc = gru_shape_ok(who, B, 1, H, W, dtype)) || (rc = conv_channels_ok(who, C0, C1, Cout, any_cout))) return rc;
     if ((uintptr_t)packed % 16) {
         vppx_set_error("%s: the packed buffer is not 16-byte aligned", who);
         return VPPX_E_INVALID_ARG;
@@ -2922,7 +2931,7 @@ extern "C" size_t vppx_raft_conv3x3_packed_bytes(int Cout, int Cin, int dtype)
     if (Cout <= 0 || Cin <= 0 || Cout % 16 || Cin % 16 || Cin > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT ||
         (dtype != VPPX_DT_F32 && dtype != VPPX_DT_BF16))
         return 0;
-    return conv3x3_packed_bytes(Cout, Cin, dtype);
+    return conv_packed_bytes(Cout, Cin, 3, dtype);
 }
 
 extern "C" int vppx_raft_conv3x3_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed, vppx_ctx *ctx)
@@ -2940,7 +2949,7 @@ extern "C" int vppx_raft_conv3x3_pack_dev(const float *weight, const float *bias
         vppx_set_error("%s: the packed buffer is not 16-byte aligned", who);
         return VPPX_E_INVALID_ARG;
     }
-    return conv3x3_pack(ctx, weight, bias, Cout, Cin, dtype, packed);
+    return conv_pack(ctx, weight, bias, Cout, Cin, 3, dtype, packed);
 }
 
 extern "C" int vppx_raft_conv3x3_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
@@ -2957,8 +2966,65 @@ extern "C" int vppx_raft_conv3x3_dt_dev(const void *x0, int64_t x0_frame_stride,
     if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, B, H, W, dtype)) ||
         (rc = gru_stride_ok(who, "out", out_frame_stride, Cout, H, W)))
         return rc;
-    return conv3x3_run(ctx, who, 0, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
-                       out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, dtype);
+    return conv_run(ctx, who, 0, 3, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
+                    out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, 1.0f, dtype);
+}
+
+// Any Cout, ksize 3 or 1 and a scale: the motion encoder's tail, the flow head and the mask head (update.py:34-42, :83-87, :113-116).
+static int conv_ksize_ok(const char *who, int ksize)
+{
+    if (ksize == 1 || ksize == 3) return 0;
+    vppx_set_error("%s: a kernel size of %d: 1 and 3 are built", who, ksize);
+    return VPPX_E_UNSUPPORTED;
+}
+
+extern "C" size_t vppx_raft_conv_packed_bytes(int Cout, int Cin, int ksize, int dtype)
+{
+    if (Cout <= 0 || Cin <= 0 || Cin % 16 || Cin > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT || (ksize != 1 && ksize != 3) ||
+        (dtype != VPPX_DT_F32 && dtype != VPPX_DT_BF16))
+        return 0;
+    return conv_packed_bytes(Cout, Cin, ksize, dtype);
+}
+
+extern "C" int vppx_raft_conv_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed,
+                                       vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_conv_pack";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!weight || !packed) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok(who, dtype)) return VPPX_E_INVALID_ARG;
+    if ((rc = conv_channels_ok(who, Cin, 0, Cout, true)) || (rc = conv_ksize_ok(who, ksize))) return rc;
+    if ((uintptr_t)packed % 16) {
+        vppx_set_error("%s: the packed buffer is not 16-byte aligned", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    return conv_pack(ctx, weight, bias, Cout, Cin, ksize, dtype, packed);
+}
+
+extern "C" int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                     const void *packed, int Cout, int ksize, int B, int H, int W, int relu, float scale, void *out,
+                                     int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_raft_conv";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!out) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!std::isfinite(scale)) {
+        vppx_set_error("%s: the scale is not finite", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, B, H, W, dtype, true)) ||
+        (rc = gru_stride_ok(who, "out", out_frame_stride, Cout, H, W)) || (rc = conv_ksize_ok(who, ksize)))
+        return rc;
+    return conv_run(ctx, who, 0, ksize, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
+                    out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, scale, dtype);
 }
 
 extern "C" int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
@@ -2983,8 +3049,8 @@ extern "C" int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, 
         (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "z", z_frame_stride, C, H, W)) ||
         (rc = gru_stride_ok(who, "rh", rh_frame_stride, C, H, W)))
         return rc;
-    return conv3x3_run(ctx, who, 1, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_zr, 2 * C, cz, cz_frame_stride, cr,
-                       cr_frame_stride, h, h_frame_stride, z, z_frame_stride, rh, rh_frame_stride, B, C, H, W, 0, dtype);
+    return conv_run(ctx, who, 1, 3, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_zr, 2 * C, cz, cz_frame_stride, cr,
+                    cr_frame_stride, h, h_frame_stride, z, z_frame_stride, rh, rh_frame_stride, B, C, H, W, 0, 1.0f, dtype);
 }
 
 extern "C" int vppx_raft_gru_q_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
@@ -3003,8 +3069,8 @@ extern "C" int vppx_raft_gru_q_dt_dev(const void *x0, int64_t x0_frame_stride, i
     if ((rc = gru_stride_ok(who, "cq", cq_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "z", z_frame_stride, C, H, W)) ||
         (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "out", out_frame_stride, C, H, W)))
         return rc;
-    return conv3x3_run(ctx, who, 2, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_q, C, cq, cq_frame_stride, z, z_frame_stride, h,
-                       h_frame_stride, out, out_frame_stride, NULL, 0, B, C, H, W, 0, dtype);
+    return conv_run(ctx, who, 2, 3, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_q, C, cq, cq_frame_stride, z, z_frame_stride, h,
+                    h_frame_stride, out, out_frame_stride, NULL, 0, B, C, H, W, 0, 1.0f, dtype);
 }
 
 extern "C" int vppx_kitti_disp_decode_dev(vppx_ctx *ctx, const uint16_t *png_u16, int64_t n, float *disp, uint8_t *valid)

@@ -576,11 +576,13 @@ int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *
 
 // conv_kernels.hip: the 3x3 convolution on the matrix cores and ConvGRU's gates as its epilogues (update.py:19-32).
 // epi: 0 plain (o0 = out), 1 zr (e0, e1, e2 = cz, cr, h; o0, o1 = z, rh), 2 q (e0, e1, e2 = cq, z, h; o0 = out)
-size_t conv3x3_packed_bytes(int Cout, int Cin, int dtype);
-int conv3x3_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed);
-int conv3x3_run(vppx_ctx *ctx, const char *who, int epi, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
-                const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
-                int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, int dtype);
+// ksize 3 or 1.  The plain epilogue takes any Cout >= 1 (padded to 16 in the packing, masked in the store), ksize 1 and a scale;
+// the gates take ksize 3, Cout % 16 == 0 and ignore the scale.
+size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype);
+int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed);
+int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
+             const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
+             int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, float scale, int dtype);
 
 // norm_kernels.hip: the encoders' glue (models/raft_stereo/extractor.py:48-60, :181-183, :276-278)
 int norm_stats_pieces(int64_t planes, int64_t cells); // host arithmetic: workgroups per plane

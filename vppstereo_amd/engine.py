@@ -927,15 +927,18 @@ class Engine:
         _lib.check(self.lib.vppx_raft_conv3x3_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, dt, _ptr(packed), self.ctx.handle))
         return packed
 
-    def _packed_bytes(self, cout, cin, dt):
-        """vppx_raft_conv3x3_packed_bytes, asked once per (Cout, Cin, dtype): host arithmetic on constants."""
-        key = (cout, cin, dt)
+    def _packed_bytes(self, cout, cin, dt, ksize=None):
+        """vppx_raft_conv3x3_packed_bytes (ksize None) or vppx_raft_conv_packed_bytes, asked once per (Cout, Cin, dtype, ksize):
+        host arithmetic on constants."""
+        key = (cout, cin, dt) if ksize is None else (cout, cin, dt, ksize)
         if key not in self._conv_sizes:
-            self._conv_sizes[key] = int(self.lib.vppx_raft_conv3x3_packed_bytes(cout, cin, dt))
+            self._conv_sizes[key] = int(self.lib.vppx_raft_conv3x3_packed_bytes(cout, cin, dt) if ksize is None else
+                                        self.lib.vppx_raft_conv_packed_bytes(cout, cin, ksize, dt))
         return self._conv_sizes[key]
 
-    def _chk_conv(self, x0, x1, packed, cout):
-        """The sources and the packed weights of a convolution call -> (dtype, dt, B, H, W, s0, C0, s1, C1)."""
+    def _chk_conv(self, x0, x1, packed, cout, ksize=None):
+        """The sources and the packed weights of a convolution call -> (dtype, dt, B, H, W, s0, C0, s1, C1).  ksize None: the
+        3x3 calls that take multiples of 16 output channels; 1 or 3: raft_conv."""
         torch = self.torch
         dtype, dt = self._norm_dtype(x0, "x0")
         s0 = self._chk_frames(x0, dtype, "x0")
@@ -948,10 +951,11 @@ class Engine:
                 raise ValueError(f"x1: expected [{B},C1,{H},{W}], got {tuple(x1.shape)}")
         if getattr(packed, "device", None) != self.device or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
             raise ValueError(f"packed: expected what raft_conv3x3_pack returns, a torch.uint8 vector on {self.device}")
-        want = self._packed_bytes(int(cout), C0 + C1, dt)
+        want = self._packed_bytes(int(cout), C0 + C1, dt, ksize)
         if want == 0 or packed.numel() != want:
-            raise ValueError(f"packed: {packed.numel()} bytes; {C0 + C1} -> {cout} channels of {dtype} take {want or 'no'} bytes "
-                             f"(multiples of 16 up to {_lib.CONV_MAX_CIN} in and {_lib.CONV_MAX_COUT} out are built)")
+            built = (f"multiples of 16 up to {_lib.CONV_MAX_CIN} in and {_lib.CONV_MAX_COUT} out are built" if ksize is None else
+                     f"kernel sizes 1 and 3, multiples of 16 up to {_lib.CONV_MAX_CIN} in and 1 to {_lib.CONV_MAX_COUT} out are built")
+            raise ValueError(f"packed: {packed.numel()} bytes; {C0 + C1} -> {cout} channels of {dtype} take {want or 'no'} bytes ({built})")
         return dtype, dt, B, H, W, s0, C0, s1, C1
 
     def raft_conv3x3(self, x0, packed, cout, x1=None, relu=False, out=None):
@@ -966,6 +970,46 @@ class Engine:
         self._bind_stream()
         _lib.check(self.lib.vppx_raft_conv3x3_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), B, H, W, int(bool(relu)),
                                                      _ptr(out), so, dt, self.ctx.handle))
+        return out
+
+    def raft_conv_pack(self, weight, bias=None, dtype=None):
+        """raft_conv3x3_pack for raft_conv: the weights [Cout,Cin,k,k], k 1 or 3, of an nn.Conv2d(Cin, Cout, k, padding=k // 2) with
+        any Cout from 1 to CONV_MAX_COUT (Cin a multiple of 16).  -> an opaque torch.uint8 device tensor; for k = 3 and a Cout that is a
+        multiple of 16, the bytes raft_conv3x3_pack makes."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"dtype is {dtype}; the kernels store float32 and bfloat16")
+        dt = _lib.DT_BF16 if dtype == torch.bfloat16 else _lib.DT_F32
+        if (getattr(weight, "device", None) != self.device or weight.dim() != 4 or weight.shape[2] != weight.shape[3]
+                or weight.shape[2] not in (1, 3)):
+            raise ValueError(f"weight: expected a [Cout,Cin,k,k] tensor with k 1 or 3 on {self.device}")
+        Cout, Cin, ksize = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
+        weight = weight.detach().to(torch.float32).contiguous()
+        if bias is not None:
+            bias = bias.detach().to(torch.float32).contiguous()
+            self._chk(bias, torch.float32, 1, "bias", (Cout,))
+        size = self._packed_bytes(Cout, Cin, dt, ksize)
+        if size == 0:
+            raise ValueError(f"weight: {Cin} -> {Cout} channels: multiples of 16 up to {_lib.CONV_MAX_CIN} in and 1 to "
+                             f"{_lib.CONV_MAX_COUT} out are built")
+        packed = torch.empty((size,), dtype=torch.uint8, device=self.device)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_conv_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, ksize, dt, _ptr(packed), self.ctx.handle))
+        return packed
+
+    def raft_conv(self, x0, packed, cout, ksize, x1=None, relu=False, scale=1.0, out=None):
+        """conv(cat([x0, x1], dim=1)) of an nn.Conv2d(C0 + C1, cout, ksize, padding=ksize // 2), ksize 1 or 3, whose weights `packed`
+        holds (raft_conv_pack, for the dtype of x0): + bias, with `relu` torch's ReLU, then * scale (one float32 multiplication;
+        1.0 changes no bit).  cout is any count from 1 on; x0, x1 and `out` may be channel slices of wider tensors, and no cell of
+        `out`'s buffer outside its cout channels is written.  -> [B,cout,H,W]; with `out` nothing is allocated."""
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed, cout, int(ksize))
+        if out is None:
+            out = self.torch.empty((B, int(cout), H, W), dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", (B, int(cout), H, W))
+        self._bind_stream()
+        _lib.check(self.lib.vppx_raft_conv_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), int(ksize), B, H, W,
+                                                  int(bool(relu)), float(scale), _ptr(out), so, dt, self.ctx.handle))
         return out
 
     def raft_gru_zr(self, x0, packed_zr, cz, cr, h, x1=None, z=None, rh=None):

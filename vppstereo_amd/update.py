@@ -8,7 +8,7 @@ hx = cat([h, *x]) with pool2x (:89-90) and interp (:95-97) applied on the way, o
 that buffer, which convq then reads as cat([r*h, x]), and one launch makes the new hidden state
 (`Engine.raft_gru_assemble`, `raft_gru_reset`, `raft_gru_update`; include/vppx.h has the arithmetic).  The encoder's
 `cat([out, flow])` (:87) becomes two sources of gru08's hx.  The convolutions, their ReLUs, `flow_head`, `mask` and the
-`.25 *` stay torch's.
+`.25 *` stay torch's (but see convs=True below).
 
 `FusedUpdate(block, motion_front=True)` also takes the front of the motion encoder (update.py:80,82): given
 `corr = corr_fn.deferred(coords1)` (vppstereo_amd.corr.DeferredCorr) instead of the lookup's result, one launch makes
@@ -23,6 +23,20 @@ without the flag.  It is opt-in: README.md has what was measured.  The cache rul
 object, when its storage has moved (`p.data = new`, `.to()`, `load_state_dict(assign=True)`) or when its version counter has
 (`p.copy_()` under no_grad, `load_state_dict`); an entry lives no longer than its GRU.  A write through `p.data`
 (`p.data.copy_()`, `p.data.mul_()`) shows in neither and keeps the old packed weights: call `forget_weights()` after one.
+
+`FusedUpdate(block, convs=True)` takes the seven convolutions that are left: convc2, convf2 and conv of the motion encoder
+(update.py:81,83,86; conv reads cor and flo as two sources, so their `cat` is never written), conv1 and conv2 of the flow head
+(:34-42) and the two of the mask head with its `.25 *` (:113-116, :141), each one launch of `Engine.raft_conv` with its ReLU or
+its scale in the epilogue.  Each convolution is decided on its own: one that is not a plain nn.Conv2d (stride 1, dilation 1,
+groups 1, zero padding of k // 2, k 1 or 3, channel counts within what include/vppx.h says is built) runs in torch, as does
+everything when the hidden state is of a dtype the kernel does not store.  The packed weights follow the GRUs' cache rule, per
+convolution.  It is independent of the other two flags and opt-in: README.md has what was measured.
+
+A lookup that `_motion` itself materialises (a DeferredCorr with motion_front=False) is float32; for a bfloat16 block outside
+autocast it is converted to bfloat16 on its way into convc1, which would refuse it otherwise.  A tensor the caller passes is left alone.
+
+`forward(..., mask=False)` skips the mask head on either path and returns None in its place: in test_mode the reference
+computes the mask in every iteration and uses the last one (raft_stereo.py:146-153).
 
 Inference only: the hidden state of a level is overwritten inside a buffer that is reused from call to call, which
 autograd cannot follow.  float32 or bfloat16; a tensor of another dtype than the hidden state's (a convolution's output
@@ -54,7 +68,9 @@ class GruGlue:
         self._hx = {}                      # level (or the GRU's id) -> the hx buffer of that GRU
         self._gates = {}                   # (level, "z" / "rh") -> the z and r*h buffers of that GRU (conv=True)
         self._packed = {}                  # the GRU's id -> (what they were made from, packed convz + convr, packed convq,
-        #                                    a weak reference to the GRU, the parameter objects)
+        #                                    a weak reference to the GRU, the parameter objects); a single convolution's id
+        #                                    (convs=True) -> the same with its packed weights and None
+        self._bufs = {}                    # name -> a buffer between two convolutions of convs=True
 
     def _buffer(self, level, shape, dtype, device, kept=None):
         """The hx buffer of a level (or a buffer of `kept`): kept from call to call, made again when its shape, dtype or device
@@ -88,32 +104,47 @@ class GruGlue:
         be seen: call forget_weights() after one.  The entry holds its parameter objects, so their ids cannot come back under
         other tensors while it lives, and it goes when its GRU does: a later GRU at the same address never meets it."""
         params = [p for conv in (gru.convz, gru.convr, gru.convq) for p in (conv.weight, conv.bias)]
-        stamp = (device, dtype, tuple(None if p is None else (id(p), p.data_ptr(), p._version) for p in params))
-        key = id(gru)
-        kept = self._packed.get(key)
-        if kept is not None and kept[3] is not None and kept[3]() is not gru:      # the entry of a GRU that is gone
-            kept = None
-        if kept is None or kept[0] != stamp:
+
+        def make():
             wz, bz, wr, br, wq, bq = params
             bzr = None if bz is None and br is None else torch.cat([
                 torch.zeros(w.shape[0], dtype=w.dtype, device=w.device) if b is None else b.detach() for w, b in ((wz, bz), (wr, br))])
+            return (eng.raft_conv3x3_pack(torch.cat([wz.detach(), wr.detach()]), bzr, dtype=dtype),
+                    eng.raft_conv3x3_pack(wq, bq, dtype=dtype))
+
+        return self._packed_for(gru, params, make, dtype, device)
+
+    def _packed_conv(self, eng, conv, dtype, device):
+        """The packed weights of one plain convolution (convs=True): the same rule, the convolution in the GRU's place."""
+        make = lambda: (eng.raft_conv_pack(conv.weight, conv.bias, dtype=dtype), None)      # noqa: E731
+        return self._packed_for(conv, [conv.weight, conv.bias], make, dtype, device)[0]
+
+    def _packed_for(self, owner, params, make, dtype, device):
+        """The pair make() returns, kept under id(owner) while the device, the dtype and every parameter of `params` stay what they
+        were; the rule is _packed_weights'."""
+        stamp = (device, dtype, tuple(None if p is None else (id(p), p.data_ptr(), p._version) for p in params))
+        key = id(owner)
+        kept = self._packed.get(key)
+        if kept is not None and kept[3] is not None and kept[3]() is not owner:    # the entry of a module that is gone
+            kept = None
+        if kept is None or kept[0] != stamp:
             store = self._packed
 
-            def gone(ref, key=key, store=store):     # the GRU was freed: its packed weights go with it
+            def gone(ref, key=key, store=store):     # the module was freed: its packed weights go with it
                 hit = store.get(key)
                 if hit is not None and hit[3] is ref:
                     del store[key]
 
             try:
-                ref = weakref.ref(gru, gone)
+                ref = weakref.ref(owner, gone)
             except TypeError:                        # an object that takes no weak reference: the held parameters still pin the ids
                 ref = None
-            kept = store[key] = (stamp, eng.raft_conv3x3_pack(torch.cat([wz.detach(), wr.detach()]), bzr, dtype=dtype),
-                                 eng.raft_conv3x3_pack(wq, bq, dtype=dtype), ref, tuple(params))
+            first, second = make()
+            kept = store[key] = (stamp, first, second, ref, tuple(params))
         return kept[1], kept[2]
 
     def forget_weights(self):
-        """Drop every packed weight: the next call with conv=True packs again.  For the one change _packed_weights cannot see,
+        """Drop every packed weight, the GRUs' and the single convolutions': the next call with conv=True or convs=True packs again.  For the one change _packed_weights cannot see,
         a write through `p.data` (`p.data.copy_(new)`, `p.data.mul_(2)`)."""
         self._packed.clear()
 
@@ -164,11 +195,12 @@ class FusedUpdate(torch.nn.Module, GruGlue):
     """A module, so that it can take the block's place as `self.update_block` of a RAFTStereo; the block is its only child
     (`state_dict` keys gain the prefix `block.`: wrap after the weights are loaded)."""
 
-    def __init__(self, block, motion_front=False, gru_conv=False):
+    def __init__(self, block, motion_front=False, gru_conv=False, convs=False):
         torch.nn.Module.__init__(self)
         GruGlue.__init__(self)
         self.motion_front = bool(motion_front)
         self.gru_conv = bool(gru_conv)
+        self.convs = bool(convs)
         for name in ("encoder", "gru08", "gru16", "gru32", "flow_head", "mask", "n_gru_layers"):
             if not hasattr(block, name):
                 raise TypeError(f"FusedUpdate: the block has no {name!r}")
@@ -183,20 +215,87 @@ class FusedUpdate(torch.nn.Module, GruGlue):
                 raise
             return getattr(block, name)
 
-    def _motion(self, flow, corr):
-        """BasicMotionEncoder.forward (update.py:79-87) up to its last cat: -> (out [B,126,H,W], flow)."""
+    @staticmethod
+    def _conv_plain(conv, cin):
+        """Whether Engine.raft_conv takes this module on `cin` input channels: an nn.Conv2d whose forward is nn.Conv2d's, 1x1 or
+        3x3, stride 1, dilation 1, groups 1, zeros outside the map, padding k // 2, within the channel counts that are built."""
+        from . import _lib
+        if not isinstance(conv, torch.nn.Conv2d) or type(conv).forward is not torch.nn.Conv2d.forward:
+            return False
+        k = conv.kernel_size[0]
+        return (tuple(conv.kernel_size) in ((1, 1), (3, 3)) and tuple(conv.weight.shape) == (conv.out_channels, cin, k, k)
+                and conv.padding == (k // 2, k // 2) and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
+                and conv.padding_mode == "zeros" and cin % 16 == 0 and 0 < cin <= _lib.CONV_MAX_CIN
+                and 0 < conv.out_channels <= _lib.CONV_MAX_COUT)
+
+    def _conv(self, conv, dtype, x0, x1=None, relu=False, scale=1.0, keep=None):
+        """[relu](conv(cat([x0, x1]))) [* scale]: one launch of Engine.raft_conv in `dtype` where the kernel takes the module,
+        torch otherwise.  keep: the name of the kept buffer the launch writes; None makes a new tensor."""
+        cin = x0.shape[1] + (0 if x1 is None else x1.shape[1])
+        if dtype in (torch.float32, torch.bfloat16) and self._conv_plain(conv, cin):
+            eng = _engine(x0.device)
+            x0, x1 = _as(x0, dtype), None if x1 is None else _as(x1, dtype)
+            out = None
+            if keep is not None:
+                out = self._buffer(keep, (x0.shape[0], conv.out_channels) + tuple(x0.shape[2:]), dtype, x0.device, self._bufs)
+            return eng.raft_conv(x0, self._packed_conv(eng, conv, dtype, x0.device), conv.out_channels, conv.kernel_size[0], x1=x1,
+                                 relu=relu, scale=scale, out=out)
+        y = conv(x0 if x1 is None else torch.cat([x0, x1.to(x0.dtype)], dim=1))
+        y = F.relu(y) if relu else y
+        return y if scale == 1.0 else scale * y
+
+    @staticmethod
+    def _head_convs(head):
+        """(first, second) convolution of a head that is second(relu(first(x))): the reference's FlowHead (conv1, conv2, relu) or
+        an nn.Sequential(Conv2d, ReLU, Conv2d); None for anything else."""
+        nn = torch.nn
+        if isinstance(head, nn.Sequential):
+            if len(head) == 3 and isinstance(head[0], nn.Conv2d) and isinstance(head[1], nn.ReLU) and isinstance(head[2], nn.Conv2d):
+                return head[0], head[2]
+            return None
+        kids = dict(head.named_children()) if isinstance(head, nn.Module) else {}
+        if (set(kids) == {"conv1", "conv2", "relu"} and isinstance(kids["conv1"], nn.Conv2d) and isinstance(kids["conv2"], nn.Conv2d)
+                and isinstance(kids["relu"], nn.ReLU)):
+            return kids["conv1"], kids["conv2"]
+        return None
+
+    def _head(self, head, x, dtype, name, scale=1.0):
+        """head(x) [* scale] of the flow head or the mask head: two launches where the head is one _head_convs knows."""
+        pair = self._head_convs(head) if self.convs else None
+        if pair is None:
+            y = head(x)
+            return y if scale == 1.0 else scale * y
+        return self._conv(pair[1], dtype, self._conv(pair[0], dtype, x, relu=True, keep=name), scale=scale)
+
+    def _motion(self, flow, corr, dtype=None):
+        """BasicMotionEncoder.forward (update.py:79-87) up to its last cat: -> (out [B,126,H,W], flow).  dtype: the working dtype of
+        convs=True, the hidden state's."""
         enc = self.block.encoder
         if isinstance(corr, DeferredCorr) and self.motion_front:
             cor, flo = self._front(enc, corr, flow)
         else:
             if isinstance(corr, DeferredCorr):
-                corr = corr.materialize()
+                corr = corr.materialize()  # float32; convc1 of a bfloat16 block takes bfloat16 (autocast converts by itself)
+                want = getattr(getattr(enc.convc1, "weight", None), "dtype", corr.dtype)
+                if corr.dtype != want and want == torch.bfloat16 and not torch.is_autocast_enabled():
+                    corr = corr.to(want)
             cor, flo = F.relu(enc.convc1(corr)), None
+        return self._motion_tail(enc, cor, flo, dtype, flow), flow
+
+    def _motion_tail(self, enc, cor, flo, dtype, flow=None):
+        """update.py:81-86 on relu(convc1(.)) and relu(convf1(.)): with convs=True three launches and no cat.  flo None: convf1 runs
+        here on `flow`, behind convc2 as the reference orders them."""
+        if self.convs:
+            cor = self._conv(enc.convc2, dtype, cor, relu=True, keep="cor2")
+            if flo is None:
+                flo = F.relu(enc.convf1(flow))
+            flo = self._conv(enc.convf2, dtype, flo, relu=True, keep="flo2")
+            return self._conv(enc.conv, dtype, cor, flo, relu=True, keep="motion")
         cor = F.relu(enc.convc2(cor))
         if flo is None:
             flo = F.relu(enc.convf1(flow))
         flo = F.relu(enc.convf2(flo))
-        return F.relu(enc.conv(torch.cat([cor, flo], dim=1))), flow
+        return F.relu(enc.conv(torch.cat([cor, flo], dim=1)))
 
     @staticmethod
     def _front(enc, corr, flow):
@@ -209,7 +308,7 @@ class FusedUpdate(torch.nn.Module, GruGlue):
                                                       f32(c1.bias), f32(f1.weight), f32(f1.bias), corr.radius, out_dtype=flow.dtype)
 
     @torch.no_grad()
-    def forward(self, net, inp, corr=None, flow=None, iter08=True, iter16=True, iter32=True, update=True):
+    def forward(self, net, inp, corr=None, flow=None, iter08=True, iter16=True, iter32=True, update=True, mask=True):
         blk = self.block
         n = blk.n_gru_layers
         if iter32:                         # reads the old net[1]
@@ -218,11 +317,17 @@ class FusedUpdate(torch.nn.Module, GruGlue):
             x = [(net[0], "pool2x")] + ([(net[2], "interp")] if n > 2 else [])
             net[1] = self.fused_gru(blk.gru16, net[1], *(inp[1]), *x, level=16, conv=self.gru_conv)
         if iter08:                         # reads the new net[1]
-            out, fl = self._motion(flow, corr)
+            out, fl = self._motion(flow, corr, net[0].dtype)
             x = [out, fl] + ([(net[1], "interp")] if n > 1 else [])
             net[0] = self.fused_gru(blk.gru08, net[0], *(inp[0]), *x, level=8, conv=self.gru_conv)
         if not update:
             return net
+        if self.convs:
+            dtype = net[0].dtype
+            delta_flow = self._head(blk.flow_head, net[0], dtype, "flow_head")
+            return net, (self._head(blk.mask, net[0], dtype, "mask", scale=.25) if mask else None), delta_flow
         delta_flow = blk.flow_head(net[0])
+        if not mask:                       # test_mode uses the last iteration's only (raft_stereo.py:146-153)
+            return net, None, delta_flow
         mask = .25 * blk.mask(net[0])      # scale mask to balance gradients (update.py:140-141)
         return net, mask, delta_flow
