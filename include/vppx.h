@@ -32,6 +32,7 @@
  *   BasicMotionEncoder convc2 / convf2 / conv raft_stereo/update.py:81,83,86 vppx_raft_conv_dt_dev
  *   FlowHead conv1 / conv2              raft_stereo/update.py:34-42 vppx_raft_conv_dt_dev
  *   BasicMultiUpdateBlock.mask, .25 *   raft_stereo/update.py:113-116,141 vppx_raft_conv_dt_dev
+ *   ResidualBlock conv1 / conv2 / downsample, encoder conv2, output heads -> extractor.py:10-11,45,149,231,240,247 vppx_raft_conv_strided_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -993,7 +994,28 @@ int vppx_norm_stats_pieces(int64_t planes, int64_t cells_per_plane);
  * or Cout <= 0, C1 < 0; a frame stride below its tensor's size; a scale that is not finite; a dtype other than the two; a packed
  * pointer that is not 16-byte aligned (VPPX_E_INVALID_ARG); a ksize other than 1 and 3, C0 or C1 not a multiple of 16, C0 + C1
  * above VPPX_CONV_MAX_CIN, Cout above VPPX_CONV_MAX_COUT, B*H*W above 2^31 - 1 or more tiles than one launch takes
- * (VPPX_E_UNSUPPORTED). */
+ * (VPPX_E_UNSUPPORTED).
+ *
+ * The encoders' convolutions (models/raft_stereo/extractor.py:10-11 ResidualBlock conv1 / conv2, :45 downsample, :149 and :231
+ * the basic encoder's conv2, :240,247 the output heads): vppx_raft_conv_strided_dt_dev is vppx_raft_conv_dt_dev with `stride`
+ * behind ksize, nn.Conv2d(Cin, Cout, ksize, stride=stride, padding=ksize / 2) for stride 1 or 2.  H, W are the INPUT's: x0 is
+ * [B,C0,H,W], x1 [B,C1,H,W], and their frame strides are checked against C0 * H * W and C1 * H * W.  The output is
+ *     out [B,Cout,Ho,Wo],   Ho = (H - 1) / stride + 1,   Wo = (W - 1) / stride + 1      (integer division)
+ * which is torch's size for ksize 3 with padding 1 and for ksize 1 with padding 0; out's frame stride is checked against
+ * Cout * Ho * Wo.  The tile count and its refusal, the 16-byte and the cell-by-cell route (now decided by Wo) are in output pixels.
+ *     ksize 3:  acc[b][m][y][x] = sum over c < Cin, dy < 3, dx < 3 of w[m][c][dy][dx] * in[b][c][stride*y + dy - 1][stride*x + dx - 1]
+ *     ksize 1:  acc[b][m][y][x] = sum over c < Cin of w[m][c] * in[b][c][stride*y][stride*x]
+ * with +0 outside the map: at stride 2 output pixel (y, x) sums input rows 2y-1 .. 2y+1 and columns 2x-1 .. 2x+1.  For an odd H
+ * (W) the last window reaches one row (column) past the map, for an even one it does not.  The 1x1 at stride 2 reads the
+ * cells (2y, 2x) only: nothing at an odd row or column is read.  Bias, ReLU, scale and the rounding are those of
+ * vppx_raft_conv_dt_dev, and stride == 1 gives its bits.  The packed weights are exactly those of stride 1: a buffer packed by
+ * vppx_raft_conv_pack_dev for (Cout, Cin, ksize, dtype) serves either stride.
+ * NaN rule: a NaN (or infinite) input cell reaches exactly the output pixels whose window holds it, in every output channel of
+ * its frame, and no other cell.  For ksize 3 at stride 2 a cell (r, c) lies in the windows of rows (r-1)/2 .. (r+1)/2 rounded
+ * inwards: one output row for an even r, two for an odd r (one where the second would be row Ho), and columns likewise.  For
+ * ksize 1 at stride 2 a NaN at an odd row or column reaches nothing.
+ * Refused before anything is launched, with no output byte touched: a stride other than 1 and 2 (VPPX_E_UNSUPPORTED), and
+ * everything vppx_raft_conv_dt_dev refuses, with the same code. */
 #define VPPX_CONV_MAX_CIN 512
 #define VPPX_CONV_MAX_COUT 256
 size_t vppx_raft_conv3x3_packed_bytes(int Cout, int Cin, int dtype);
@@ -1014,6 +1036,9 @@ int vppx_raft_conv_pack_dev(const float *weight, const float *bias, int Cout, in
 int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
                           const void *packed, int Cout, int ksize, int B, int H, int W, int relu, float scale, void *out,
                           int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
+int vppx_raft_conv_strided_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                  const void *packed, int Cout, int ksize, int stride, int B, int H, int W, int relu, float scale,
+                                  void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

@@ -1,4 +1,4 @@
-// conv_kernels.hip -- gfx950 implicit-GEMM kernel for nn.Conv2d(Cin, Cout, 3, padding=1), stride 1, on the matrix cores, with
+// conv_kernels.hip -- gfx950 implicit-GEMM kernel for nn.Conv2d(Cin, Cout, 3, padding=1), stride 1 (2: below), on the matrix cores, with
 // the gates of ConvGRU.forward (models/raft_stereo/update.py:23-32) as epilogues: include/vppx.h has the arithmetic.
 //   M = pixels, N = output channels, K = 9 * Cin.  bfloat16 storage: v_mfma_f32_16x16x32_bf16; float32 storage:
 //   v_mfma_f32_16x16x4_f32 (exact float32 products, 1/16 of the bfloat16 rate).  Accumulation is float32 either way.
@@ -22,6 +22,19 @@
 //
 // The plain epilogue also serves the update block's other convolutions (vppx_raft_conv_*): any Cout >= 1 (the packing pads the
 // output channels to 16 with +0 rows and +0 bias slots, the store skips channel m >= Cout), a 1x1 kernel (TAPS = 1) and a scale.
+//
+// Stride 2 (STRIDE = 2, plain epilogue only; the encoders' layerN[0].conv1 and downsample[0]).  Tiles, the epilogue and the tile
+// count are in OUTPUT pixels, Ho = (H - 1) / 2 + 1 and Wo likewise; the packed weights are those of stride 1.
+//   1x1: output pixel (y, x) is input cell (2y, 2x).  The staged image is the TAPS = 1 image of stride 1, fetched at doubled
+//     source offsets: no cell of an odd row or column is read.
+//   3x3: output pixel (y, x) sums input rows 2y-1 .. 2y+1 and columns 2x-1 .. 2x+1.  A tile is CV_TH2 x CV_TW = 4 x 32 output
+//     pixels, one row and two M tiles per wave: its footprint of 9 x 65 input pixels is 46.8 KB of LDS, so that two workgroups
+//     still share a CU (8 x 32 would need 17 x 65 pixels = 88 KB, more than a static array holds).  A staged row is split by
+//     COLUMN PARITY: first the 33 odd columns 2 (x0 + q) - 1, q = 0 .. 32, then the 32 even columns 2 (x0 + q).  Tap dx = 0 of
+//     output pixel x0 + xl is then slot xl, dx = 1 slot 33 + xl and dx = 2 slot xl + 1: the pixels of an M tile lie CV_ROWB
+//     bytes apart as at stride 1, with the bank pattern of stride 1 (at 160 bytes, pixels 8 apart start on the same bank, and
+//     an M tile's rows are pixels 0-3, 8-11, 16-19, 24-27: the lanes of a read group would collide at least two ways), and the
+//     A fragment stays one 16-byte read per lane and tap.
 #include "cells.h"
 #include "gru_math.h"
 
@@ -29,6 +42,10 @@
 #define CV_TW 32
 #define CV_HW (CV_TW + 2)
 #define CV_HALO ((CV_TH + 2) * CV_HW)
+#define CV_TH2 4                 // rows of a tile of the 3x3 at stride 2
+#define CV_ODD2 (CV_TW + 1)      // odd columns of a staged row there, in front of the CV_TW even ones
+#define CV_HW2 (2 * CV_TW + 1)
+#define CV_HALO2 ((2 * CV_TH2 + 1) * CV_HW2)
 #define CV_ROWB 80
 #define CV_NB 64
 
@@ -47,10 +64,11 @@ struct ConvArgs {
     void *o0, *o1;           // plain: out;  zr: z, rh;  q: out
     long long so0, so1;
     int C0, Cin, NT, nchunks; // NT = ceil(Cout / 16): the packing pads the output channels with rows of +0
-    int H, W, tilesX, tilesY;
+    int H, W, tilesX, tilesY; // H, W: the OUTPUT's size (the input's too at stride 1)
     int C, relu, vec;        // C: the hidden size of the gates;  vec: 16-byte groups in the epilogue
     int Cout;                // plain: channel m is stored where m < Cout (the gates' Cout is NT * 16)
     float scale;             // plain: out = relu(v) * scale
+    int Hi, Wi;              // STRIDE == 2: the input's size
 };
 
 // Eight cells of a [B,C,H,W] tensor from cell `at` on, the first `nv` of them inside the row.  vec: every base, stride, plane
@@ -93,12 +111,19 @@ __device__ __forceinline__ void cv_store8(void *p, size_t at, int nv, bool vec, 
 
 // TAPS = 9: the 3x3 convolution.  TAPS = 1: a 1x1 convolution as the centre tap of the same staged image; its halo slots are
 // written as +0 without a read, so that nothing but the tile's own pixels is fetched.
-template <bool BF16, int EPI, int TAPS>
+// STRIDE = 2: see the head of the file.  S2 marks the 3x3 at stride 2, the one instance with a tile and a staged image of its own.
+template <bool BF16, int EPI, int TAPS, int STRIDE = 1>
 __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 {
     static_assert(TAPS == 9 || TAPS == 1, "3x3 or 1x1");
+    static_assert(STRIDE == 1 || (STRIDE == 2 && EPI == CV_PLAIN), "stride 2 goes with the plain epilogue");
     constexpr int CK = BF16 ? 32 : 16;
-    __shared__ __attribute__((aligned(16))) unsigned char sA[CV_HALO * CV_ROWB];
+    constexpr bool S2 = STRIDE == 2 && TAPS == 9;
+    constexpr int TH = S2 ? CV_TH2 : CV_TH, RPW = TH / 4, MT = 2 * RPW; // rows and M tiles of a wave
+    constexpr int HW = S2 ? CV_HW2 : CV_HW, NPIX = S2 ? CV_HALO2 : CV_HALO;
+    constexpr int NFULL = NPIX / 256, REM = NPIX - 256 * NFULL;        // pixels a thread stages whole, and those shared out
+    static_assert(3 * REM <= 256 && REM > 0, "the pixels beyond the whole rounds are spread three units apart");
+    __shared__ __attribute__((aligned(16))) unsigned char sA[NPIX * CV_ROWB];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, i = lane & 15;
     unsigned t = blockIdx.x;
@@ -106,56 +131,70 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     t /= (unsigned)a.tilesX;
     const int ty = (int)(t % (unsigned)a.tilesY);
     const size_t b = t / (unsigned)a.tilesY;
-    const int x0 = tx * CV_TW, y0 = ty * CV_TH, H = a.H, W = a.W;
-    const size_t plane = (size_t)H * W;
+    const int x0 = tx * CV_TW, y0 = ty * TH, H = a.H, W = a.W;
+    const int Hi = STRIDE == 1 ? H : a.Hi, Wi = STRIDE == 1 ? W : a.Wi;
+    const size_t plane = (size_t)H * W, planeIn = STRIDE == 1 ? plane : (size_t)Hi * Wi;
     const int nb = blockIdx.y, ntl = min(4, a.NT - 4 * nb);
 
     // The staging.  A pixel's row of a chunk is 16 units of 4 bytes: one float32 channel, or two bfloat16 channels (an even
     // channel and the next lie in the same source, both below Cin or both not, because C0 and Cin are multiples of 16).
     // Thread tid stages all 16 units of pixel tid of the 340, and unit tid / 84 + 3 j of pixel 256 + tid % 84 (tid < 252), so
     // that the 84 pixels beyond the first 256 are spread over the workgroup: 22 units per thread, read into registers one
-    // chunk ahead, while the matrix cores work on the chunk before.
-    const int pB = CV_TH * CV_TW + tid % (CV_HALO - CV_TH * CV_TW), uB = tid / (CV_HALO - CV_TH * CV_TW);
-    int offA, offB; // y * W + x of the two pixels, -1 outside the map
-    {
-        const int ryA = tid / CV_HW, rxA = tid - ryA * CV_HW, gyA = y0 + ryA - 1, gxA = x0 + rxA - 1;
-        const bool inA = TAPS == 9 || (ryA >= 1 && ryA <= CV_TH && rxA >= 1 && rxA <= CV_TW);
-        offA = inA && gyA >= 0 && gyA < H && gxA >= 0 && gxA < W ? gyA * W + gxA : -1;
-        const int ryB = pB / CV_HW, rxB = pB - ryB * CV_HW, gyB = y0 + ryB - 1, gxB = x0 + rxB - 1;
-        const bool inB = TAPS == 9 || (ryB >= 1 && ryB <= CV_TH && rxB >= 1 && rxB <= CV_TW);
-        offB = inB && uB < 3 && gyB >= 0 && gyB < H && gxB >= 0 && gxB < W ? gyB * W + gxB : -1;
-    }
+    // chunk ahead, while the matrix cores work on the chunk before.  (The 3x3 at stride 2: pixels tid and 256 + tid of the 585
+    // whole, and the last 73 spread likewise: 38 units.)
+    const int pB = 256 * NFULL + tid % REM, uB = tid / REM;
+    // y * Wi + x of the input cell behind staged pixel p, -1 outside the map and for a slot that is written as +0 unread
+    auto source = [&](int p) -> int {
+        int gy, gx;
+        bool in = true;
+        if (S2) {
+            const int r = p / HW, q = p - r * HW;
+            gy = 2 * y0 - 1 + r, gx = q < CV_ODD2 ? 2 * (x0 + q) - 1 : 2 * (x0 + q - CV_ODD2);
+        } else {
+            const int ry = p / HW, rx = p - ry * HW;
+            in = TAPS == 9 || (ry >= 1 && ry <= CV_TH && rx >= 1 && rx <= CV_TW);
+            gy = STRIDE * (y0 + ry - 1), gx = STRIDE * (x0 + rx - 1);
+        }
+        return in && gy >= 0 && gy < Hi && gx >= 0 && gx < Wi ? gy * Wi + gx : -1;
+    };
+    int offA[NFULL], offB;
+#pragma unroll
+    for (int f = 0; f < NFULL; f++) offA[f] = source(tid + 256 * f);
+    offB = uB < 3 ? source(pB) : -1;
     auto unit = [&](int chunk, int u, int off) -> u32 {
         const int c = chunk * CK + (BF16 ? 2 * u : u);
         if (off < 0 || c >= a.Cin) return 0u; // +0 outside the map and for the channels that pad K
         const bool first = c < a.C0;
-        const size_t at = (first ? b * (size_t)a.s0 + (size_t)c * plane : b * (size_t)a.s1 + (size_t)(c - a.C0) * plane) + (size_t)off;
+        const size_t at = (first ? b * (size_t)a.s0 + (size_t)c * planeIn : b * (size_t)a.s1 + (size_t)(c - a.C0) * planeIn) + (size_t)off;
         const void *src = first ? a.x0 : a.x1;
         if (BF16) {
             const u16 *p = (const u16 *)src + at;
-            return (u32)p[0] | ((u32)p[plane] << 16);
+            return (u32)p[0] | ((u32)p[planeIn] << 16);
         }
         return ((const u32 *)src)[at];
     };
-    u32 stA[16], stB[6];
+    u32 stA[NFULL][16], stB[6];
     auto fetch = [&](int chunk) {
 #pragma unroll
-        for (int u = 0; u < 16; u++) stA[u] = unit(chunk, u, offA);
+        for (int f = 0; f < NFULL; f++)
+#pragma unroll
+            for (int u = 0; u < 16; u++) stA[f][u] = unit(chunk, u, offA[f]);
 #pragma unroll
         for (int j = 0; j < 6; j++) stB[j] = uB + 3 * j < 16 ? unit(chunk, uB + 3 * j, offB) : 0u;
     };
     fetch(0);
 
-    cv_f32x4 acc[4][4];
+    cv_f32x4 acc[MT][4];
 #pragma unroll
-    for (int m = 0; m < 4; m++)
+    for (int m = 0; m < MT; m++)
 #pragma unroll
         for (int n = 0; n < 4; n++) acc[m][n] = (cv_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 
-    // byte offset of this lane's A fragment of M tile m = 2 * p + t at tap (0, 0)
-    int la[4];
+    // byte offset of this lane's A fragment of M tile m = 2 * p + t at tap (0, 0); S2: output row `wave` is staged row 2 * wave
+    int la[MT];
 #pragma unroll
-    for (int m = 0; m < 4; m++) la[m] = ((2 * wave + (m >> 1)) * CV_HW + 8 * (i >> 2) + 4 * (m & 1) + (i & 3)) * CV_ROWB + 16 * g;
+    for (int m = 0; m < MT; m++)
+        la[m] = ((S2 ? 2 * wave : 2 * wave + (m >> 1)) * HW + 8 * (i >> 2) + 4 * (m & 1) + (i & 3)) * CV_ROWB + 16 * g;
 
     const uint4 *pk = a.packed + (size_t)(4 * nb) * 64 + lane;
     const size_t step = (size_t)a.NT * 64; // fragments of one (chunk, tap)
@@ -167,7 +206,10 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     for (int chunk = 0; chunk < a.nchunks; chunk++) {
         __syncthreads(); // the last chunk's fragments have been read
 #pragma unroll
-        for (int k = 0; k < 4; k++) *(uint4 *)(sA + tid * CV_ROWB + 16 * k) = make_uint4(stA[4 * k], stA[4 * k + 1], stA[4 * k + 2], stA[4 * k + 3]);
+        for (int f = 0; f < NFULL; f++)
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                *(uint4 *)(sA + (tid + 256 * f) * CV_ROWB + 16 * k) = make_uint4(stA[f][4 * k], stA[f][4 * k + 1], stA[f][4 * k + 2], stA[f][4 * k + 3]);
         if (uB < 3) {
 #pragma unroll
             for (int j = 0; j < 6; j++)
@@ -183,16 +225,17 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
                 for (int n = 0; n < 4; n++)
                     if (n < ntl) bnext[n] = pk[(size_t)(s + 1) * step + 64 * n];
             }
-            const int toff = (TAPS == 9 ? (tap / 3) * CV_HW + tap % 3 : CV_HW + 1) * CV_ROWB;
-            uint4 fa[4];
+            // S2: columns 2x - 1 and 2x + 1 are slots x and x + 1 of the odd part, column 2x slot x of the even part behind it
+            const int toff = (S2 ? (tap / 3) * HW + (tap % 3 == 1 ? CV_ODD2 : tap % 3 / 2) : TAPS == 9 ? (tap / 3) * CV_HW + tap % 3 : CV_HW + 1) * CV_ROWB;
+            uint4 fa[MT];
 #pragma unroll
-            for (int m = 0; m < 4; m++) fa[m] = *(const uint4 *)(sA + la[m] + toff);
+            for (int m = 0; m < MT; m++) fa[m] = *(const uint4 *)(sA + la[m] + toff);
             if (BF16) {
 #pragma unroll
                 for (int n = 0; n < 4; n++) {
                     if (n >= ntl) break;
 #pragma unroll
-                    for (int m = 0; m < 4; m++)
+                    for (int m = 0; m < MT; m++)
                         acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cv_bf16x8, fa[m]),
                                                                             __builtin_bit_cast(cv_bf16x8, bcur[n]), acc[m][n], 0, 0, 0);
                 }
@@ -204,7 +247,7 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
                     for (int n = 0; n < 4; n++) {
                         if (n >= ntl) break;
 #pragma unroll
-                        for (int m = 0; m < 4; m++)
+                        for (int m = 0; m < MT; m++)
                             acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(cv_f32x4, fa[m])[k],
                                                                              __builtin_bit_cast(cv_f32x4, bcur[n])[k], acc[m][n], 0, 0, 0);
                     }
@@ -220,8 +263,8 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     const int x = x0 + 8 * g, nv = min(8, W - x);
     if (nv <= 0) return;
 #pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const int y = y0 + 2 * wave + p;
+    for (int p = 0; p < RPW; p++) {
+        const int y = y0 + RPW * wave + p;
         if (y >= H) break;
         const size_t pix = (size_t)y * W + x;
 #pragma unroll
@@ -336,7 +379,8 @@ int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, i
 }
 
 // ksize 1 and a Cout that is no multiple of 16 go with the plain epilogue only (vppx_api.hip sees to it)
-int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
+// stride 2 goes with the plain epilogue only as well; H, W are the input's, the output is (H - 1) / stride + 1 by (W - 1) / stride + 1
+int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, int stride, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
              const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
              int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, float scale, int dtype)
 {
@@ -349,29 +393,34 @@ int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, const void *x0,
     a.bias = (const float *)((const unsigned char *)packed + conv_weight_bytes(Cout, a.Cin, ksize, dtype));
     a.e0 = e0, a.e1 = e1, a.e2 = e2, a.se0 = (long long)se0, a.se1 = (long long)se1, a.se2 = (long long)se2;
     a.o0 = o0, a.o1 = o1, a.so0 = (long long)so0, a.so1 = (long long)so1;
-    a.H = H, a.W = W, a.tilesX = (W + CV_TW - 1) / CV_TW, a.tilesY = (H + CV_TH - 1) / CV_TH;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1, th = stride == 2 && ksize == 3 ? CV_TH2 : CV_TH;
+    a.H = Ho, a.W = Wo, a.Hi = H, a.Wi = W, a.tilesX = (Wo + CV_TW - 1) / CV_TW, a.tilesY = (Ho + th - 1) / th;
     a.C = C, a.relu = relu;
     const size_t tiles = (size_t)B * a.tilesX * a.tilesY;
     if (tiles > 0x7FFFFFFFull) {
-        vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, B, H, W, tiles);
+        vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, B, Ho, Wo, tiles);
         return VPPX_E_UNSUPPORTED;
     }
     const int64_t V = bf16 ? 8 : 4;
     const void *ptrs[5] = {e0, e1, e2, o0, o1};
     const int64_t strides[5] = {se0, se1, se2, so0, so1};
-    bool vec = W % V == 0; // then H * W is a whole number of groups as well
+    bool vec = Wo % V == 0; // then Ho * Wo is a whole number of groups as well
     for (int k = 0; k < 5; k++)
         if (ptrs[k]) vec = vec && aligned16(ptrs[k]) && strides[k] % V == 0;
     a.vec = vec;
     const dim3 grid((unsigned)tiles, (unsigned)((a.NT + 3) / 4));
-#define CONV_LAUNCH(BF, EP, TAPS) raft_conv3x3_kernel<BF, EP, TAPS><<<grid, 256, 0, ctx->stream>>>(a)
+#define CONV_LAUNCH(BF, EP, TAPS, ...) raft_conv3x3_kernel<BF, EP, TAPS, ##__VA_ARGS__><<<grid, 256, 0, ctx->stream>>>(a)
     if (bf16) {
-        if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(true, CV_PLAIN, 1);
+        if (epi == CV_PLAIN && stride == 2 && ksize == 1) CONV_LAUNCH(true, CV_PLAIN, 1, 2);
+        else if (epi == CV_PLAIN && stride == 2) CONV_LAUNCH(true, CV_PLAIN, 9, 2);
+        else if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(true, CV_PLAIN, 1);
         else if (epi == CV_PLAIN) CONV_LAUNCH(true, CV_PLAIN, 9);
         else if (epi == CV_ZR) CONV_LAUNCH(true, CV_ZR, 9);
         else CONV_LAUNCH(true, CV_Q, 9);
     } else {
-        if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(false, CV_PLAIN, 1);
+        if (epi == CV_PLAIN && stride == 2 && ksize == 1) CONV_LAUNCH(false, CV_PLAIN, 1, 2);
+        else if (epi == CV_PLAIN && stride == 2) CONV_LAUNCH(false, CV_PLAIN, 9, 2);
+        else if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(false, CV_PLAIN, 1);
         else if (epi == CV_PLAIN) CONV_LAUNCH(false, CV_PLAIN, 9);
         else if (epi == CV_ZR) CONV_LAUNCH(false, CV_ZR, 9);
         else CONV_LAUNCH(false, CV_Q, 9);

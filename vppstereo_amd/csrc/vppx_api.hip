@@ -2966,7 +2966,7 @@ extern "C" int vppx_raft_conv3x3_dt_dev(const void *x0, int64_t x0_frame_stride,
     if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, B, H, W, dtype)) ||
         (rc = gru_stride_ok(who, "out", out_frame_stride, Cout, H, W)))
         return rc;
-    return conv_run(ctx, who, 0, 3, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
+    return conv_run(ctx, who, 0, 3, 1, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
                     out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, 1.0f, dtype);
 }
 
@@ -3005,13 +3005,12 @@ extern "C" int vppx_raft_conv_pack_dev(const float *weight, const float *bias, i
     return conv_pack(ctx, weight, bias, Cout, Cin, ksize, dtype, packed);
 }
 
-extern "C" int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
-                                     const void *packed, int Cout, int ksize, int B, int H, int W, int relu, float scale, void *out,
-                                     int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
+// the plain call at stride 1 or 2: H, W are the input's, out is [B,Cout,(H - 1) / stride + 1,(W - 1) / stride + 1]
+static int conv_plain_call(const char *who, const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                           const void *packed, int Cout, int ksize, int stride, int B, int H, int W, int relu, float scale, void *out,
+                           int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
 {
-    static const char *who = "vppx_raft_conv";
     int rc;
-    VPPX_ENTER(ctx);
     if (!out) {
         vppx_set_error("%s: bad arguments", who);
         return VPPX_E_INVALID_ARG;
@@ -3020,11 +3019,35 @@ extern "C" int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, in
         vppx_set_error("%s: the scale is not finite", who);
         return VPPX_E_INVALID_ARG;
     }
+    if (stride != 1 && stride != 2) {
+        vppx_set_error("%s: a stride of %d: 1 and 2 are built", who, stride);
+        return VPPX_E_UNSUPPORTED;
+    }
     if ((rc = conv_call_ok(who, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, B, H, W, dtype, true)) ||
-        (rc = gru_stride_ok(who, "out", out_frame_stride, Cout, H, W)) || (rc = conv_ksize_ok(who, ksize)))
+        (rc = gru_stride_ok(who, "out", out_frame_stride, Cout, (H - 1) / stride + 1, (W - 1) / stride + 1)) ||
+        (rc = conv_ksize_ok(who, ksize)))
         return rc;
-    return conv_run(ctx, who, 0, ksize, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0, out,
-                    out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, scale, dtype);
+    return conv_run(ctx, who, 0, ksize, stride, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, NULL, 0, NULL, 0, NULL, 0,
+                    out, out_frame_stride, NULL, 0, B, 0, H, W, relu != 0, scale, dtype);
+}
+
+extern "C" int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                     const void *packed, int Cout, int ksize, int B, int H, int W, int relu, float scale, void *out,
+                                     int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
+{
+    VPPX_ENTER(ctx);
+    return conv_plain_call("vppx_raft_conv", x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, ksize, 1, B, H, W, relu, scale,
+                           out, out_frame_stride, dtype, ctx);
+}
+
+// nn.Conv2d(Cin, Cout, ksize, stride=stride, padding=ksize // 2): the encoders' layerN[0].conv1 and downsample[0] (extractor.py:10-11,45)
+extern "C" int vppx_raft_conv_strided_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride,
+                                             int C1, const void *packed, int Cout, int ksize, int stride, int B, int H, int W, int relu,
+                                             float scale, void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
+{
+    VPPX_ENTER(ctx);
+    return conv_plain_call("vppx_raft_conv_strided", x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, ksize, stride, B, H, W,
+                           relu, scale, out, out_frame_stride, dtype, ctx);
 }
 
 extern "C" int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
@@ -3049,7 +3072,7 @@ extern "C" int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, 
         (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "z", z_frame_stride, C, H, W)) ||
         (rc = gru_stride_ok(who, "rh", rh_frame_stride, C, H, W)))
         return rc;
-    return conv_run(ctx, who, 1, 3, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_zr, 2 * C, cz, cz_frame_stride, cr,
+    return conv_run(ctx, who, 1, 3, 1, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_zr, 2 * C, cz, cz_frame_stride, cr,
                     cr_frame_stride, h, h_frame_stride, z, z_frame_stride, rh, rh_frame_stride, B, C, H, W, 0, 1.0f, dtype);
 }
 
@@ -3069,7 +3092,7 @@ extern "C" int vppx_raft_gru_q_dt_dev(const void *x0, int64_t x0_frame_stride, i
     if ((rc = gru_stride_ok(who, "cq", cq_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "z", z_frame_stride, C, H, W)) ||
         (rc = gru_stride_ok(who, "h", h_frame_stride, C, H, W)) || (rc = gru_stride_ok(who, "out", out_frame_stride, C, H, W)))
         return rc;
-    return conv_run(ctx, who, 2, 3, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_q, C, cq, cq_frame_stride, z, z_frame_stride, h,
+    return conv_run(ctx, who, 2, 3, 1, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed_q, C, cq, cq_frame_stride, z, z_frame_stride, h,
                     h_frame_stride, out, out_frame_stride, NULL, 0, B, C, H, W, 0, 1.0f, dtype);
 }
 

@@ -580,7 +580,7 @@ int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *
 // the gates take ksize 3, Cout % 16 == 0 and ignore the scale.
 size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype);
 int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed);
-int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
+int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, int stride, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
              const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
              int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, float scale, int dtype);
 

@@ -998,18 +998,28 @@ class Engine:
         _lib.check(self.lib.vppx_raft_conv_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, ksize, dt, _ptr(packed), self.ctx.handle))
         return packed
 
-    def raft_conv(self, x0, packed, cout, ksize, x1=None, relu=False, scale=1.0, out=None):
-        """conv(cat([x0, x1], dim=1)) of an nn.Conv2d(C0 + C1, cout, ksize, padding=ksize // 2), ksize 1 or 3, whose weights `packed`
-        holds (raft_conv_pack, for the dtype of x0): + bias, with `relu` torch's ReLU, then * scale (one float32 multiplication;
-        1.0 changes no bit).  cout is any count from 1 on; x0, x1 and `out` may be channel slices of wider tensors, and no cell of
-        `out`'s buffer outside its cout channels is written.  -> [B,cout,H,W]; with `out` nothing is allocated."""
+    def raft_conv(self, x0, packed, cout, ksize, x1=None, relu=False, scale=1.0, out=None, stride=1):
+        """conv(cat([x0, x1], dim=1)) of an nn.Conv2d(C0 + C1, cout, ksize, stride=stride, padding=ksize // 2), ksize 1 or 3, stride 1
+        or 2, whose weights `packed` holds (raft_conv_pack, for the dtype of x0; the same buffer serves either stride): + bias, with
+        `relu` torch's ReLU, then * scale (one float32 multiplication; 1.0 changes no bit).  cout is any count from 1 on; x0, x1 and
+        `out` may be channel slices of wider tensors, and no cell of `out`'s buffer outside its cout channels is written.
+        -> [B,cout,Ho,Wo] with Ho = (H - 1) // stride + 1, Wo likewise; with `out` nothing is allocated."""
         dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed, cout, int(ksize))
+        stride = int(stride)
+        if stride not in (1, 2):
+            raise ValueError(f"stride is {stride}; 1 and 2 are built")
+        shape = (B, int(cout), (H - 1) // stride + 1, (W - 1) // stride + 1)
         if out is None:
-            out = self.torch.empty((B, int(cout), H, W), dtype=dtype, device=self.device)
-        so = self._chk_frames(out, dtype, "out", (B, int(cout), H, W))
+            out = self.torch.empty(shape, dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", shape)
         self._bind_stream()
-        _lib.check(self.lib.vppx_raft_conv_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), int(ksize), B, H, W,
-                                                  int(bool(relu)), float(scale), _ptr(out), so, dt, self.ctx.handle))
+        if stride == 1:
+            _lib.check(self.lib.vppx_raft_conv_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), int(ksize), B, H, W,
+                                                      int(bool(relu)), float(scale), _ptr(out), so, dt, self.ctx.handle))
+        else:
+            _lib.check(self.lib.vppx_raft_conv_strided_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), int(ksize),
+                                                              stride, B, H, W, int(bool(relu)), float(scale), _ptr(out), so, dt,
+                                                              self.ctx.handle))
         return out
 
     def raft_gru_zr(self, x0, packed_zr, cz, cr, h, x1=None, z=None, rh=None):

@@ -14,9 +14,21 @@ Norms taken: `InstanceNorm2d` without running statistics, affine or not, and `Ba
 (GroupNorm, the empty Sequential of norm_fn='none', a BatchNorm in training mode, dropout while training) is a TypeError
 when wrapping.  Inference only, as `FusedUpdate`: float32 or bfloat16; a tensor of another dtype than the first
 convolution's output is converted to it, and a dtype the kernels do not store (float16) is an error.
+
+`FusedEncoder(encoder, convs=True)` takes the convolutions too, as `FusedUpdate(block, convs=True)` does for the update block:
+every convolution of the trunk and the blocks (conv1, conv2 and downsample[0] of each ResidualBlock, extractor.py:10-11,45),
+the basic encoder's conv2 (:149), the second element of every outputs08 / outputs16 head and the outputs32 convolutions
+(:231,240,247) runs as one launch of `Engine.raft_conv` in the dtype of its input, at stride 1 or 2.  Each convolution is decided
+on its own: one that is not a plain nn.Conv2d (k 1 or 3, padding k // 2, stride (1, 1) or (2, 2), dilation 1, groups 1, zero
+padding, Cin a positive multiple of 16 up to CONV_MAX_CIN, Cout up to CONV_MAX_COUT) runs in torch -- the 7x7 stem on three
+channels always does --, as does one whose input is of a dtype the kernel does not store.  Under autocast the stem returns
+bfloat16 and everything behind it runs in bfloat16 with weights rounded once when they are packed; a float32 model runs the
+float32 matrix path.  The packed weights follow FusedUpdate's cache rule (`PackedWeights` of _convs.py, `forget_weights()`
+included).  It is opt-in: README.md has what was measured.
 """
 import torch
 
+from ._convs import PackedWeights, conv_plain
 from .corr import _engine
 from .update import _as
 
@@ -47,12 +59,14 @@ def _check_norm(m, where):
         raise TypeError(f"FusedEncoder: {where} is a {type(m).__name__}; InstanceNorm2d and BatchNorm2d in eval mode are taken")
 
 
-class FusedEncoder(torch.nn.Module):
+class FusedEncoder(torch.nn.Module, PackedWeights):
     """A module, so that it can take the encoder's place as `fnet` / `cnet` of a RAFTStereo; the encoder is its only child
     (`state_dict` keys gain the prefix `encoder.`: wrap after the weights are loaded)."""
 
-    def __init__(self, encoder):
-        super().__init__()
+    def __init__(self, encoder, convs=False):
+        torch.nn.Module.__init__(self)
+        PackedWeights.__init__(self)
+        self.convs = bool(convs)
         for name in ("conv1", "norm1"):
             if not hasattr(encoder, name):
                 raise TypeError(f"FusedEncoder: the encoder has no {name!r}")
@@ -117,7 +131,20 @@ class FusedEncoder(torch.nn.Module):
         stats, w, b = self._stats(eng, m, x)
         return eng.raft_norm_apply(x, stats, w, b, relu=True, out=x)
 
+    @staticmethod
+    def _conv_plain(conv, cin):
+        """Whether Engine.raft_conv takes this module on `cin` input channels: FusedUpdate's rule, with stride (2, 2) as well."""
+        return conv_plain(conv, cin, strides=((1, 1), (2, 2)))
+
     def _conv(self, conv, x, dtype):
+        """conv(x) in the working dtype (None: whatever the convolution returns).  convs=True: one launch of Engine.raft_conv in
+        the dtype of x where the kernel takes the module."""
+        if self.convs and x.dtype in (torch.float32, torch.bfloat16) and self._conv_plain(conv, x.shape[1]):
+            eng = _engine(x.device)
+            x = _as(x, x.dtype)
+            y = eng.raft_conv(x, self._packed_conv(eng, conv, x.dtype, x.device), conv.out_channels, conv.kernel_size[0],
+                              stride=conv.stride[0])
+            return _as(y, dtype or y.dtype)
         y = conv(x)
         if y.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"FusedEncoder: a convolution returned {y.dtype}; the kernels store float32 and bfloat16")
@@ -154,20 +181,21 @@ class FusedEncoder(torch.nn.Module):
         x = self._layer(eng, enc.layer2, x)
         x = self._layer(eng, enc.layer3, x)
         if not self.multi:
-            x = enc.conv2(x)
+            x = self._conv(enc.conv2, x, None) if self.convs else enc.conv2(x)
             if is_list:
                 x = x.split(split_size=batch_dim, dim=0)
             return x
         if dual_inp:
             v = x
             x = x[:(x.shape[0] // 2)]
-        outputs08 = [f[1](self._block(eng, f[0], x)) for f in enc.outputs08]
+        head = (lambda conv, t: self._conv(conv, t, None)) if self.convs else (lambda conv, t: conv(t))     # noqa: E731
+        outputs08 = [head(f[1], self._block(eng, f[0], x)) for f in enc.outputs08]
         if num_layers == 1:
             return (outputs08, v) if dual_inp else (outputs08,)
         y = self._layer(eng, enc.layer4, x)
-        outputs16 = [f[1](self._block(eng, f[0], y)) for f in enc.outputs16]
+        outputs16 = [head(f[1], self._block(eng, f[0], y)) for f in enc.outputs16]
         if num_layers == 2:
             return (outputs08, outputs16, v) if dual_inp else (outputs08, outputs16)
         z = self._layer(eng, enc.layer5, y)
-        outputs32 = [f(z) for f in enc.outputs32]
+        outputs32 = [head(f, z) for f in enc.outputs32]
         return (outputs08, outputs16, outputs32, v) if dual_inp else (outputs08, outputs16, outputs32)
