@@ -49,8 +49,6 @@
 #define CV_ROWB 80
 #define CV_NB 64
 
-enum { CV_PLAIN = 0, CV_ZR = 1, CV_Q = 2 };
-
 typedef float cv_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 cv_bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -348,7 +346,7 @@ __global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, 
 }
 
 // ---------------------------------------------------------------------------------------
-// launchers (every argument has been checked by vppx_api.hip)
+// launchers (every argument has been checked by vppx_net_api.hip)
 // ---------------------------------------------------------------------------------------
 static int conv_chunks(int Cin, int dtype) { return dtype == VPPX_DT_BF16 ? (Cin + 31) / 32 : (Cin + 15) / 16; }
 
@@ -378,54 +376,49 @@ int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, i
     return 0;
 }
 
-// ksize 1 and a Cout that is no multiple of 16 go with the plain epilogue only (vppx_api.hip sees to it)
-// stride 2 goes with the plain epilogue only as well; H, W are the input's, the output is (H - 1) / stride + 1 by (W - 1) / stride + 1
-int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, int stride, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
-             const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
-             int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, float scale, int dtype)
+// one launch per (epilogue, taps, stride) that is built: ksize 1, stride 2 and a Cout that is no multiple of 16 go with the plain
+// epilogue only (vppx_net_api.hip sees to it)
+template <bool BF16>
+static void conv_launch(vppx_ctx *ctx, const ConvCall &c, const ConvArgs &a, dim3 grid)
 {
-    const bool bf16 = dtype == VPPX_DT_BF16;
+    if (c.epi == CV_PLAIN && c.stride == 2 && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1, 2><<<grid, 256, 0, ctx->stream>>>(a);
+    else if (c.epi == CV_PLAIN && c.stride == 2) raft_conv3x3_kernel<BF16, CV_PLAIN, 9, 2><<<grid, 256, 0, ctx->stream>>>(a);
+    else if (c.epi == CV_PLAIN && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1><<<grid, 256, 0, ctx->stream>>>(a);
+    else if (c.epi == CV_PLAIN) raft_conv3x3_kernel<BF16, CV_PLAIN, 9><<<grid, 256, 0, ctx->stream>>>(a);
+    else if (c.epi == CV_ZR) raft_conv3x3_kernel<BF16, CV_ZR, 9><<<grid, 256, 0, ctx->stream>>>(a);
+    else raft_conv3x3_kernel<BF16, CV_Q, 9><<<grid, 256, 0, ctx->stream>>>(a);
+}
+
+int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c)
+{
+    const bool bf16 = c.dtype == VPPX_DT_BF16;
     ConvArgs a = {};
-    a.x0 = x0, a.x1 = C1 ? x1 : x0, a.s0 = (long long)s0, a.s1 = C1 ? (long long)s1 : 0;
-    a.C0 = C0, a.Cin = C0 + C1, a.NT = conv_ntiles(Cout), a.nchunks = conv_chunks(a.Cin, dtype);
-    a.Cout = Cout, a.scale = scale;
-    a.packed = (const uint4 *)packed;
-    a.bias = (const float *)((const unsigned char *)packed + conv_weight_bytes(Cout, a.Cin, ksize, dtype));
-    a.e0 = e0, a.e1 = e1, a.e2 = e2, a.se0 = (long long)se0, a.se1 = (long long)se1, a.se2 = (long long)se2;
-    a.o0 = o0, a.o1 = o1, a.so0 = (long long)so0, a.so1 = (long long)so1;
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1, th = stride == 2 && ksize == 3 ? CV_TH2 : CV_TH;
-    a.H = Ho, a.W = Wo, a.Hi = H, a.Wi = W, a.tilesX = (Wo + CV_TW - 1) / CV_TW, a.tilesY = (Ho + th - 1) / th;
-    a.C = C, a.relu = relu;
-    const size_t tiles = (size_t)B * a.tilesX * a.tilesY;
+    a.x0 = c.x0, a.x1 = c.C1 ? c.x1 : c.x0, a.s0 = (long long)c.s0, a.s1 = c.C1 ? (long long)c.s1 : 0;
+    a.C0 = c.C0, a.Cin = c.C0 + c.C1, a.NT = conv_ntiles(c.Cout), a.nchunks = conv_chunks(a.Cin, c.dtype);
+    a.Cout = c.Cout, a.scale = c.scale;
+    a.packed = (const uint4 *)c.packed;
+    a.bias = (const float *)((const unsigned char *)c.packed + conv_weight_bytes(c.Cout, a.Cin, c.ksize, c.dtype));
+    a.e0 = c.in[0].p, a.e1 = c.in[1].p, a.e2 = c.in[2].p;
+    a.se0 = (long long)c.in[0].stride, a.se1 = (long long)c.in[1].stride, a.se2 = (long long)c.in[2].stride;
+    a.o0 = (void *)c.out[0].p, a.o1 = (void *)c.out[1].p, a.so0 = (long long)c.out[0].stride, a.so1 = (long long)c.out[1].stride;
+    const int Ho = (c.H - 1) / c.stride + 1, Wo = (c.W - 1) / c.stride + 1, th = c.stride == 2 && c.ksize == 3 ? CV_TH2 : CV_TH;
+    a.H = Ho, a.W = Wo, a.Hi = c.H, a.Wi = c.W, a.tilesX = (Wo + CV_TW - 1) / CV_TW, a.tilesY = (Ho + th - 1) / th;
+    a.C = c.C, a.relu = c.relu;
+    const size_t tiles = (size_t)c.B * a.tilesX * a.tilesY;
     if (tiles > 0x7FFFFFFFull) {
-        vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, B, Ho, Wo, tiles);
+        vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, c.B, Ho, Wo, tiles);
         return VPPX_E_UNSUPPORTED;
     }
     const int64_t V = bf16 ? 8 : 4;
-    const void *ptrs[5] = {e0, e1, e2, o0, o1};
-    const int64_t strides[5] = {se0, se1, se2, so0, so1};
     bool vec = Wo % V == 0; // then Ho * Wo is a whole number of groups as well
-    for (int k = 0; k < 5; k++)
-        if (ptrs[k]) vec = vec && aligned16(ptrs[k]) && strides[k] % V == 0;
+    for (const ConvTensor &t : c.in)
+        if (t.p) vec = vec && aligned16(t.p) && t.stride % V == 0;
+    for (const ConvTensor &t : c.out)
+        if (t.p) vec = vec && aligned16(t.p) && t.stride % V == 0;
     a.vec = vec;
     const dim3 grid((unsigned)tiles, (unsigned)((a.NT + 3) / 4));
-#define CONV_LAUNCH(BF, EP, TAPS, ...) raft_conv3x3_kernel<BF, EP, TAPS, ##__VA_ARGS__><<<grid, 256, 0, ctx->stream>>>(a)
-    if (bf16) {
-        if (epi == CV_PLAIN && stride == 2 && ksize == 1) CONV_LAUNCH(true, CV_PLAIN, 1, 2);
-        else if (epi == CV_PLAIN && stride == 2) CONV_LAUNCH(true, CV_PLAIN, 9, 2);
-        else if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(true, CV_PLAIN, 1);
-        else if (epi == CV_PLAIN) CONV_LAUNCH(true, CV_PLAIN, 9);
-        else if (epi == CV_ZR) CONV_LAUNCH(true, CV_ZR, 9);
-        else CONV_LAUNCH(true, CV_Q, 9);
-    } else {
-        if (epi == CV_PLAIN && stride == 2 && ksize == 1) CONV_LAUNCH(false, CV_PLAIN, 1, 2);
-        else if (epi == CV_PLAIN && stride == 2) CONV_LAUNCH(false, CV_PLAIN, 9, 2);
-        else if (epi == CV_PLAIN && ksize == 1) CONV_LAUNCH(false, CV_PLAIN, 1);
-        else if (epi == CV_PLAIN) CONV_LAUNCH(false, CV_PLAIN, 9);
-        else if (epi == CV_ZR) CONV_LAUNCH(false, CV_ZR, 9);
-        else CONV_LAUNCH(false, CV_Q, 9);
-    }
-#undef CONV_LAUNCH
+    if (bf16) conv_launch<true>(ctx, c, a, grid);
+    else conv_launch<false>(ctx, c, a, grid);
     VPPX_CHECK_LAUNCH();
     return 0;
 }

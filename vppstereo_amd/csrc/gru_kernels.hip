@@ -206,7 +206,7 @@ __global__ void __launch_bounds__(256) gru_assemble_kernel(GruAsm a, int H, int 
 }
 
 // ---------------------------------------------------------------------------------------
-// launchers (every argument has been checked by vppx_api.hip)
+// launchers (every argument has been checked by vppx_net_api.hip)
 // ---------------------------------------------------------------------------------------
 static int gru_grid(const char *who, int B, long long n, int V, long long *G, size_t *total, unsigned *blocks)
 {

@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(256) raft_motion_front_kernel(MotionArgs a)
 }
 
 // ---------------------------------------------------------------------------------------
-// launcher (every argument has been checked by vppx_api.hip)
+// launcher (every argument has been checked by vppx_net_api.hip)
 // ---------------------------------------------------------------------------------------
 int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *coords_x, int64_t coords_frame_stride, const float *flow,
                  int64_t flow_frame_stride, const float *wc, const float *bias_c, int Cc, const float *wf, const float *bias_f, int Cf,

@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(256) norm_apply_kernel(NormApply a)
 }
 
 // ---------------------------------------------------------------------------------------
-// launchers (every argument has been checked by vppx_api.hip)
+// launchers (every argument has been checked by vppx_net_api.hip)
 // ---------------------------------------------------------------------------------------
 int norm_stats(vppx_ctx *ctx, const void *x, int64_t sx, int B, int C, int H, int W, double eps, float *stats, int dtype)
 {

@@ -45,6 +45,16 @@ struct DevGuard {
     }
 };
 
+#define VPPX_ENTER(ctx)                                                                                              \
+    if (!(ctx)) { vppx_set_error("context is NULL (vppx_create failed? there is no CPU fallback)"); return VPPX_E_NO_DEVICE; } \
+    DevGuard dev_guard_((ctx)->device);                                                                                  \
+    /* cross-call pipelining: any entry point but the two pipelined ones may queue work that touches the front stage's   \
+       buffers, so the next front stage must wait for the whole launch stream again (PIPE_KEEP restores the flag) */      \
+    const bool pipe_had_agg_done_ = (ctx)->have_agg_done;                                                                 \
+    (ctx)->have_agg_done = false;                                                                                         \
+    (void)pipe_had_agg_done_
+#define VPPX_PIPE_KEEP(ctx) (ctx)->have_agg_done = pipe_had_agg_done_
+
 // ---------------------------------------------------------------------------------------
 // workspace arena: named, grow-only device buffers owned by the context.  Everything the
 // pipeline needs between kernels lives in HBM for the lifetime of the context (288 GB:
@@ -575,14 +585,36 @@ int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *
                  int64_t out_f_frame_stride, int dtype, int out_dtype);
 
 // conv_kernels.hip: the 3x3 convolution on the matrix cores and ConvGRU's gates as its epilogues (update.py:19-32).
-// epi: 0 plain (o0 = out), 1 zr (e0, e1, e2 = cz, cr, h; o0, o1 = z, rh), 2 q (e0, e1, e2 = cq, z, h; o0 = out)
-// ksize 3 or 1.  The plain epilogue takes any Cout >= 1 (padded to 16 in the packing, masked in the store), ksize 1 and a scale;
-// the gates take ksize 3, Cout % 16 == 0 and ignore the scale.
+// The plain epilogue takes any Cout >= 1 (padded to 16 in the packing, masked in the store), ksize 1, stride 2 and a scale;
+// the gates take ksize 3, stride 1, Cout % 16 == 0 and ignore the scale.
+enum ConvEpi { CV_PLAIN = 0, CV_ZR = 1, CV_Q = 2 };
+
+// a tensor the epilogue reads or writes, under the name its entry point gives it in a refusal; name NULL: the call has none
+struct ConvTensor {
+    const char *name = NULL;
+    const void *p = NULL; // (an output's is written: its entry point took it as void *)
+    int64_t stride = 0;   // cells between frames
+};
+
+// One call of the convolution kernel; what is left out is the 3x3 call at stride 1.
+struct ConvCall {
+    ConvEpi epi = CV_PLAIN;
+    int ksize = 3, stride = 1, dtype = VPPX_DT_F32;
+    const void *x0 = NULL, *x1 = NULL; // the input is cat([x0, x1], dim=1); x1 is not read where C1 == 0
+    int64_t s0 = 0, s1 = 0;            // cells between frames
+    int C0 = 0, C1 = 0;
+    const void *packed = NULL;         // conv_pack's buffer for (Cout, C0 + C1, ksize, dtype)
+    int Cout = 0;                      // output channels of the packed weights (zr packs convz and convr: 2 C)
+    ConvTensor in[3];                  // zr: cz, cr, h;  q: cq, z, h
+    ConvTensor out[2];                 // plain: out;  zr: z, rh;  q: out
+    int B = 0, C = 0, H = 0, W = 0;    // C: the hidden size of the gates.  H, W: the input's; the output is (H - 1) / stride + 1 high
+    int relu = 0;                      // plain: out = relu(v) * scale
+    float scale = 1.0f;
+};
+
 size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype);
 int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed);
-int conv_run(vppx_ctx *ctx, const char *who, int epi, int ksize, int stride, const void *x0, int64_t s0, int C0, const void *x1, int64_t s1, int C1,
-             const void *packed, int Cout, const void *e0, int64_t se0, const void *e1, int64_t se1, const void *e2, int64_t se2, void *o0,
-             int64_t so0, void *o1, int64_t so1, int B, int C, int H, int W, int relu, float scale, int dtype);
+int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c); // every field has been checked by vppx_net_api.hip
 
 // norm_kernels.hip: the encoders' glue (models/raft_stereo/extractor.py:48-60, :181-183, :276-278)
 int norm_stats_pieces(int64_t planes, int64_t cells); // host arithmetic: workgroups per plane

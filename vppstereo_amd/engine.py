@@ -13,6 +13,15 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+# The convolution's rule for output channels: multiples of 16 (raft_conv3x3* and the gates) or any count from 1 on (raft_conv*).
+_OUT_16, _OUT_ANY = "out16", "any"
+
+
+def _conv_built(rule):
+    return (f"multiples of 16 up to {_lib.CONV_MAX_CIN} in and {'1 to ' if rule is _OUT_ANY else ''}{_lib.CONV_MAX_COUT} "
+            "out are built")
+
+
 class Engine:
     """One GPU's VPP+rSGM pipeline.  Inputs are CUDA tensors:
         left, right : uint8  [B,H,W,C]     hints : float32 [B,H,W]     g_occ : uint8 [B,H,W] or None
@@ -26,7 +35,7 @@ class Engine:
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.ctx = _lib.Context(self.device.index)
         self.lib = _lib.load()
-        self._conv_sizes = {}              # (Cout, Cin, VppxDtype) -> bytes of the packed weights
+        self._conv_sizes = {}              # (rule, Cout, Cin, ksize, VppxDtype) -> bytes of the packed weights
 
     def _bind_stream(self):
         """Run on torch's current stream, so that library kernels are ordered with the torch work around them.
@@ -906,39 +915,45 @@ class Engine:
         """The weights [Cout,Cin,3,3] (and bias [Cout]) of an nn.Conv2d(Cin, Cout, 3, padding=1) in the layout the convolution
         kernel reads, for activations stored as `dtype` (torch.float32, the default, or torch.bfloat16: the weights are then
         rounded to bfloat16 once).  -> an opaque torch.uint8 device tensor; pack once per module, it serves any B, H, W."""
+        return self._conv_pack(weight, bias, dtype, (3,), _OUT_16, self.lib.vppx_raft_conv3x3_pack_dev)
+
+    def _conv_pack(self, weight, bias, dtype, ksizes, rule, pack_dev):
+        """raft_conv3x3_pack and raft_conv_pack: the kernel sizes and the rule for the channels each takes, and its C entry."""
         torch = self.torch
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"dtype is {dtype}; the kernels store float32 and bfloat16")
         dt = _lib.DT_BF16 if dtype == torch.bfloat16 else _lib.DT_F32
-        if getattr(weight, "device", None) != self.device or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-            raise ValueError(f"weight: expected a [Cout,Cin,3,3] tensor on {self.device}")
-        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+        if (getattr(weight, "device", None) != self.device or weight.dim() != 4 or weight.shape[2] != weight.shape[3]
+                or weight.shape[2] not in ksizes):
+            want = "[Cout,Cin,3,3] tensor" if ksizes == (3,) else "[Cout,Cin,k,k] tensor with k 1 or 3"
+            raise ValueError(f"weight: expected a {want} on {self.device}")
+        Cout, Cin, ksize = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         weight = weight.detach().to(torch.float32).contiguous()
         if bias is not None:
             bias = bias.detach().to(torch.float32).contiguous()
             self._chk(bias, torch.float32, 1, "bias", (Cout,))
-        size = self._packed_bytes(Cout, Cin, dt)
+        size = self._packed_bytes(rule, Cout, Cin, ksize, dt)
         if size == 0:
-            raise ValueError(f"weight: {Cin} -> {Cout} channels: multiples of 16 up to {_lib.CONV_MAX_CIN} in and "
-                             f"{_lib.CONV_MAX_COUT} out are built")
+            raise ValueError(f"weight: {Cin} -> {Cout} channels: {_conv_built(rule)}")
         packed = torch.empty((size,), dtype=torch.uint8, device=self.device)
         self._bind_stream()
-        _lib.check(self.lib.vppx_raft_conv3x3_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, dt, _ptr(packed), self.ctx.handle))
+        shape = (Cout, Cin, ksize) if rule is _OUT_ANY else (Cout, Cin)
+        _lib.check(pack_dev(_ptr(weight), _ptr(bias), *shape, dt, _ptr(packed), self.ctx.handle))
         return packed
 
-    def _packed_bytes(self, cout, cin, dt, ksize=None):
-        """vppx_raft_conv3x3_packed_bytes (ksize None) or vppx_raft_conv_packed_bytes, asked once per (Cout, Cin, dtype, ksize):
-        host arithmetic on constants."""
-        key = (cout, cin, dt) if ksize is None else (cout, cin, dt, ksize)
+    def _packed_bytes(self, rule, cout, cin, ksize, dt):
+        """vppx_raft_conv3x3_packed_bytes (_OUT_16, ksize 3) or vppx_raft_conv_packed_bytes (_OUT_ANY), asked once per key: host
+        arithmetic on constants."""
+        key = (rule, cout, cin, ksize, dt)
         if key not in self._conv_sizes:
-            self._conv_sizes[key] = int(self.lib.vppx_raft_conv3x3_packed_bytes(cout, cin, dt) if ksize is None else
-                                        self.lib.vppx_raft_conv_packed_bytes(cout, cin, ksize, dt))
+            self._conv_sizes[key] = int(self.lib.vppx_raft_conv_packed_bytes(cout, cin, ksize, dt) if rule is _OUT_ANY else
+                                        self.lib.vppx_raft_conv3x3_packed_bytes(cout, cin, dt))
         return self._conv_sizes[key]
 
-    def _chk_conv(self, x0, x1, packed, cout, ksize=None):
-        """The sources and the packed weights of a convolution call -> (dtype, dt, B, H, W, s0, C0, s1, C1).  ksize None: the
-        3x3 calls that take multiples of 16 output channels; 1 or 3: raft_conv."""
+    def _chk_conv(self, rule, x0, x1, packed, cout, ksize=3):
+        """The sources and the packed weights of a convolution call -> (dtype, dt, B, H, W, s0, C0, s1, C1).  _OUT_16: the 3x3
+        calls that take multiples of 16 output channels; _OUT_ANY: raft_conv, ksize 1 or 3."""
         torch = self.torch
         dtype, dt = self._norm_dtype(x0, "x0")
         s0 = self._chk_frames(x0, dtype, "x0")
@@ -951,10 +966,9 @@ class Engine:
                 raise ValueError(f"x1: expected [{B},C1,{H},{W}], got {tuple(x1.shape)}")
         if getattr(packed, "device", None) != self.device or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
             raise ValueError(f"packed: expected what raft_conv3x3_pack returns, a torch.uint8 vector on {self.device}")
-        want = self._packed_bytes(int(cout), C0 + C1, dt, ksize)
+        want = self._packed_bytes(rule, int(cout), C0 + C1, ksize, dt)
         if want == 0 or packed.numel() != want:
-            built = (f"multiples of 16 up to {_lib.CONV_MAX_CIN} in and {_lib.CONV_MAX_COUT} out are built" if ksize is None else
-                     f"kernel sizes 1 and 3, multiples of 16 up to {_lib.CONV_MAX_CIN} in and 1 to {_lib.CONV_MAX_COUT} out are built")
+            built = ("kernel sizes 1 and 3, " if rule is _OUT_ANY else "") + _conv_built(rule)
             raise ValueError(f"packed: {packed.numel()} bytes; {C0 + C1} -> {cout} channels of {dtype} take {want or 'no'} bytes ({built})")
         return dtype, dt, B, H, W, s0, C0, s1, C1
 
@@ -963,40 +977,35 @@ class Engine:
         (raft_conv3x3_pack, for the dtype of x0), with its bias and, with `relu`, torch's ReLU.  x0 [B,C0,H,W] and x1
         [B,C1,H,W] or None are float32 or bfloat16 and may be channel slices of wider tensors.  -> [B,cout,H,W]; with `out`
         nothing is allocated (include/vppx.h has the arithmetic)."""
-        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed, cout)
+        return self._conv_plain(_OUT_16, x0, x1, packed, cout, 3, 1, relu, 1.0, out)
+
+    def _conv_plain(self, rule, x0, x1, packed, cout, ksize, stride, relu, scale, out):
+        """raft_conv3x3 (_OUT_16: vppx_raft_conv3x3_dt_dev) and raft_conv (_OUT_ANY: vppx_raft_conv_dt_dev at stride 1,
+        vppx_raft_conv_strided_dt_dev at stride 2)."""
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(rule, x0, x1, packed, cout, ksize)
+        cout, stride, relu = int(cout), int(stride), int(bool(relu))
+        if stride not in (1, 2):
+            raise ValueError(f"stride is {stride}; 1 and 2 are built")
+        shape = (B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1)
         if out is None:
-            out = self.torch.empty((B, int(cout), H, W), dtype=dtype, device=self.device)
-        so = self._chk_frames(out, dtype, "out", (B, int(cout), H, W))
+            out = self.torch.empty(shape, dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", shape)
         self._bind_stream()
-        _lib.check(self.lib.vppx_raft_conv3x3_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), B, H, W, int(bool(relu)),
-                                                     _ptr(out), so, dt, self.ctx.handle))
+        lib, ctx, p0, p1, pw, po = self.lib, self.ctx.handle, _ptr(x0), _ptr(x1), _ptr(packed), _ptr(out)
+        if rule is _OUT_16:
+            rc = lib.vppx_raft_conv3x3_dt_dev(p0, s0, C0, p1, s1, C1, pw, cout, B, H, W, relu, po, so, dt, ctx)
+        elif stride == 1:
+            rc = lib.vppx_raft_conv_dt_dev(p0, s0, C0, p1, s1, C1, pw, cout, ksize, B, H, W, relu, float(scale), po, so, dt, ctx)
+        else:
+            rc = lib.vppx_raft_conv_strided_dt_dev(p0, s0, C0, p1, s1, C1, pw, cout, ksize, stride, B, H, W, relu, float(scale), po, so, dt, ctx)
+        _lib.check(rc)
         return out
 
     def raft_conv_pack(self, weight, bias=None, dtype=None):
         """raft_conv3x3_pack for raft_conv: the weights [Cout,Cin,k,k], k 1 or 3, of an nn.Conv2d(Cin, Cout, k, padding=k // 2) with
         any Cout from 1 to CONV_MAX_COUT (Cin a multiple of 16).  -> an opaque torch.uint8 device tensor; for k = 3 and a Cout that is a
         multiple of 16, the bytes raft_conv3x3_pack makes."""
-        torch = self.torch
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"dtype is {dtype}; the kernels store float32 and bfloat16")
-        dt = _lib.DT_BF16 if dtype == torch.bfloat16 else _lib.DT_F32
-        if (getattr(weight, "device", None) != self.device or weight.dim() != 4 or weight.shape[2] != weight.shape[3]
-                or weight.shape[2] not in (1, 3)):
-            raise ValueError(f"weight: expected a [Cout,Cin,k,k] tensor with k 1 or 3 on {self.device}")
-        Cout, Cin, ksize = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
-        weight = weight.detach().to(torch.float32).contiguous()
-        if bias is not None:
-            bias = bias.detach().to(torch.float32).contiguous()
-            self._chk(bias, torch.float32, 1, "bias", (Cout,))
-        size = self._packed_bytes(Cout, Cin, dt, ksize)
-        if size == 0:
-            raise ValueError(f"weight: {Cin} -> {Cout} channels: multiples of 16 up to {_lib.CONV_MAX_CIN} in and 1 to "
-                             f"{_lib.CONV_MAX_COUT} out are built")
-        packed = torch.empty((size,), dtype=torch.uint8, device=self.device)
-        self._bind_stream()
-        _lib.check(self.lib.vppx_raft_conv_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, ksize, dt, _ptr(packed), self.ctx.handle))
-        return packed
+        return self._conv_pack(weight, bias, dtype, (1, 3), _OUT_ANY, self.lib.vppx_raft_conv_pack_dev)
 
     def raft_conv(self, x0, packed, cout, ksize, x1=None, relu=False, scale=1.0, out=None, stride=1):
         """conv(cat([x0, x1], dim=1)) of an nn.Conv2d(C0 + C1, cout, ksize, stride=stride, padding=ksize // 2), ksize 1 or 3, stride 1
@@ -1004,23 +1013,7 @@ class Engine:
         `relu` torch's ReLU, then * scale (one float32 multiplication; 1.0 changes no bit).  cout is any count from 1 on; x0, x1 and
         `out` may be channel slices of wider tensors, and no cell of `out`'s buffer outside its cout channels is written.
         -> [B,cout,Ho,Wo] with Ho = (H - 1) // stride + 1, Wo likewise; with `out` nothing is allocated."""
-        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed, cout, int(ksize))
-        stride = int(stride)
-        if stride not in (1, 2):
-            raise ValueError(f"stride is {stride}; 1 and 2 are built")
-        shape = (B, int(cout), (H - 1) // stride + 1, (W - 1) // stride + 1)
-        if out is None:
-            out = self.torch.empty(shape, dtype=dtype, device=self.device)
-        so = self._chk_frames(out, dtype, "out", shape)
-        self._bind_stream()
-        if stride == 1:
-            _lib.check(self.lib.vppx_raft_conv_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), int(ksize), B, H, W,
-                                                      int(bool(relu)), float(scale), _ptr(out), so, dt, self.ctx.handle))
-        else:
-            _lib.check(self.lib.vppx_raft_conv_strided_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), int(cout), int(ksize),
-                                                              stride, B, H, W, int(bool(relu)), float(scale), _ptr(out), so, dt,
-                                                              self.ctx.handle))
-        return out
+        return self._conv_plain(_OUT_ANY, x0, x1, packed, cout, int(ksize), stride, relu, scale, out)
 
     def raft_gru_zr(self, x0, packed_zr, cz, cr, h, x1=None, z=None, rh=None):
         """convz and convr of a ConvGRU (update.py:27-28) in one launch with their gates: `packed_zr` holds
@@ -1028,7 +1021,7 @@ class Engine:
         buffer raft_gru_assemble made.  -> (z, rh) = (sigmoid(convz(hx) + cz), sigmoid(convr(hx) + cr) * h), each [B,C,H,W].
         `rh` must be a buffer of its own, not the h part of hx."""
         Cc = h.shape[1]
-        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed_zr, 2 * Cc)
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(_OUT_16, x0, x1, packed_zr, 2 * Cc)
         shape = (B, Cc, H, W)
         sh = self._chk_frames(h, dtype, "h", shape)
         sz, sr = self._chk_frames(cz, dtype, "cz", shape), self._chk_frames(cr, dtype, "cr", shape)
@@ -1046,7 +1039,7 @@ class Engine:
         """convq of a ConvGRU with the rest of its forward (update.py:29-31): x0 = rh of raft_gru_zr and x1 = the x part of
         hx (hx[:, C:]) are cat([r*h, x]); -> (1 - z) * h + z * tanh(convq(.) + cq).  `out` may be `h`."""
         Cc = h.shape[1]
-        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(x0, x1, packed_q, Cc)
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(_OUT_16, x0, x1, packed_q, Cc)
         shape = (B, Cc, H, W)
         sh = self._chk_frames(h, dtype, "h", shape)
         sq, sz = self._chk_frames(cq, dtype, "cq", shape), self._chk_frames(z, dtype, "z", shape)
