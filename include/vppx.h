@@ -33,6 +33,8 @@
  *   FlowHead conv1 / conv2              raft_stereo/update.py:34-42 vppx_raft_conv_dt_dev
  *   BasicMultiUpdateBlock.mask, .25 *   raft_stereo/update.py:113-116,141 vppx_raft_conv_dt_dev
  *   ResidualBlock conv1 / conv2 / downsample, encoder conv2, output heads -> extractor.py:10-11,45,149,231,240,247 vppx_raft_conv_strided_dt_dev
+ *   feature_extraction convbn / BasicBlock  psmnet/submodule.py:29-42,60-84 vppx_conv2d_dt_dev
+ *   feature_extraction branches, cat    psmnet/submodule.py:149-171,208-250 vppx_psm_spp_pool_dt_dev, vppx_raft_gru_assemble_strided_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -1039,6 +1041,59 @@ int vppx_raft_conv_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const
 int vppx_raft_conv_strided_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
                                   const void *packed, int Cout, int ksize, int stride, int B, int H, int W, int relu, float scale,
                                   void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
+/* ---- PSMNet's feature_extraction (models/psmnet/submodule.py:131-253) on the convolution kernel ----------------------------
+ * Its convolutions are convbn groups, Conv2d(bias=False) -> BatchNorm2d [-> ReLU], and BasicBlocks, out = conv2bn(conv1bn_relu(x));
+ * out += x (:60-84).  A frozen BatchNorm folds into the weights and the bias on the host (vppstereo_amd/_convs.py), the sum with x
+ * goes into the epilogue, layer4's dilation into the kernel:
+ * vppx_conv2d_dt_dev is vppx_raft_conv_strided_dt_dev with `dilation` behind stride and a residual in front of relu:
+ *     nn.Conv2d(Cin, Cout, ksize, stride=stride, padding=dilation * (ksize / 2), dilation=dilation)
+ *     ksize 3:  acc[b][m][y][x] = sum over c < Cin, dy < 3, dx < 3 of
+ *                                 w[m][c][dy][dx] * in[b][c][stride*y + dilation*(dy - 1)][stride*x + dilation*(dx - 1)]
+ * with +0 outside the map; the output's size is that of the strided call for either dilation.  Built: dilation 1 with everything
+ * the strided call takes, and dilation 2 at stride 1; at dilation 2 a ksize of 1 is the 1x1 convolution itself, the bits of
+ * dilation 1.  The packed weights are those of vppx_raft_conv_pack_dev: one buffer serves every stride and dilation.
+ * The epilogue, every step one correctly rounded float32 operation:
+ *     v = acc + bias[m];   res: v = v + res[b][m][y][x] (a bfloat16 cell widened);   relu: v = v < 0 ? 0 : v (a NaN stays NaN);
+ *     out[b][m][y][x] = v * scale
+ * res is NULL or [B,Cout,Ho,Wo] with a frame stride of its own, at least Cout*Ho*Wo; it moves 16 bytes at a time under the rule
+ * the gates' inputs follow above (its pointer and frame stride count with out's), cell by cell otherwise, with the same bits.
+ * out may be res itself, the same pointer and frame stride: each cell is read by the lane that writes it.  out and res must not
+ * overlap x0 or x1.  With res == NULL and dilation 1 the call gives the bits of vppx_raft_conv_strided_dt_dev.
+ * NaN rule at dilation 2, ksize 3: a NaN (or infinite) input cell (r, c) reaches exactly the output pixels (r + 2i, c + 2j), i, j
+ * in -1 .. 1, that lie inside the map, in every output channel of its frame, and nothing else: not (r +- 1, c +- 1).  A NaN in
+ * res stays in its cell.
+ * Refused before anything is launched, with no output byte touched, in this order where several apply: everything
+ * vppx_raft_conv_strided_dt_dev refuses, with its code; behind the stride's refusal, a dilation other than 1 and 2, or
+ * dilation 2 at stride 2 (VPPX_E_UNSUPPORTED); among the frame strides, a res_frame_stride below Cout*Ho*Wo
+ * (VPPX_E_INVALID_ARG), in front of out's. */
+int vppx_conv2d_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                       const void *packed, int Cout, int ksize, int stride, int dilation, int B, int H, int W,
+                       const void *res, int64_t res_frame_stride, int relu, float scale,
+                       void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
+/* The pyramid pooling's average pools (submodule.py:149-171): every level in one launch, x [B,C,H,W] read once.
+ *     level i:  nn.AvgPool2d((k, k), stride=(k, k)), k = ks[i];   outs[i] is [B,C,H/k,W/k] (integer division), contiguous
+ *     out[y][x] = (the float32 sum of the k*k cells x[k*y .. k*y+k-1][k*x .. k*x+k-1]) / (float)(k*k), one correctly rounded division
+ * The order of the sum is the library's (spp_kernels.hip states it): it depends on (H, W, ks) alone, never on the dispatch, so a
+ * call gives the same bits run after run; tests/_psm_ref.py bounds any order.  Rows and columns behind (H/k)*k and (W/k)*k are
+ * not read for that level: a NaN there reaches nothing of it; a NaN inside reaches the one cell whose window holds it.
+ * ks and outs are HOST arrays of n_levels entries, outs of device pointers; the levels need not nest or be ordered, and no
+ * pointer has to be aligned beyond its cell.  Stream-ordered, never synchronises, allocates nothing.
+ * Refused before anything is launched, with no output byte touched: a NULL x, ks, outs or outs[i]; B, C, H or W <= 0; n_levels
+ * outside 1 .. VPPX_SPP_MAX_LEVELS; a k < 1; H/k or W/k == 0; x_frame_stride below C*H*W; a dtype other than the two
+ * (VPPX_E_INVALID_ARG); a k above VPPX_SPP_MAX_K, or B*C above 2^31 - 1 (VPPX_E_UNSUPPORTED). */
+#define VPPX_SPP_MAX_LEVELS 4
+#define VPPX_SPP_MAX_K 64
+int vppx_psm_spp_pool_dt_dev(const void *x, int64_t x_frame_stride, int B, int C, int H, int W, int n_levels,
+                             const int *ks /* host */, void *const *outs /* host array of device pointers */, int dtype, vppx_ctx *ctx);
+/* vppx_raft_gru_assemble_dt_dev (above) into a channel slice: the destination's frames lie out_frame_stride cells apart, at
+ * least sum C_i * H * W; channels 0 .. sum C_i - 1 of each frame are written and no cell behind them.  The same kernel, the same
+ * arithmetic and the same 16-byte rule, out_frame_stride in hx_channels*H*W's place: with out_frame_stride = hx_channels*H*W
+ * the bits of vppx_raft_gru_assemble_dt_dev.  PSMNet's four upsampled branches are one such call of four VPPX_GRU_INTERP sources
+ * into channels 192 .. 319 of the 320-channel feature buffer (submodule.py:243-250).  Refusals: those of the assemble call, an
+ * out_frame_stride below sum C_i * H * W in the place of hx_channels below sum C_i.  The context comes last, as in every call
+ * of the flat form. */
+int vppx_raft_gru_assemble_strided_dt_dev(const VppxGruSource *sources, int n_sources, int B, int H, int W, void *out,
+                                          int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
 /* Disparity payload decoders (dataloaders/frame_utils.py): KITTI uint16 PNG samples -> disp = v/256
  * float32 + valid = disp>0 uint8 (readDispKITTI :66-69, valid may be NULL); PFM payload (after the
  * text header) -> float32 [H,W(,3)] flipped upside-down, byte-swapped if big-endian (readPFM :34-64).

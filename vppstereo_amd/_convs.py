@@ -1,23 +1,55 @@
-"""What FusedUpdate (update.py) and FusedEncoder (extractor.py) share around `Engine.raft_conv`: the decision whether the
-kernel takes a convolution, and the one cache of packed weights.
+"""What FusedUpdate (update.py), FusedEncoder (extractor.py) and FusedFeatureExtraction (psmnet.py) share around
+`Engine.raft_conv` / `Engine.conv2d`: the decision whether the kernel takes a convolution, the fold of a frozen BatchNorm into
+a convolution's weights, and the one cache of packed weights.
 """
 import weakref
 
 import torch
 
 
-def conv_plain(conv, cin, strides=((1, 1),)):
-    """Whether Engine.raft_conv takes this module on `cin` input channels: an nn.Conv2d whose forward is nn.Conv2d's, 1x1 or
-    3x3, a stride of `strides`, dilation 1, groups 1, zeros outside the map, padding k // 2, within the channel counts that
-    are built."""
+def conv_plain(conv, cin, strides=((1, 1),), dilations=((1, 1),)):
+    """Whether Engine.raft_conv (Engine.conv2d, with `dilations`) takes this module on `cin` input channels: an nn.Conv2d whose
+    forward is nn.Conv2d's, 1x1 or 3x3, a stride of `strides`, a dilation d of `dilations` (dilation 1 unless the caller names
+    others; (2, 2) goes with stride (1, 1) only), groups 1, zeros outside the map, padding d * (k // 2), within the channel
+    counts that are built."""
     from . import _lib
     if not isinstance(conv, torch.nn.Conv2d) or type(conv).forward is not torch.nn.Conv2d.forward:
         return False
-    k = conv.kernel_size[0]
+    k, d = conv.kernel_size[0], tuple(conv.dilation)
     return (tuple(conv.kernel_size) in ((1, 1), (3, 3)) and tuple(conv.weight.shape) == (conv.out_channels, cin, k, k)
-            and conv.padding == (k // 2, k // 2) and tuple(conv.stride) in strides and conv.dilation == (1, 1) and conv.groups == 1
+            and d in dilations and d in ((1, 1), (2, 2)) and conv.padding == (d[0] * (k // 2), d[0] * (k // 2))
+            and tuple(conv.stride) in strides and (d == (1, 1) or tuple(conv.stride) == (1, 1)) and conv.groups == 1
             and conv.padding_mode == "zeros" and cin % 16 == 0 and 0 < cin <= _lib.CONV_MAX_CIN
             and 0 < conv.out_channels <= _lib.CONV_MAX_COUT)
+
+
+def frozen_bn(bn, what):
+    """Raise the TypeError of a wrapper for a norm that cannot be folded: anything but a BatchNorm2d in eval mode with running
+    statistics."""
+    if not isinstance(bn, torch.nn.BatchNorm2d):
+        raise TypeError(f"{what} is {type(bn).__name__}, not a BatchNorm2d")
+    if bn.training:
+        raise TypeError(f"{what} is in training mode; only a frozen BatchNorm2d (model.eval()) folds into its convolution")
+    if bn.running_mean is None or bn.running_var is None:
+        raise TypeError(f"{what} keeps no running statistics (track_running_stats=False): there is nothing to fold")
+
+
+def fold_bn(conv, bn):
+    """(weight [Cout,Cin,k,k], bias [Cout]) float32 of the convolution that equals bn(conv(x)) for a BatchNorm2d in eval mode,
+    computed in float64 and rounded to float32 once each:
+        s = gamma / sqrt(running_var + eps);   w' = w * s[m];   b' = beta + (conv_bias - running_mean) * s
+    (gamma 1 and beta 0 for a norm without affine parameters)."""
+    frozen_bn(bn, "the norm")
+    f64 = lambda t: t.detach().double()                                                  # noqa: E731
+    s = 1.0 / torch.sqrt(f64(bn.running_var) + float(bn.eps))
+    if bn.weight is not None:
+        s = f64(bn.weight) * s
+    shift = -f64(bn.running_mean) if conv.bias is None else f64(conv.bias) - f64(bn.running_mean)
+    b = shift * s
+    if bn.bias is not None:
+        b = f64(bn.bias) + b
+    w = f64(conv.weight) * s[:, None, None, None]
+    return w.to(torch.float32).contiguous(), b.to(torch.float32).contiguous()
 
 
 class PackedWeights:
@@ -34,6 +66,16 @@ class PackedWeights:
         buffer serves either stride."""
         make = lambda: (eng.raft_conv_pack(conv.weight, conv.bias, dtype=dtype), None)      # noqa: E731
         return self._packed_for(conv, [conv.weight, conv.bias], make, dtype, device)[0]
+
+    def _packed_conv_bn(self, eng, conv, bn, dtype, device):
+        """The packed weights of `conv` with the frozen BatchNorm2d `bn` behind it folded in (fold_bn), kept under the
+        convolution: the conv cache rule over the convolution's two parameters and the norm's four tensors and eps, which is
+        what FusedEncoder._norm_consts looks at.  For bfloat16 the packing rounds the folded weights once more, as always."""
+        if bn.training:
+            raise RuntimeError("a BatchNorm2d went back to training mode; the wrapper is inference only")
+        make = lambda: (eng.raft_conv_pack(*fold_bn(conv, bn), dtype=dtype), None)          # noqa: E731
+        params = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return self._packed_for(conv, params, make, (dtype, float(bn.eps), id(bn)), device)[0]
 
     def _packed_for(self, owner, params, make, dtype, device):
         """The pair make() returns, kept under id(owner) while the device, the dtype and every parameter of `params` stay what they

@@ -27,6 +27,7 @@ DT_F32, DT_BF16 = _K["VPPX_DT_F32"], _K["VPPX_DT_BF16"]
 GRU_MAX_SOURCES = _K["VPPX_GRU_MAX_SOURCES"]
 MOTION_MAX_CH, MOTION_MAX_KS = _K["VPPX_MOTION_MAX_CH"], _K["VPPX_MOTION_MAX_KS"]
 CONV_MAX_CIN, CONV_MAX_COUT = _K["VPPX_CONV_MAX_CIN"], _K["VPPX_CONV_MAX_COUT"]
+SPP_MAX_LEVELS, SPP_MAX_K = _K["VPPX_SPP_MAX_LEVELS"], _K["VPPX_SPP_MAX_K"]
 GRU_MODES = {m: _K["VPPX_GRU_" + m.upper()] for m in ("copy", "pool2x", "interp")}
 FS_PATTERNS, FS_MASK, FS_GOCC, FS_GUIDED, FS_METRICS, FS_NO_DISP, FS_SAMPLE = (
     _K["VPPX_FS_" + n] for n in ("PATTERNS", "MASK", "GOCC", "GUIDED", "METRICS", "NO_DISP", "SAMPLE"))

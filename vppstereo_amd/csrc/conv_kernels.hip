@@ -35,6 +35,19 @@
 //     bytes apart as at stride 1, with the bank pattern of stride 1 (at 160 bytes, pixels 8 apart start on the same bank, and
 //     an M tile's rows are pixels 0-3, 8-11, 16-19, 24-27: the lanes of a read group would collide at least two ways), and the
 //     A fragment stays one 16-byte read per lane and tap.
+//
+// Dilation 2 (DIL = 2: nine taps, stride 1, plain epilogue only; PSMNet's layer4).  Tap (dy, dx) of output pixel (y, x) is input
+// cell (y + 2 (dy - 1), x + 2 (dx - 1)).  The staged image is the tile and a TWO-pixel halo, 12 x 36 = 432 pixels = 34.6 KB, so two
+// workgroups still share a CU, and tap (dy, dx) is the staged pixel 2 dy rows and 2 dx columns behind the lane's own at tap (0, 0).
+// The lanes of a read are the pixels of one M tile in one staged row, CV_ROWB bytes apart exactly as at dilation 1; a tap moves
+// all of them by the same 2 dx * 80 + 2 dy * 36 * 80 bytes, and a shift common to every lane of a read changes which bank each
+// lane starts on but not which lanes share one (160 bytes = 40 banks; at dilation 1 a tap step is 20 banks): the bank pattern of
+// a read is that of stride 1, one 16-byte read per lane and tap.  Staging: thread tid stages pixel tid whole, and the 176 pixels
+// beyond the first 256 are 2816 = 11 * 256 units, unit e = 256 j + tid being unit e / 176 of pixel 256 + e % 176 (neighbouring
+// threads read neighbouring pixels of one channel): 27 units per thread, every thread the same, read one chunk ahead.
+//
+// A residual (plain epilogue): v = acc + bias, then v + res[b][m][y][x] before the ReLU and the scale, res being read by the lane
+// that writes the cell, so that out may be res itself.
 #include "cells.h"
 #include "gru_math.h"
 
@@ -46,6 +59,8 @@
 #define CV_ODD2 (CV_TW + 1)      // odd columns of a staged row there, in front of the CV_TW even ones
 #define CV_HW2 (2 * CV_TW + 1)
 #define CV_HALO2 ((2 * CV_TH2 + 1) * CV_HW2)
+#define CV_HWD (CV_TW + 4)       // dilation 2: a staged row with its two-pixel halo
+#define CV_HALOD ((CV_TH + 4) * CV_HWD)
 #define CV_ROWB 80
 #define CV_NB 64
 
@@ -57,7 +72,7 @@ struct ConvArgs {
     long long s0, s1;        // cells between frames
     const uint4 *packed;     // [chunk][tap][N tile][lane] fragments
     const float *bias;       // [Cout], behind the fragments
-    const void *e0, *e1, *e2; // epilogue inputs: zr: cz, cr, h;  q: cq, z, h
+    const void *e0, *e1, *e2; // epilogue inputs: zr: cz, cr, h;  q: cq, z, h;  plain: e0 = the residual where res != 0
     long long se0, se1, se2;
     void *o0, *o1;           // plain: out;  zr: z, rh;  q: out
     long long so0, so1;
@@ -67,6 +82,7 @@ struct ConvArgs {
     int Cout;                // plain: channel m is stored where m < Cout (the gates' Cout is NT * 16)
     float scale;             // plain: out = relu(v) * scale
     int Hi, Wi;              // STRIDE == 2: the input's size
+    int res;                 // plain: v += e0[b][m][y][x] in front of the ReLU
 };
 
 // Eight cells of a [B,C,H,W] tensor from cell `at` on, the first `nv` of them inside the row.  vec: every base, stride, plane
@@ -110,17 +126,21 @@ __device__ __forceinline__ void cv_store8(void *p, size_t at, int nv, bool vec, 
 // TAPS = 9: the 3x3 convolution.  TAPS = 1: a 1x1 convolution as the centre tap of the same staged image; its halo slots are
 // written as +0 without a read, so that nothing but the tile's own pixels is fetched.
 // STRIDE = 2: see the head of the file.  S2 marks the 3x3 at stride 2, the one instance with a tile and a staged image of its own.
-template <bool BF16, int EPI, int TAPS, int STRIDE = 1>
+// DIL = 2: see the head of the file.
+template <bool BF16, int EPI, int TAPS, int STRIDE = 1, int DIL = 1>
 __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 {
     static_assert(TAPS == 9 || TAPS == 1, "3x3 or 1x1");
     static_assert(STRIDE == 1 || (STRIDE == 2 && EPI == CV_PLAIN), "stride 2 goes with the plain epilogue");
+    static_assert(DIL == 1 || (DIL == 2 && TAPS == 9 && STRIDE == 1 && EPI == CV_PLAIN), "dilation 2 goes with nine taps, stride 1 and the plain epilogue");
     constexpr int CK = BF16 ? 32 : 16;
-    constexpr bool S2 = STRIDE == 2 && TAPS == 9;
+    constexpr bool S2 = STRIDE == 2 && TAPS == 9, D2 = DIL == 2;
     constexpr int TH = S2 ? CV_TH2 : CV_TH, RPW = TH / 4, MT = 2 * RPW; // rows and M tiles of a wave
-    constexpr int HW = S2 ? CV_HW2 : CV_HW, NPIX = S2 ? CV_HALO2 : CV_HALO;
+    constexpr int HW = S2 ? CV_HW2 : D2 ? CV_HWD : CV_HW, NPIX = S2 ? CV_HALO2 : D2 ? CV_HALOD : CV_HALO;
     constexpr int NFULL = NPIX / 256, REM = NPIX - 256 * NFULL;        // pixels a thread stages whole, and those shared out
-    static_assert(3 * REM <= 256 && REM > 0, "the pixels beyond the whole rounds are spread three units apart");
+    static_assert(D2 || (3 * REM <= 256 && REM > 0), "the pixels beyond the whole rounds are spread three units apart");
+    constexpr int NB = D2 ? 16 * REM / 256 : 6;                        // units of the shared-out pixels a thread holds
+    static_assert(!D2 || (16 * REM == 256 * NB && 16 * NFULL + NB == 27), "dilation 2: every thread stages the same 27 units");
     __shared__ __attribute__((aligned(16))) unsigned char sA[NPIX * CV_ROWB];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, i = lane & 15;
@@ -151,14 +171,18 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
         } else {
             const int ry = p / HW, rx = p - ry * HW;
             in = TAPS == 9 || (ry >= 1 && ry <= CV_TH && rx >= 1 && rx <= CV_TW);
-            gy = STRIDE * (y0 + ry - 1), gx = STRIDE * (x0 + rx - 1);
+            gy = STRIDE * (y0 + ry - DIL), gx = STRIDE * (x0 + rx - DIL);
         }
         return in && gy >= 0 && gy < Hi && gx >= 0 && gx < Wi ? gy * Wi + gx : -1;
     };
-    int offA[NFULL], offB;
+    int offA[NFULL], offB, offD[D2 ? NB : 1];
 #pragma unroll
     for (int f = 0; f < NFULL; f++) offA[f] = source(tid + 256 * f);
-    offB = uB < 3 ? source(pB) : -1;
+    offB = !D2 && uB < 3 ? source(pB) : -1;
+    if (D2) {
+#pragma unroll
+        for (int j = 0; j < NB; j++) offD[j] = source(256 * NFULL + (tid + 256 * j) % REM);
+    }
     auto unit = [&](int chunk, int u, int off) -> u32 {
         const int c = chunk * CK + (BF16 ? 2 * u : u);
         if (off < 0 || c >= a.Cin) return 0u; // +0 outside the map and for the channels that pad K
@@ -171,14 +195,19 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
         }
         return ((const u32 *)src)[at];
     };
-    u32 stA[NFULL][16], stB[6];
+    u32 stA[NFULL][16], stB[NB];
     auto fetch = [&](int chunk) {
 #pragma unroll
         for (int f = 0; f < NFULL; f++)
 #pragma unroll
             for (int u = 0; u < 16; u++) stA[f][u] = unit(chunk, u, offA[f]);
+        if (D2) {
 #pragma unroll
-        for (int j = 0; j < 6; j++) stB[j] = uB + 3 * j < 16 ? unit(chunk, uB + 3 * j, offB) : 0u;
+            for (int j = 0; j < NB; j++) stB[j] = unit(chunk, (tid + 256 * j) / REM, offD[D2 ? j : 0]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NB; j++) stB[j] = uB + 3 * j < 16 ? unit(chunk, uB + 3 * j, offB) : 0u;
+        }
     };
     fetch(0);
 
@@ -208,9 +237,13 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 #pragma unroll
             for (int k = 0; k < 4; k++)
                 *(uint4 *)(sA + (tid + 256 * f) * CV_ROWB + 16 * k) = make_uint4(stA[f][4 * k], stA[f][4 * k + 1], stA[f][4 * k + 2], stA[f][4 * k + 3]);
-        if (uB < 3) {
+        if (D2) {
 #pragma unroll
-            for (int j = 0; j < 6; j++)
+            for (int j = 0; j < NB; j++)
+                *(u32 *)(sA + (256 * NFULL + (tid + 256 * j) % REM) * CV_ROWB + 4 * ((tid + 256 * j) / REM)) = stB[j];
+        } else if (uB < 3) {
+#pragma unroll
+            for (int j = 0; j < NB; j++)
                 if (uB + 3 * j < 16) *(u32 *)(sA + pB * CV_ROWB + 4 * (uB + 3 * j)) = stB[j];
         }
         __syncthreads();
@@ -224,7 +257,7 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
                     if (n < ntl) bnext[n] = pk[(size_t)(s + 1) * step + 64 * n];
             }
             // S2: columns 2x - 1 and 2x + 1 are slots x and x + 1 of the odd part, column 2x slot x of the even part behind it
-            const int toff = (S2 ? (tap / 3) * HW + (tap % 3 == 1 ? CV_ODD2 : tap % 3 / 2) : TAPS == 9 ? (tap / 3) * CV_HW + tap % 3 : CV_HW + 1) * CV_ROWB;
+            const int toff = (S2 ? (tap / 3) * HW + (tap % 3 == 1 ? CV_ODD2 : tap % 3 / 2) : TAPS == 9 ? DIL * ((tap / 3) * HW + tap % 3) : CV_HW + 1) * CV_ROWB;
             uint4 fa[MT];
 #pragma unroll
             for (int m = 0; m < MT; m++) fa[m] = *(const uint4 *)(sA + la[m] + toff);
@@ -275,6 +308,12 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 #pragma unroll
             for (int j = 0; j < 8; j++) v[j] = __fadd_rn(acc[2 * p + (j >> 2)][n][j & 3], bias);
             if (EPI == CV_PLAIN) {
+                if (a.res) { // uniform over the launch; out may be the residual: read before the store
+                    float r[8];
+                    cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * plane + pix, nv, vec, r);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) v[j] = __fadd_rn(v[j], r[j]);
+                }
 #pragma unroll
                 for (int j = 0; j < 8; j++) o[j] = __fmul_rn(a.relu ? relu_nan(v[j]) : v[j], a.scale);
                 cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
@@ -376,13 +415,14 @@ int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, i
     return 0;
 }
 
-// one launch per (epilogue, taps, stride) that is built: ksize 1, stride 2 and a Cout that is no multiple of 16 go with the plain
-// epilogue only (vppx_net_api.hip sees to it)
+// one launch per (epilogue, taps, stride, dilation) that is built: ksize 1, stride 2, dilation 2 and a Cout that is no multiple
+// of 16 go with the plain epilogue only, dilation 2 with stride 1; a 1x1 at dilation 2 is the 1x1 itself (vppx_net_api.hip sees to it)
 template <bool BF16>
 static void conv_launch(vppx_ctx *ctx, const ConvCall &c, const ConvArgs &a, dim3 grid)
 {
     if (c.epi == CV_PLAIN && c.stride == 2 && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1, 2><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_PLAIN && c.stride == 2) raft_conv3x3_kernel<BF16, CV_PLAIN, 9, 2><<<grid, 256, 0, ctx->stream>>>(a);
+    else if (c.epi == CV_PLAIN && c.ksize == 3 && c.dilation == 2) raft_conv3x3_kernel<BF16, CV_PLAIN, 9, 1, 2><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_PLAIN && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_PLAIN) raft_conv3x3_kernel<BF16, CV_PLAIN, 9><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_ZR) raft_conv3x3_kernel<BF16, CV_ZR, 9><<<grid, 256, 0, ctx->stream>>>(a);
@@ -403,7 +443,7 @@ int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c)
     a.o0 = (void *)c.out[0].p, a.o1 = (void *)c.out[1].p, a.so0 = (long long)c.out[0].stride, a.so1 = (long long)c.out[1].stride;
     const int Ho = (c.H - 1) / c.stride + 1, Wo = (c.W - 1) / c.stride + 1, th = c.stride == 2 && c.ksize == 3 ? CV_TH2 : CV_TH;
     a.H = Ho, a.W = Wo, a.Hi = c.H, a.Wi = c.W, a.tilesX = (Wo + CV_TW - 1) / CV_TW, a.tilesY = (Ho + th - 1) / th;
-    a.C = c.C, a.relu = c.relu;
+    a.C = c.C, a.relu = c.relu, a.res = c.epi == CV_PLAIN && c.in[0].p != NULL;
     const size_t tiles = (size_t)c.B * a.tilesX * a.tilesY;
     if (tiles > 0x7FFFFFFFull) {
         vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, c.B, Ho, Wo, tiles);

@@ -221,11 +221,12 @@ static int gru_grid(const char *who, int B, long long n, int V, long long *G, si
     return 0;
 }
 
-int gru_assemble(vppx_ctx *ctx, const VppxGruSource *src, int n_src, int B, int H, int W, void *hx, int hx_channels, int dtype)
+// shx: cells between the frames of hx, at least the sources' channels; the cells of a frame behind them are not written
+int gru_assemble(vppx_ctx *ctx, const VppxGruSource *src, int n_src, int B, int H, int W, void *hx, int64_t hx_frame_stride, int dtype)
 {
     const bool bf16 = dtype == VPPX_DT_BF16;
     const int VF = bf16 ? 8 : 4;
-    const long long plane = (long long)H * W, shx = (long long)hx_channels * plane;
+    const long long plane = (long long)H * W, shx = (long long)hx_frame_stride;
     GruAsm a;
     memset(&a, 0, sizeof(a));
     a.n = n_src;

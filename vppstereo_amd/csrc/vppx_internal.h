@@ -572,7 +572,7 @@ int readout_raft_upsample(vppx_ctx *ctx, const void *flow, int64_t flow_frame_st
                           int sign, int top, int left, int Hout, int Wout, float *out, int dtype);
 
 // gru_kernels.hip: the update block's glue (models/raft_stereo/update.py:23-32, 87-97, 119-142)
-int gru_assemble(vppx_ctx *ctx, const VppxGruSource *src, int n_src, int B, int H, int W, void *hx, int hx_channels, int dtype);
+int gru_assemble(vppx_ctx *ctx, const VppxGruSource *src, int n_src, int B, int H, int W, void *hx, int64_t hx_frame_stride, int dtype);
 int gru_reset(vppx_ctx *ctx, const void *ar, int64_t sar, const void *cr, int64_t scr, const void *h, int64_t sh, void *hx, int64_t shx,
               int B, int C, int H, int W, int dtype);
 int gru_update(vppx_ctx *ctx, const void *az, int64_t saz, const void *cz, int64_t scz, const void *aq, int64_t saq, const void *cq,
@@ -585,7 +585,8 @@ int motion_front(vppx_ctx *ctx, const void *corr, const void *pyr, const float *
                  int64_t out_f_frame_stride, int dtype, int out_dtype);
 
 // conv_kernels.hip: the 3x3 convolution on the matrix cores and ConvGRU's gates as its epilogues (update.py:19-32).
-// The plain epilogue takes any Cout >= 1 (padded to 16 in the packing, masked in the store), ksize 1, stride 2 and a scale;
+// The plain epilogue takes any Cout >= 1 (padded to 16 in the packing, masked in the store), ksize 1, stride 2, dilation 2 (at
+// stride 1), a residual and a scale;
 // the gates take ksize 3, stride 1, Cout % 16 == 0 and ignore the scale.
 enum ConvEpi { CV_PLAIN = 0, CV_ZR = 1, CV_Q = 2 };
 
@@ -599,22 +600,25 @@ struct ConvTensor {
 // One call of the convolution kernel; what is left out is the 3x3 call at stride 1.
 struct ConvCall {
     ConvEpi epi = CV_PLAIN;
-    int ksize = 3, stride = 1, dtype = VPPX_DT_F32;
+    int ksize = 3, stride = 1, dilation = 1, dtype = VPPX_DT_F32;
     const void *x0 = NULL, *x1 = NULL; // the input is cat([x0, x1], dim=1); x1 is not read where C1 == 0
     int64_t s0 = 0, s1 = 0;            // cells between frames
     int C0 = 0, C1 = 0;
     const void *packed = NULL;         // conv_pack's buffer for (Cout, C0 + C1, ksize, dtype)
     int Cout = 0;                      // output channels of the packed weights (zr packs convz and convr: 2 C)
-    ConvTensor in[3];                  // zr: cz, cr, h;  q: cq, z, h
+    ConvTensor in[3];                  // zr: cz, cr, h;  q: cq, z, h;  plain: the residual [B,Cout,Ho,Wo], or none
     ConvTensor out[2];                 // plain: out;  zr: z, rh;  q: out
     int B = 0, C = 0, H = 0, W = 0;    // C: the hidden size of the gates.  H, W: the input's; the output is (H - 1) / stride + 1 high
-    int relu = 0;                      // plain: out = relu(v) * scale
+    int relu = 0;                      // plain: out = relu(v [+ res]) * scale
     float scale = 1.0f;
 };
 
 size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype);
 int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed);
 int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c); // every field has been checked by vppx_net_api.hip
+
+// spp_kernels.hip: PSMNet's pyramid pooling (models/psmnet/submodule.py:149-171), every level in one launch
+int spp_pool(vppx_ctx *ctx, const void *x, int64_t sx, int B, int C, int H, int W, int n_levels, const int *ks, void *const *outs, int dtype);
 
 // norm_kernels.hip: the encoders' glue (models/raft_stereo/extractor.py:48-60, :181-183, :276-278)
 int norm_stats_pieces(int64_t planes, int64_t cells); // host arithmetic: workgroups per plane

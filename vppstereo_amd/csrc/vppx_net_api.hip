@@ -232,10 +232,10 @@ static int gru_shape_ok(const char *who, int B, int C, int H, int W, int dtype)
     return 0;
 }
 
-extern "C" int vppx_raft_gru_assemble_dt_dev(vppx_ctx *ctx, const VppxGruSource *sources, int n_sources, int B, int H, int W, void *hx,
-                                             int hx_channels, int dtype)
+// both assemble calls: the strided one's destination is checked by its frame stride, the other's by its channels
+static int gru_assemble_call(const char *who, bool strided, vppx_ctx *ctx, const VppxGruSource *sources, int n_sources, int B, int H, int W,
+                             void *hx, int hx_channels, int64_t hx_frame_stride, int dtype)
 {
-    static const char *who = "vppx_raft_gru_assemble";
     int rc;
     VPPX_ENTER(ctx);
     if (!sources || !hx) {
@@ -276,11 +276,32 @@ extern "C" int vppx_raft_gru_assemble_dt_dev(vppx_ctx *ctx, const VppxGruSource 
         if ((rc = gru_stride_ok(who, "source", s.frame_stride, s.C, s.Hs, s.Ws))) return rc;
         channels += s.C;
     }
+    if (strided) {
+        if (hx_frame_stride < channels * H * W) {
+            vppx_set_error("%s: out_frame_stride %lld is less than the sources' %lld planes of %dx%d", who, (long long)hx_frame_stride,
+                           (long long)channels, H, W);
+            return VPPX_E_INVALID_ARG;
+        }
+        return gru_assemble(ctx, sources, n_sources, B, H, W, hx, hx_frame_stride, dtype);
+    }
     if (hx_channels < channels) {
         vppx_set_error("%s: hx has %d channels, the sources have %lld", who, hx_channels, (long long)channels);
         return VPPX_E_INVALID_ARG;
     }
-    return gru_assemble(ctx, sources, n_sources, B, H, W, hx, hx_channels, dtype);
+    return gru_assemble(ctx, sources, n_sources, B, H, W, hx, (int64_t)hx_channels * H * W, dtype);
+}
+
+extern "C" int vppx_raft_gru_assemble_dt_dev(vppx_ctx *ctx, const VppxGruSource *sources, int n_sources, int B, int H, int W, void *hx,
+                                             int hx_channels, int dtype)
+{
+    return gru_assemble_call("vppx_raft_gru_assemble", false, ctx, sources, n_sources, B, H, W, hx, hx_channels, 0, dtype);
+}
+
+// the same into a channel slice: the destination's frames out_frame_stride cells apart (PSMNet's 320-channel feature buffer)
+extern "C" int vppx_raft_gru_assemble_strided_dt_dev(const VppxGruSource *sources, int n_sources, int B, int H, int W, void *out,
+                                                     int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
+{
+    return gru_assemble_call("vppx_raft_gru_assemble_strided", true, ctx, sources, n_sources, B, H, W, out, 0, out_frame_stride, dtype);
 }
 
 extern "C" int vppx_raft_gru_reset_dt_dev(vppx_ctx *ctx, const void *ar, int64_t ar_frame_stride, const void *cr, int64_t cr_frame_stride,
@@ -527,6 +548,10 @@ static int conv_call_ok(const char *who, const ConvCall &c, ConvRule rule)
         vppx_set_error("%s: a stride of %d: 1 and 2 are built", who, c.stride);
         return VPPX_E_UNSUPPORTED;
     }
+    if ((c.dilation != 1 && c.dilation != 2) || (c.dilation == 2 && c.stride == 2)) {
+        vppx_set_error("%s: a dilation of %d at stride %d: dilation 1, and dilation 2 at stride 1, are built", who, c.dilation, c.stride);
+        return VPPX_E_UNSUPPORTED;
+    }
     if (c.epi == CV_ZR && (c.C % 16 || c.C > VPPX_CONV_MAX_COUT / 2)) {
         vppx_set_error("%s: a hidden size of %d makes 2 x %d output channels: multiples of 16 up to %d in all are built", who, c.C, c.C,
                        VPPX_CONV_MAX_COUT);
@@ -552,17 +577,20 @@ static int conv_call_ok(const char *who, const ConvCall &c, ConvRule rule)
     return conv_ksize_ok(who, c.ksize);
 }
 
-// the plain call at stride 1 or 2: H, W are the input's, out is [B,Cout,(H - 1) / stride + 1,(W - 1) / stride + 1]
+// the plain call at stride 1 or 2: H, W are the input's, out is [B,Cout,(H - 1) / stride + 1,(W - 1) / stride + 1]; res, where there
+// is one, is of out's shape
 static int conv_plain_call(const char *who, ConvRule rule, const void *x0, int64_t x0_frame_stride, int C0, const void *x1,
                            int64_t x1_frame_stride, int C1, const void *packed, int Cout, int ksize, int stride, int B, int H, int W, int relu,
-                           float scale, void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx)
+                           float scale, void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx, int dilation = 1,
+                           const void *res = NULL, int64_t res_frame_stride = 0)
 {
     int rc;
     VPPX_ENTER(ctx);
     ConvCall c;
-    c.ksize = ksize, c.stride = stride, c.dtype = dtype, c.B = B, c.H = H, c.W = W;
+    c.ksize = ksize, c.stride = stride, c.dilation = dilation, c.dtype = dtype, c.B = B, c.H = H, c.W = W;
     c.x0 = x0, c.s0 = x0_frame_stride, c.C0 = C0, c.x1 = x1, c.s1 = x1_frame_stride, c.C1 = C1;
     c.packed = packed, c.Cout = Cout, c.relu = relu != 0, c.scale = scale;
+    if (res) c.in[0] = {"res", res, res_frame_stride};
     c.out[0] = {"out", out, out_frame_stride};
     if ((rc = conv_call_ok(who, c, rule))) return rc;
     return conv_run(ctx, who, c);
@@ -591,6 +619,55 @@ extern "C" int vppx_raft_conv_strided_dt_dev(const void *x0, int64_t x0_frame_st
 {
     return conv_plain_call("vppx_raft_conv_strided", CONV_OUT_ANY, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, ksize, stride,
                            B, H, W, relu, scale, out, out_frame_stride, dtype, ctx);
+}
+
+// nn.Conv2d(Cin, Cout, ksize, stride=stride, padding=dilation * (ksize / 2), dilation=dilation) with a residual in front of the
+// ReLU: PSMNet's feature_extraction (models/psmnet/submodule.py:29-42 convbn, :60-84 BasicBlock) with its BatchNorm folded
+extern "C" int vppx_conv2d_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,
+                                  const void *packed, int Cout, int ksize, int stride, int dilation, int B, int H, int W, const void *res,
+                                  int64_t res_frame_stride, int relu, float scale, void *out, int64_t out_frame_stride, int dtype,
+                                  vppx_ctx *ctx)
+{
+    return conv_plain_call("vppx_conv2d", CONV_OUT_ANY, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, ksize, stride, B, H, W,
+                           relu, scale, out, out_frame_stride, dtype, ctx, dilation, res, res_frame_stride);
+}
+
+// PSMNet's pyramid pooling (spp_kernels.hip; submodule.py:149-171 the four AvgPool2d).  ks and outs are host arrays.
+extern "C" int vppx_psm_spp_pool_dt_dev(const void *x, int64_t x_frame_stride, int B, int C, int H, int W, int n_levels, const int *ks,
+                                        void *const *outs, int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_psm_spp_pool";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!x || !ks || !outs) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (n_levels < 1 || n_levels > VPPX_SPP_MAX_LEVELS) {
+        vppx_set_error("%s: %d levels, 1 .. %d are taken", who, n_levels, VPPX_SPP_MAX_LEVELS);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, B, C, H, W, dtype)) || (rc = gru_stride_ok(who, "x", x_frame_stride, C, H, W))) return rc;
+    for (int i = 0; i < n_levels; i++) {
+        if (!outs[i]) {
+            vppx_set_error("%s: level %d: bad arguments", who, i);
+            return VPPX_E_INVALID_ARG;
+        }
+        if (ks[i] < 1 || (ks[i] <= VPPX_SPP_MAX_K && (H / ks[i] == 0 || W / ks[i] == 0))) {
+            vppx_set_error("%s: level %d: a window of %d over a %dx%d map leaves no cell", who, i, ks[i], H, W);
+            return VPPX_E_INVALID_ARG;
+        }
+    }
+    for (int i = 0; i < n_levels; i++)
+        if (ks[i] > VPPX_SPP_MAX_K) {
+            vppx_set_error("%s: level %d: a window of %d, up to %d are built", who, i, ks[i], VPPX_SPP_MAX_K);
+            return VPPX_E_UNSUPPORTED;
+        }
+    if ((int64_t)B * C > 0x7FFFFFFF) {
+        vppx_set_error("%s: %d frames of %d planes are more workgroups than one launch takes", who, B, C);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return spp_pool(ctx, x, x_frame_stride, B, C, H, W, n_levels, ks, outs, dtype);
 }
 
 extern "C" int vppx_raft_gru_zr_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const void *x1, int64_t x1_frame_stride, int C1,

@@ -845,7 +845,9 @@ class Engine:
         (avg_pool2d(3, stride=2, padding=1)) and "interp" its interp (bilinear, align_corners=True) to the H x W of the
         result, which a copied source or `out` fixes.  float32 or bfloat16, all the same; every tensor may be a channel
         slice of a wider one.  -> contiguous [B, sum C_i, H, W]; with `out` nothing is allocated, and an `out` of more
-        channels keeps the others (include/vppx.h has the arithmetic)."""
+        channels keeps the others (include/vppx.h has the arithmetic).  `out` may itself be a channel slice of a wider tensor
+        whose frames are contiguous (vppx_raft_gru_assemble_strided_dt_dev): the cells of the wider tensor outside the
+        sources' channels are not written."""
         torch = self.torch
         sources = list(sources)
         if not 1 <= len(sources) <= _lib.GRU_MAX_SOURCES:
@@ -868,6 +870,14 @@ class Engine:
             if size is None:
                 raise ValueError("sources: no copied source fixes the size of hx; pass out=")
             out = torch.empty((B, total) + size, dtype=dtype, device=self.device)
+        elif not out.is_contiguous():
+            so = self._chk_frames(out, dtype, "out")
+            if out.shape[0] != B or out.shape[1] < total:
+                raise ValueError(f"out: expected [{B},>={total},H,W], got {tuple(out.shape)}")
+            self._bind_stream()
+            _lib.check(self.lib.vppx_raft_gru_assemble_strided_dt_dev(arr, len(sources), B, out.shape[2], out.shape[3], _ptr(out), so, dt,
+                                                                      self.ctx.handle))
+            return out
         else:
             self._chk(out, dtype, 4, "out")
             if out.shape[0] != B:
@@ -1014,6 +1024,47 @@ class Engine:
         `out` may be channel slices of wider tensors, and no cell of `out`'s buffer outside its cout channels is written.
         -> [B,cout,Ho,Wo] with Ho = (H - 1) // stride + 1, Wo likewise; with `out` nothing is allocated."""
         return self._conv_plain(_OUT_ANY, x0, x1, packed, cout, int(ksize), stride, relu, scale, out)
+
+    def conv2d(self, x0, packed, cout, ksize, x1=None, stride=1, dilation=1, residual=None, relu=False, scale=1.0, out=None):
+        """raft_conv with a dilation and a residual (vppx_conv2d_dt_dev; PSMNet's feature_extraction with its BatchNorm folded):
+        nn.Conv2d(C0 + C1, cout, ksize, stride=stride, padding=dilation * (ksize // 2), dilation=dilation) on cat([x0, x1], dim=1),
+        + bias, + `residual` [B,cout,Ho,Wo] where there is one, with `relu` torch's ReLU, then * scale.  Dilation 1 takes what
+        raft_conv takes, dilation 2 goes with stride 1.  `packed` is raft_conv_pack's.  `out` may be `residual` itself; every
+        tensor may be a channel slice of a wider one.  -> [B,cout,Ho,Wo]; with `out` nothing is allocated."""
+        ksize, cout, stride, dilation, relu = int(ksize), int(cout), int(stride), int(dilation), int(bool(relu))
+        dtype, dt, B, H, W, s0, C0, s1, C1 = self._chk_conv(_OUT_ANY, x0, x1, packed, cout, ksize)
+        if stride not in (1, 2):
+            raise ValueError(f"stride is {stride}; 1 and 2 are built")
+        if dilation not in (1, 2) or (dilation == 2 and stride == 2):
+            raise ValueError(f"dilation is {dilation} at stride {stride}; dilation 1, and dilation 2 at stride 1, are built")
+        shape = (B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1)
+        sr = 0 if residual is None else self._chk_frames(residual, dtype, "residual", shape)
+        if out is None:
+            out = self.torch.empty(shape, dtype=dtype, device=self.device)
+        so = self._chk_frames(out, dtype, "out", shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_conv2d_dt_dev(_ptr(x0), s0, C0, _ptr(x1), s1, C1, _ptr(packed), cout, ksize, stride, dilation, B, H, W,
+                                               _ptr(residual), sr, relu, float(scale), _ptr(out), so, dt, self.ctx.handle))
+        return out
+
+    def psm_spp_pool(self, x, ks=(8, 16, 32, 64)):
+        """The average pools of PSMNet's pyramid pooling in one launch (vppx_psm_spp_pool_dt_dev): x [B,C,H,W], float32 or
+        bfloat16, possibly a channel slice of a wider tensor, read once -> [nn.AvgPool2d((k, k), stride=(k, k))(x) for k in ks],
+        each [B,C,H // k,W // k] contiguous (include/vppx.h has the arithmetic)."""
+        dtype, dt = self._norm_dtype(x, "x")
+        sx = self._chk_frames(x, dtype, "x")
+        B, Cc, H, W = x.shape
+        ks = [int(k) for k in ks]
+        if not 1 <= len(ks) <= _lib.SPP_MAX_LEVELS:
+            raise ValueError(f"ks: {len(ks)} levels, 1 .. {_lib.SPP_MAX_LEVELS} are taken")
+        for k in ks:
+            if not 1 <= k <= _lib.SPP_MAX_K or H // k == 0 or W // k == 0:
+                raise ValueError(f"ks: a window of {k} over a {H}x{W} map: 1 .. {_lib.SPP_MAX_K} that leave a cell are taken")
+        outs = [self.torch.empty((B, Cc, H // k, W // k), dtype=dtype, device=self.device) for k in ks]
+        self._bind_stream()
+        _lib.check(self.lib.vppx_psm_spp_pool_dt_dev(_ptr(x), sx, B, Cc, H, W, len(ks), (C.c_int * len(ks))(*ks),
+                                                     (C.c_void_p * len(ks))(*[o.data_ptr() for o in outs]), dt, self.ctx.handle))
+        return outs
 
     def raft_gru_zr(self, x0, packed_zr, cz, cr, h, x1=None, z=None, rh=None):
         """convz and convr of a ConvGRU (update.py:27-28) in one launch with their gates: `packed_zr` holds
