@@ -35,6 +35,7 @@
  *   ResidualBlock conv1 / conv2 / downsample, encoder conv2, output heads -> extractor.py:10-11,45,149,231,240,247 vppx_raft_conv_strided_dt_dev
  *   feature_extraction convbn / BasicBlock  psmnet/submodule.py:29-42,60-84 vppx_conv2d_dt_dev
  *   feature_extraction branches, cat    psmnet/submodule.py:149-171,208-250 vppx_psm_spp_pool_dt_dev, vppx_raft_gru_assemble_strided_dt_dev
+ *   dres0 / dres1 / hourglass conv2, conv4 / classif  psmnet/psmnet.py:24-36,93-128 vppx_conv3d_dt_dev
  *
  * Conventions
  *   - plain C, no torch types.  "_host" entry points take host pointers (what a ctypes /
@@ -1070,6 +1071,42 @@ int vppx_conv2d_dt_dev(const void *x0, int64_t x0_frame_stride, int C0, const vo
                        const void *packed, int Cout, int ksize, int stride, int dilation, int B, int H, int W,
                        const void *res, int64_t res_frame_stride, int relu, float scale,
                        void *out, int64_t out_frame_stride, int dtype, vppx_ctx *ctx);
+/* ---- PSMNet's stride-1 3-D convolutions (models/psmnet/psmnet.py:24-36, 93-128) on the convolution kernel --------------------
+ * vppx_conv3d_dt_dev is nn.Conv3d(Cin, Cout, 3, stride=1, padding=1) with the epilogue of vppx_conv2d_dt_dev:
+ *     x [B,Cin,D,H,W], frames x_frame_stride cells apart (at least Cin*D*H*W), every frame contiguous;  out [B,Cout,D,H,W]
+ *     acc[b][m][d][y][x] = sum over c < Cin, dz < 3, dy < 3, dx < 3 of w[m][c][dz][dy][dx] * x[b][c][d + dz - 1][y + dy - 1][x + dx - 1]
+ * with +0 outside the volume, in depth as in the map: plane -1 and plane D of a frame are +0, never a plane of frame b - 1 or
+ * b + 1.  The sum runs on the 3x3 kernel over 3*Cin pseudo-channels (channel dz*Cin + c is plane d + dz - 1 of channel c):
+ * K = 27*Cin float32 accumulations from +0 in an order the library chooses, padded as above by rows whose activation and weight
+ * are both +0; the two dtypes, the exact bfloat16 products and the float32 accumulation are those of the 3x3 call.
+ * The epilogue, every step one correctly rounded float32 operation:
+ *     v = acc + bias[m];   res: v = v + res[b][m][d][y][x] (a bfloat16 cell widened);   relu: v = v < 0 ? 0 : v (a NaN stays NaN);
+ *     out[b][m][d][y][x] = v * scale          (scale == 1.0f changes no bit; a bfloat16 result is the float32 one rounded once)
+ * res is NULL or [B,Cout,D,H,W] with a frame stride of its own; out may be res itself (the same pointer and frame stride): each
+ * cell is read by the lane that writes it.  out and res must not overlap x.  Channel m is stored only where m < Cout: out may
+ * be channels [0, Cout) of a wider tensor.  The 16-byte and the cell-by-cell route are decided as for the 3x3 call (pointers and
+ * frame strides of res and out, and W) and give the same bits.  Stream-ordered, never synchronises, allocates nothing.
+ * Packing.  vppx_conv3d_pack_dev writes vppx_conv3d_packed_bytes(Cout, Cin, dtype) bytes from weight [Cout][Cin][3][3][3]
+ * float32 (torch's layout, contiguous, device) and bias [Cout] or NULL: exactly the bytes vppx_raft_conv_pack_dev writes for
+ * the [Cout][3*Cin][3][3] weight w2[m][dz*Cin + c][dy][dx] = w[m][c][dz][dy][dx].  The size is 0, and the pack refuses, for
+ * Cin not a positive multiple of 16, 3*Cin above VPPX_CONV_MAX_CIN, Cout outside 1 .. VPPX_CONV_MAX_COUT, a dtype other than
+ * the two.  One buffer serves any B, D, H, W.
+ * NaN rule: a NaN (or infinite) input cell (b, c, z, r, q) reaches exactly the up to 27 output cells (z + i, r + j, q + k), i, j,
+ * k in -1 .. 1, that lie inside the volume, in every output channel of batch frame b, and nothing else: in particular nothing
+ * in frame b - 1 or b + 1.  A NaN in res stays in its cell.
+ * Every batch frame's result has the bits of the B = 1 call on that frame.
+ * Refused before anything is launched, with no output byte touched, in this order where several apply: a NULL out or a scale
+ * that is not finite; a NULL x or packed; B, D, H or W <= 0; a dtype other than the two (VPPX_E_INVALID_ARG); H*W or D*H*W
+ * above 2^31 - 1 (VPPX_E_UNSUPPORTED); Cin or Cout <= 0 (VPPX_E_INVALID_ARG); Cin not a multiple of 16, 3*Cin above
+ * VPPX_CONV_MAX_CIN, Cout above VPPX_CONV_MAX_COUT (VPPX_E_UNSUPPORTED); a packed pointer that is not 16-byte aligned; an
+ * x_frame_stride below Cin*D*H*W (VPPX_E_INVALID_ARG); B*D*H*W above 2^31 - 1 (VPPX_E_UNSUPPORTED); a res_frame_stride, then an
+ * out_frame_stride, below Cout*D*H*W (VPPX_E_INVALID_ARG); more tiles than one launch takes (VPPX_E_UNSUPPORTED).
+ * Out of scope: Conv3d at stride 2 and ConvTranspose3d (the hourglasses' conv1, conv3, conv5, conv6) stay in torch. */
+size_t vppx_conv3d_packed_bytes(int Cout, int Cin, int dtype);
+int vppx_conv3d_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed, vppx_ctx *ctx);
+int vppx_conv3d_dt_dev(const void *x, int64_t x_frame_stride, int Cin, const void *packed, int Cout, int B, int D, int H, int W,
+                       const void *res, int64_t res_frame_stride, int relu, float scale, void *out, int64_t out_frame_stride,
+                       int dtype, vppx_ctx *ctx);
 /* The pyramid pooling's average pools (submodule.py:149-171): every level in one launch, x [B,C,H,W] read once.
  *     level i:  nn.AvgPool2d((k, k), stride=(k, k)), k = ks[i];   outs[i] is [B,C,H/k,W/k] (integer division), contiguous
  *     out[y][x] = (the float32 sum of the k*k cells x[k*y .. k*y+k-1][k*x .. k*x+k-1]) / (float)(k*k), one correctly rounded division

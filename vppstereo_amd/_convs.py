@@ -1,6 +1,6 @@
-"""What FusedUpdate (update.py), FusedEncoder (extractor.py) and FusedFeatureExtraction (psmnet.py) share around
-`Engine.raft_conv` / `Engine.conv2d`: the decision whether the kernel takes a convolution, the fold of a frozen BatchNorm into
-a convolution's weights, and the one cache of packed weights.
+"""What FusedUpdate (update.py), FusedEncoder (extractor.py), FusedFeatureExtraction and FusedRegularization (psmnet.py) share around
+`Engine.raft_conv` / `Engine.conv2d` / `Engine.conv3d`: the decision whether the kernel takes a convolution, the fold of a frozen
+BatchNorm into a convolution's weights, and the one cache of packed weights.
 """
 import weakref
 
@@ -52,6 +52,46 @@ def fold_bn(conv, bn):
     return w.to(torch.float32).contiguous(), b.to(torch.float32).contiguous()
 
 
+def conv3d_plain(conv, cin):
+    """Whether Engine.conv3d takes this module on `cin` input channels: an nn.Conv3d whose forward is nn.Conv3d's, kernel
+    (3, 3, 3), stride 1, padding 1, dilation 1, groups 1, zeros outside the volume, `cin` a multiple of 16 with 3 * cin within the
+    input channels that are built, and an output channel count that is built.  A stride of 2 and a ConvTranspose3d are not."""
+    from . import _lib
+    if not isinstance(conv, torch.nn.Conv3d) or type(conv).forward is not torch.nn.Conv3d.forward:
+        return False
+    return (tuple(conv.kernel_size) == (3, 3, 3) and tuple(conv.weight.shape) == (conv.out_channels, cin, 3, 3, 3)
+            and tuple(conv.stride) == (1, 1, 1) and conv.padding == (1, 1, 1) and tuple(conv.dilation) == (1, 1, 1) and conv.groups == 1
+            and conv.padding_mode == "zeros" and cin % 16 == 0 and 0 < 3 * cin <= _lib.CONV_MAX_CIN
+            and 0 < conv.out_channels <= _lib.CONV_MAX_COUT)
+
+
+def frozen_bn3d(bn, what):
+    """frozen_bn for a BatchNorm3d: the TypeError of a wrapper for anything but a BatchNorm3d in eval mode with running statistics."""
+    if not isinstance(bn, torch.nn.BatchNorm3d):
+        raise TypeError(f"{what} is {type(bn).__name__}, not a BatchNorm3d")
+    if bn.training:
+        raise TypeError(f"{what} is in training mode; only a frozen BatchNorm3d (model.eval()) folds into its convolution")
+    if bn.running_mean is None or bn.running_var is None:
+        raise TypeError(f"{what} keeps no running statistics (track_running_stats=False): there is nothing to fold")
+
+
+def fold_bn3d(conv, bn):
+    """fold_bn for a Conv3d and a BatchNorm3d in eval mode: (weight [Cout,Cin,3,3,3], bias [Cout]) float32 of the convolution that
+    equals bn(conv(x)), computed in float64 and rounded to float32 once each:
+        s = gamma / sqrt(running_var + eps);   w' = w * s[m];   b' = beta + (conv_bias - running_mean) * s"""
+    frozen_bn3d(bn, "the norm")
+    f64 = lambda t: t.detach().double()                                                  # noqa: E731
+    s = 1.0 / torch.sqrt(f64(bn.running_var) + float(bn.eps))
+    if bn.weight is not None:
+        s = f64(bn.weight) * s
+    shift = -f64(bn.running_mean) if conv.bias is None else f64(conv.bias) - f64(bn.running_mean)
+    b = shift * s
+    if bn.bias is not None:
+        b = f64(bn.bias) + b
+    w = f64(conv.weight) * s[:, None, None, None, None]
+    return w.to(torch.float32).contiguous(), b.to(torch.float32).contiguous()
+
+
 class PackedWeights:
     """The packed weights of the modules a wrapper runs on the convolution kernel, kept per module: GruGlue's GRUs and both
     wrappers' single convolutions."""
@@ -74,6 +114,19 @@ class PackedWeights:
         if bn.training:
             raise RuntimeError("a BatchNorm2d went back to training mode; the wrapper is inference only")
         make = lambda: (eng.raft_conv_pack(*fold_bn(conv, bn), dtype=dtype), None)          # noqa: E731
+        params = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return self._packed_for(conv, params, make, (dtype, float(bn.eps), id(bn)), device)[0]
+
+    def _packed_conv3d(self, eng, conv, dtype, device):
+        """_packed_conv for a Conv3d that conv3d_plain accepts (Engine.conv3d_pack)."""
+        make = lambda: (eng.conv3d_pack(conv.weight, conv.bias, dtype=dtype), None)         # noqa: E731
+        return self._packed_for(conv, [conv.weight, conv.bias], make, dtype, device)[0]
+
+    def _packed_conv3d_bn(self, eng, conv, bn, dtype, device):
+        """_packed_conv_bn for a Conv3d with the frozen BatchNorm3d `bn` behind it (fold_bn3d), under the same cache rule."""
+        if bn.training:
+            raise RuntimeError("a BatchNorm3d went back to training mode; the wrapper is inference only")
+        make = lambda: (eng.conv3d_pack(*fold_bn3d(conv, bn), dtype=dtype), None)           # noqa: E731
         params = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
         return self._packed_for(conv, params, make, (dtype, float(bn.eps), id(bn)), device)[0]
 

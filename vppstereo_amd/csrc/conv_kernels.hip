@@ -46,6 +46,15 @@
 // beyond the first 256 are 2816 = 11 * 256 units, unit e = 256 j + tid being unit e / 176 of pixel 256 + e % 176 (neighbouring
 // threads read neighbouring pixels of one channel): 27 units per thread, every thread the same, read one chunk ahead.
 //
+// Volume (VOL: nine taps, stride 1, dilation 1, plain epilogue only; PSMNet's stride-1 Conv3d(k=3, padding=1)).  A 3x3x3
+// convolution of x [B,C,D,H,W] is, for output plane (b, d), the 3x3 convolution over 3 C pseudo-channels: pseudo-channel
+// q = dz * C + c is plane d + dz - 1 of channel c, +0 (no load) where that plane is outside 0 .. D-1, and its weights are
+// w2[m][q][dy][dx] = w[m][c][dz][dy][dx], which is what the packing writes.  A frame of the launch is a plane: frame index
+// t -> (b = t / D, d = t % D).  Only `unit` (the source address: channels D*H*W apart, the plane's offset on top) and the
+// epilogue's addresses (m * D*H*W + d * H*W) know; tile, LDS image, tap loop and both store routes are those of stride 1.  With
+// C % 16 == 0 a float32 chunk lies in one plane and the two channels of a bfloat16 unit do; a bfloat16 chunk may hold the last 16
+// channels of one plane and the first 16 of the next (C = 16, 48): `unit` decides per unit.
+//
 // A residual (plain epilogue): v = acc + bias, then v + res[b][m][y][x] before the ReLU and the scale, res being read by the lane
 // that writes the cell, so that out may be res itself.
 #include "cells.h"
@@ -83,6 +92,7 @@ struct ConvArgs {
     float scale;             // plain: out = relu(v) * scale
     int Hi, Wi;              // STRIDE == 2: the input's size
     int res;                 // plain: v += e0[b][m][y][x] in front of the ReLU
+    int D;                   // VOL: planes of a frame; C0 is then the volume's channels and Cin = 3 * C0 the pseudo-channels
 };
 
 // Eight cells of a [B,C,H,W] tensor from cell `at` on, the first `nv` of them inside the row.  vec: every base, stride, plane
@@ -126,13 +136,14 @@ __device__ __forceinline__ void cv_store8(void *p, size_t at, int nv, bool vec, 
 // TAPS = 9: the 3x3 convolution.  TAPS = 1: a 1x1 convolution as the centre tap of the same staged image; its halo slots are
 // written as +0 without a read, so that nothing but the tile's own pixels is fetched.
 // STRIDE = 2: see the head of the file.  S2 marks the 3x3 at stride 2, the one instance with a tile and a staged image of its own.
-// DIL = 2: see the head of the file.
-template <bool BF16, int EPI, int TAPS, int STRIDE = 1, int DIL = 1>
+// DIL = 2, VOL: see the head of the file.
+template <bool BF16, int EPI, int TAPS, int STRIDE = 1, int DIL = 1, bool VOL = false>
 __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 {
     static_assert(TAPS == 9 || TAPS == 1, "3x3 or 1x1");
     static_assert(STRIDE == 1 || (STRIDE == 2 && EPI == CV_PLAIN), "stride 2 goes with the plain epilogue");
     static_assert(DIL == 1 || (DIL == 2 && TAPS == 9 && STRIDE == 1 && EPI == CV_PLAIN), "dilation 2 goes with nine taps, stride 1 and the plain epilogue");
+    static_assert(!VOL || (TAPS == 9 && STRIDE == 1 && DIL == 1 && EPI == CV_PLAIN), "a volume goes with nine taps, stride 1, dilation 1 and the plain epilogue");
     constexpr int CK = BF16 ? 32 : 16;
     constexpr bool S2 = STRIDE == 2 && TAPS == 9, D2 = DIL == 2;
     constexpr int TH = S2 ? CV_TH2 : CV_TH, RPW = TH / 4, MT = 2 * RPW; // rows and M tiles of a wave
@@ -148,10 +159,13 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     const int tx = (int)(t % (unsigned)a.tilesX);
     t /= (unsigned)a.tilesX;
     const int ty = (int)(t % (unsigned)a.tilesY);
-    const size_t b = t / (unsigned)a.tilesY;
+    const size_t fr = t / (unsigned)a.tilesY;                          // the frame of the launch; VOL: plane d of batch frame b
+    const int d = VOL ? (int)(fr % (unsigned)a.D) : 0;
+    const size_t b = VOL ? fr / (unsigned)a.D : fr;
     const int x0 = tx * CV_TW, y0 = ty * TH, H = a.H, W = a.W;
     const int Hi = STRIDE == 1 ? H : a.Hi, Wi = STRIDE == 1 ? W : a.Wi;
     const size_t plane = (size_t)H * W, planeIn = STRIDE == 1 ? plane : (size_t)Hi * Wi;
+    const size_t chan = VOL ? plane * (size_t)a.D : plane;             // cells between the channels of an epilogue tensor
     const int nb = blockIdx.y, ntl = min(4, a.NT - 4 * nb);
 
     // The staging.  A pixel's row of a chunk is 16 units of 4 bytes: one float32 channel, or two bfloat16 channels (an even
@@ -186,6 +200,16 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     auto unit = [&](int chunk, int u, int off) -> u32 {
         const int c = chunk * CK + (BF16 ? 2 * u : u);
         if (off < 0 || c >= a.Cin) return 0u; // +0 outside the map and for the channels that pad K
+        if (VOL) { // pseudo-channel c = dz * C0 + cc: plane d + dz - 1 of channel cc, +0 outside the volume and never of another frame
+            const int dz = (c >= a.C0) + (c >= 2 * a.C0), z = d + dz - 1;
+            if (z < 0 || z >= a.D) return 0u;
+            const size_t at = b * (size_t)a.s0 + (size_t)(c - dz * a.C0) * chan + (size_t)z * plane + (size_t)off;
+            if (BF16) {
+                const u16 *p = (const u16 *)a.x0 + at;
+                return (u32)p[0] | ((u32)p[chan] << 16);
+            }
+            return ((const u32 *)a.x0)[at];
+        }
         const bool first = c < a.C0;
         const size_t at = (first ? b * (size_t)a.s0 + (size_t)c * planeIn : b * (size_t)a.s1 + (size_t)(c - a.C0) * planeIn) + (size_t)off;
         const void *src = first ? a.x0 : a.x1;
@@ -297,7 +321,7 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
     for (int p = 0; p < RPW; p++) {
         const int y = y0 + RPW * wave + p;
         if (y >= H) break;
-        const size_t pix = (size_t)y * W + x;
+        const size_t pix = (VOL ? (size_t)d * plane : 0) + (size_t)y * W + x;
 #pragma unroll
         for (int n = 0; n < 4; n++) {
             if (n >= ntl) break;
@@ -310,37 +334,37 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
             if (EPI == CV_PLAIN) {
                 if (a.res) { // uniform over the launch; out may be the residual: read before the store
                     float r[8];
-                    cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * plane + pix, nv, vec, r);
+                    cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * chan + pix, nv, vec, r);
 #pragma unroll
                     for (int j = 0; j < 8; j++) v[j] = __fadd_rn(v[j], r[j]);
                 }
 #pragma unroll
                 for (int j = 0; j < 8; j++) o[j] = __fmul_rn(a.relu ? relu_nan(v[j]) : v[j], a.scale);
-                cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
+                cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * chan + pix, nv, vec, o);
             } else if (EPI == CV_ZR) {
                 float c[8];
                 if (m < a.C) { // uniform over the N tile: C is a multiple of 16
-                    cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * plane + pix, nv, vec, c);
+                    cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * chan + pix, nv, vec, c);
 #pragma unroll
                     for (int j = 0; j < 8; j++) o[j] = gru_sigmoid(__fadd_rn(v[j], c[j]));
-                    cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
+                    cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * chan + pix, nv, vec, o);
                 } else {
                     const size_t mm = (size_t)(m - a.C);
                     float hh[8];
-                    cv_load8<BF16>(a.e1, b * (size_t)a.se1 + mm * plane + pix, nv, vec, c);
-                    cv_load8<BF16>(a.e2, b * (size_t)a.se2 + mm * plane + pix, nv, vec, hh);
+                    cv_load8<BF16>(a.e1, b * (size_t)a.se1 + mm * chan + pix, nv, vec, c);
+                    cv_load8<BF16>(a.e2, b * (size_t)a.se2 + mm * chan + pix, nv, vec, hh);
 #pragma unroll
                     for (int j = 0; j < 8; j++) o[j] = __fmul_rn(gru_sigmoid(__fadd_rn(v[j], c[j])), hh[j]);
-                    cv_store8<BF16>(a.o1, b * (size_t)a.so1 + mm * plane + pix, nv, vec, o);
+                    cv_store8<BF16>(a.o1, b * (size_t)a.so1 + mm * chan + pix, nv, vec, o);
                 }
             } else {
                 float c[8], z[8], hh[8];
-                cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * plane + pix, nv, vec, c);
-                cv_load8<BF16>(a.e1, b * (size_t)a.se1 + (size_t)m * plane + pix, nv, vec, z);
-                cv_load8<BF16>(a.e2, b * (size_t)a.se2 + (size_t)m * plane + pix, nv, vec, hh); // out may be h: read before the store
+                cv_load8<BF16>(a.e0, b * (size_t)a.se0 + (size_t)m * chan + pix, nv, vec, c);
+                cv_load8<BF16>(a.e1, b * (size_t)a.se1 + (size_t)m * chan + pix, nv, vec, z);
+                cv_load8<BF16>(a.e2, b * (size_t)a.se2 + (size_t)m * chan + pix, nv, vec, hh); // out may be h: read before the store
 #pragma unroll
                 for (int j = 0; j < 8; j++) o[j] = gru_mix(z[j], gru_tanh(__fadd_rn(v[j], c[j])), hh[j]);
-                cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * plane + pix, nv, vec, o);
+                cv_store8<BF16>(a.o0, b * (size_t)a.so0 + (size_t)m * chan + pix, nv, vec, o);
             }
         }
     }
@@ -353,7 +377,8 @@ __global__ void __launch_bounds__(256, 2) raft_conv3x3_kernel(ConvArgs a)
 // fragment f = ((chunk * taps + tap) * NT + N tile) * 64 + lane holds, for lane = 16 g + i, output channel 16 * tile + i and
 //   bfloat16: element j = input channel 32 * chunk + 8 g + j          (the 16x16x32 B map: k = 8 (lane >> 4) + j)
 //   float32:  element j = input channel 16 * chunk + 4 g + j          (k-step j of the chunk, 16x16x4 B map: k = lane >> 4)
-template <bool BF16>
+// VOL: w is [Cout][Cin / 3][3][3][3] and channel c of the packed layout is pseudo-channel dz * (Cin / 3) + cc (the head of the file).
+template <bool BF16, bool VOL = false>
 __global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, const float *bias, int Cout, int Cin, int nchunks, int taps, void *packed)
 {
     constexpr int E = BF16 ? 8 : 4, CK = BF16 ? 32 : 16;
@@ -372,7 +397,12 @@ __global__ void __launch_bounds__(256) raft_conv3x3_pack_kernel(const float *w, 
 #pragma unroll
     for (int j = 0; j < E; j++) {
         const int c = CK * chunk + E * g + j;
-        v[j] = c < Cin && m < Cout ? w[((size_t)m * Cin + c) * taps + tap] : 0.0f;
+        if (VOL) {
+            const int C3 = Cin / 3, dz = c / C3, cc = c - dz * C3;
+            v[j] = c < Cin && m < Cout ? w[(((size_t)m * C3 + cc) * 3 + dz) * taps + tap] : 0.0f;
+        } else {
+            v[j] = c < Cin && m < Cout ? w[((size_t)m * Cin + c) * taps + tap] : 0.0f;
+        }
     }
     if (BF16) {
         u32 h[8];
@@ -402,12 +432,18 @@ size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype)
     return conv_weight_bytes(Cout, Cin, ksize, dtype) + (size_t)conv_ntiles(Cout) * 16 * sizeof(float);
 }
 
-int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed)
+// vol: weight is [Cout][Cin][3][3][3], packed as the [Cout][3 Cin][3][3] weight of the pseudo-channels
+int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed, bool vol)
 {
+    if (vol) Cin *= 3;
     const int nchunks = conv_chunks(Cin, dtype), taps = ksize * ksize;
     const size_t nfrag = (size_t)nchunks * taps * conv_ntiles(Cout) * 64;
     const unsigned blocks = (unsigned)((nfrag + 255) / 256);
-    if (dtype == VPPX_DT_BF16)
+    if (vol && dtype == VPPX_DT_BF16)
+        raft_conv3x3_pack_kernel<true, true><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, taps, packed);
+    else if (vol)
+        raft_conv3x3_pack_kernel<false, true><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, taps, packed);
+    else if (dtype == VPPX_DT_BF16)
         raft_conv3x3_pack_kernel<true><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, taps, packed);
     else
         raft_conv3x3_pack_kernel<false><<<dim3(blocks), 256, 0, ctx->stream>>>(weight, bias, Cout, Cin, nchunks, taps, packed);
@@ -416,11 +452,13 @@ int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, i
 }
 
 // one launch per (epilogue, taps, stride, dilation) that is built: ksize 1, stride 2, dilation 2 and a Cout that is no multiple
-// of 16 go with the plain epilogue only, dilation 2 with stride 1; a 1x1 at dilation 2 is the 1x1 itself (vppx_net_api.hip sees to it)
+// of 16 go with the plain epilogue only, dilation 2 with stride 1; a 1x1 at dilation 2 is the 1x1 itself (vppx_net_api.hip sees to it);
+// a volume is 3x3x3 at stride 1, dilation 1
 template <bool BF16>
 static void conv_launch(vppx_ctx *ctx, const ConvCall &c, const ConvArgs &a, dim3 grid)
 {
-    if (c.epi == CV_PLAIN && c.stride == 2 && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1, 2><<<grid, 256, 0, ctx->stream>>>(a);
+    if (c.vol) raft_conv3x3_kernel<BF16, CV_PLAIN, 9, 1, 1, true><<<grid, 256, 0, ctx->stream>>>(a);
+    else if (c.epi == CV_PLAIN && c.stride == 2 && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1, 2><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_PLAIN && c.stride == 2) raft_conv3x3_kernel<BF16, CV_PLAIN, 9, 2><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_PLAIN && c.ksize == 3 && c.dilation == 2) raft_conv3x3_kernel<BF16, CV_PLAIN, 9, 1, 2><<<grid, 256, 0, ctx->stream>>>(a);
     else if (c.epi == CV_PLAIN && c.ksize == 1) raft_conv3x3_kernel<BF16, CV_PLAIN, 1><<<grid, 256, 0, ctx->stream>>>(a);
@@ -434,7 +472,7 @@ int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c)
     const bool bf16 = c.dtype == VPPX_DT_BF16;
     ConvArgs a = {};
     a.x0 = c.x0, a.x1 = c.C1 ? c.x1 : c.x0, a.s0 = (long long)c.s0, a.s1 = c.C1 ? (long long)c.s1 : 0;
-    a.C0 = c.C0, a.Cin = c.C0 + c.C1, a.NT = conv_ntiles(c.Cout), a.nchunks = conv_chunks(a.Cin, c.dtype);
+    a.C0 = c.C0, a.Cin = c.vol ? 3 * c.C0 : c.C0 + c.C1, a.D = c.vol ? c.D : 1, a.NT = conv_ntiles(c.Cout), a.nchunks = conv_chunks(a.Cin, c.dtype);
     a.Cout = c.Cout, a.scale = c.scale;
     a.packed = (const uint4 *)c.packed;
     a.bias = (const float *)((const unsigned char *)c.packed + conv_weight_bytes(c.Cout, a.Cin, c.ksize, c.dtype));
@@ -444,9 +482,9 @@ int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c)
     const int Ho = (c.H - 1) / c.stride + 1, Wo = (c.W - 1) / c.stride + 1, th = c.stride == 2 && c.ksize == 3 ? CV_TH2 : CV_TH;
     a.H = Ho, a.W = Wo, a.Hi = c.H, a.Wi = c.W, a.tilesX = (Wo + CV_TW - 1) / CV_TW, a.tilesY = (Ho + th - 1) / th;
     a.C = c.C, a.relu = c.relu, a.res = c.epi == CV_PLAIN && c.in[0].p != NULL;
-    const size_t tiles = (size_t)c.B * a.tilesX * a.tilesY;
+    const size_t tiles = (size_t)c.B * a.D * a.tilesX * a.tilesY;
     if (tiles > 0x7FFFFFFFull) {
-        vppx_set_error("%s: %d frames of %dx%d are %zu workgroups, more than one launch takes", who, c.B, Ho, Wo, tiles);
+        vppx_set_error("%s: %lld frames of %dx%d are %zu workgroups, more than one launch takes", who, (long long)c.B * a.D, Ho, Wo, tiles);
         return VPPX_E_UNSUPPORTED;
     }
     const int64_t V = bf16 ? 8 : 4;

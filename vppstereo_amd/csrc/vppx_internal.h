@@ -611,10 +611,12 @@ struct ConvCall {
     int B = 0, C = 0, H = 0, W = 0;    // C: the hidden size of the gates.  H, W: the input's; the output is (H - 1) / stride + 1 high
     int relu = 0;                      // plain: out = relu(v [+ res]) * scale
     float scale = 1.0f;
+    bool vol = false;                  // a volume: x0 is [B,C0,D,H,W], the kernel 3x3x3 at stride 1, packed conv_pack(vol)'s for (Cout, C0);
+    int D = 1;                         //   the residual and out are [B,Cout,D,H,W].  Plain epilogue, C1 == 0
 };
 
 size_t conv_packed_bytes(int Cout, int Cin, int ksize, int dtype);
-int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed);
+int conv_pack(vppx_ctx *ctx, const float *weight, const float *bias, int Cout, int Cin, int ksize, int dtype, void *packed, bool vol = false);
 int conv_run(vppx_ctx *ctx, const char *who, const ConvCall &c); // every field has been checked by vppx_net_api.hip
 
 // spp_kernels.hip: PSMNet's pyramid pooling (models/psmnet/submodule.py:149-171), every level in one launch

@@ -528,8 +528,54 @@ extern "C" int vppx_raft_conv_pack_dev(const float *weight, const float *bias, i
     return conv_pack_call("vppx_raft_conv_pack", CONV_OUT_ANY, weight, bias, Cout, Cin, ksize, dtype, packed, ctx);
 }
 
+// The stride-1 3x3x3 convolution (vppx_conv3d_*): Cin volume channels are 3 Cin pseudo-channels of the 3x3 kernel.
+static int conv3d_channels_ok(const char *who, int Cin, int Cout)
+{
+    if (Cin <= 0 || Cout <= 0) {
+        if (who) vppx_set_error("%s: %d input and %d output channels: Cin and Cout must be positive", who, Cin, Cout);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (Cin % 16 || 3 * (int64_t)Cin > VPPX_CONV_MAX_CIN || Cout > VPPX_CONV_MAX_COUT) {
+        if (who)
+            vppx_set_error("%s: %d input and %d output channels: multiples of 16 up to %d in (3 x Cin up to %d) and 1 to %d out are built", who,
+                           Cin, Cout, VPPX_CONV_MAX_CIN / 3 / 16 * 16, VPPX_CONV_MAX_CIN, VPPX_CONV_MAX_COUT);
+        return VPPX_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+extern "C" size_t vppx_conv3d_packed_bytes(int Cout, int Cin, int dtype)
+{
+    return !conv3d_channels_ok(NULL, Cin, Cout) && (dtype == VPPX_DT_F32 || dtype == VPPX_DT_BF16) ? conv_packed_bytes(Cout, 3 * Cin, 3, dtype) : 0;
+}
+
+extern "C" int vppx_conv3d_pack_dev(const float *weight, const float *bias, int Cout, int Cin, int dtype, void *packed, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_conv3d_pack";
+    int rc;
+    VPPX_ENTER(ctx);
+    if (!weight || !packed) {
+        vppx_set_error("%s: bad arguments", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if (!handoff_dtype_ok(who, dtype)) return VPPX_E_INVALID_ARG;
+    if ((rc = conv3d_channels_ok(who, Cin, Cout)) || (rc = conv_packed_aligned(who, packed))) return rc;
+    return conv_pack(ctx, weight, bias, Cout, Cin, 3, dtype, packed, true);
+}
+
+// a volume's frame stride holds the frame; C * D * H * W is within int64 (C <= 512, D * H * W < 2^31)
+static int vol_stride_ok(const char *who, const char *what, int64_t stride, int C, int D, int H, int W)
+{
+    if (stride < (int64_t)C * D * H * W) {
+        vppx_set_error("%s: %s_frame_stride %lld is less than %d volumes of %dx%dx%d", who, what, (long long)stride, C, D, H, W);
+        return VPPX_E_INVALID_ARG;
+    }
+    return 0;
+}
+
 // Everything the launch entry points share, in the order they have always refused in.  The tensors of the epilogue are those the
 // call names: each is there and its frame stride holds a frame of the output (the gates': C channels, the plain call's: Cout).
+// A volume (c.vol) is refused in the same places: its depth with B, H and W, its size behind theirs, its channels by its own rule.
 static int conv_call_ok(const char *who, const ConvCall &c, ConvRule rule)
 {
     int rc;
@@ -561,19 +607,34 @@ static int conv_call_ok(const char *who, const ConvCall &c, ConvRule rule)
         vppx_set_error("%s: bad arguments", who);
         return VPPX_E_INVALID_ARG;
     }
-    if ((rc = gru_shape_ok(who, c.B, 1, c.H, c.W, c.dtype)) || (rc = conv_channels_ok(who, rule, c.C0, c.C1, c.Cout)) ||
+    if (c.vol && c.D <= 0) {
+        vppx_set_error("%s: bad arguments (B, D, H and W must be positive)", who);
+        return VPPX_E_INVALID_ARG;
+    }
+    if ((rc = gru_shape_ok(who, c.B, 1, c.H, c.W, c.dtype))) return rc;
+    if (c.vol && (int64_t)c.D * c.H * c.W > 0x7FFFFFFF) { // H * W <= 2^31 - 1 by now: the product is within int64
+        vppx_set_error("%s: a %dx%dx%d volume is more than the call takes", who, c.D, c.H, c.W);
+        return VPPX_E_UNSUPPORTED;
+    }
+    if ((rc = c.vol ? conv3d_channels_ok(who, c.C0, c.Cout) : conv_channels_ok(who, rule, c.C0, c.C1, c.Cout)) ||
         (rc = conv_packed_aligned(who, c.packed)))
         return rc;
-    if ((rc = gru_stride_ok(who, "x0", c.s0, c.C0, c.H, c.W)) || (c.C1 > 0 && (rc = gru_stride_ok(who, "x1", c.s1, c.C1, c.H, c.W)))) return rc;
-    if ((int64_t)c.B * c.H * c.W > 0x7FFFFFFF) {
-        vppx_set_error("%s: B*H*W = %lld pixels are more than one launch takes", who, (long long)c.B * c.H * c.W);
+    // a frame stride against its tensor of C channels, each an h x w map or, for a volume, D of them
+    auto stride_ok = [&](const char *what, int64_t stride, int C, int h, int w) {
+        return c.vol ? vol_stride_ok(who, what, stride, C, c.D, h, w) : gru_stride_ok(who, what, stride, C, h, w);
+    };
+    if ((rc = stride_ok(c.vol ? "x" : "x0", c.s0, c.C0, c.H, c.W)) || (c.C1 > 0 && (rc = stride_ok("x1", c.s1, c.C1, c.H, c.W)))) return rc;
+    const int64_t cells = (int64_t)c.B * ((int64_t)(c.vol ? c.D : 1) * c.H * c.W); // B and D * H * W <= 2^31 - 1 each: within int64
+    if (cells > 0x7FFFFFFF) {
+        if (c.vol) vppx_set_error("%s: B*D*H*W = %lld cells are more than one launch takes", who, (long long)cells);
+        else vppx_set_error("%s: B*H*W = %lld pixels are more than one launch takes", who, (long long)c.B * c.H * c.W);
         return VPPX_E_UNSUPPORTED;
     }
     const int Ce = c.epi == CV_PLAIN ? c.Cout : c.C, Ho = (c.H - 1) / c.stride + 1, Wo = (c.W - 1) / c.stride + 1;
     for (const ConvTensor &t : c.in)
-        if (t.name && (rc = gru_stride_ok(who, t.name, t.stride, Ce, Ho, Wo))) return rc;
+        if (t.name && (rc = stride_ok(t.name, t.stride, Ce, Ho, Wo))) return rc;
     for (const ConvTensor &t : c.out)
-        if (t.name && (rc = gru_stride_ok(who, t.name, t.stride, Ce, Ho, Wo))) return rc;
+        if (t.name && (rc = stride_ok(t.name, t.stride, Ce, Ho, Wo))) return rc;
     return conv_ksize_ok(who, c.ksize);
 }
 
@@ -630,6 +691,25 @@ extern "C" int vppx_conv2d_dt_dev(const void *x0, int64_t x0_frame_stride, int C
 {
     return conv_plain_call("vppx_conv2d", CONV_OUT_ANY, x0, x0_frame_stride, C0, x1, x1_frame_stride, C1, packed, Cout, ksize, stride, B, H, W,
                            relu, scale, out, out_frame_stride, dtype, ctx, dilation, res, res_frame_stride);
+}
+
+// nn.Conv3d(Cin, Cout, 3, stride=1, padding=1) with a residual in front of the ReLU: PSMNet's dres0, dres1, the hourglasses' conv2 and
+// conv4 and the classif heads (models/psmnet/psmnet.py:24-36, 93-128) with their BatchNorm3d folded.  x [B,Cin,D,H,W]; res, out [B,Cout,D,H,W].
+extern "C" int vppx_conv3d_dt_dev(const void *x, int64_t x_frame_stride, int Cin, const void *packed, int Cout, int B, int D, int H, int W,
+                                  const void *res, int64_t res_frame_stride, int relu, float scale, void *out, int64_t out_frame_stride,
+                                  int dtype, vppx_ctx *ctx)
+{
+    static const char *who = "vppx_conv3d";
+    int rc;
+    VPPX_ENTER(ctx);
+    ConvCall c;
+    c.vol = true, c.D = D, c.dtype = dtype, c.B = B, c.H = H, c.W = W;
+    c.x0 = x, c.s0 = x_frame_stride, c.C0 = Cin;
+    c.packed = packed, c.Cout = Cout, c.relu = relu != 0, c.scale = scale;
+    if (res) c.in[0] = {"res", res, res_frame_stride};
+    c.out[0] = {"out", out, out_frame_stride};
+    if ((rc = conv_call_ok(who, c, CONV_OUT_ANY))) return rc;
+    return conv_run(ctx, who, c);
 }
 
 // PSMNet's pyramid pooling (spp_kernels.hip; submodule.py:149-171 the four AvgPool2d).  ks and outs are host arrays.

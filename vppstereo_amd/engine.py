@@ -1047,6 +1047,84 @@ class Engine:
                                                _ptr(residual), sr, relu, float(scale), _ptr(out), so, dt, self.ctx.handle))
         return out
 
+    # ---- the stride-1 3x3x3 convolution: the same kernel over 3 Cin pseudo-channels (include/vppx.h) ----
+    def _conv3d_bytes(self, cout, cin, dt):
+        key = ("3d", cout, cin, 3, dt)
+        if key not in self._conv_sizes:
+            self._conv_sizes[key] = int(self.lib.vppx_conv3d_packed_bytes(cout, cin, dt))
+        return self._conv_sizes[key]
+
+    @staticmethod
+    def _conv3d_built():
+        return (f"multiples of 16 up to {_lib.CONV_MAX_CIN // 48 * 16} in (3 x Cin up to {_lib.CONV_MAX_CIN}) and 1 to {_lib.CONV_MAX_COUT} "
+                "out are built")
+
+    def conv3d_pack(self, weight, bias=None, dtype=None):
+        """The weights [Cout,Cin,3,3,3] (and bias [Cout]) of an nn.Conv3d(Cin, Cout, 3, stride=1, padding=1) in the layout the
+        convolution kernel reads, for activations stored as `dtype` (torch.float32, the default, or torch.bfloat16: the weights are
+        then rounded to bfloat16 once).  Cin is a multiple of 16 with 3 * Cin up to CONV_MAX_CIN, Cout any count from 1 to
+        CONV_MAX_COUT.  -> an opaque torch.uint8 device tensor, the bytes raft_conv_pack makes for the [Cout,3*Cin,3,3] weight
+        weight.permute(0, 2, 1, 3, 4).reshape(Cout, 3 * Cin, 3, 3); pack once per module, it serves any B, D, H, W."""
+        torch = self.torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"dtype is {dtype}; the kernels store float32 and bfloat16")
+        dt = _lib.DT_BF16 if dtype == torch.bfloat16 else _lib.DT_F32
+        if getattr(weight, "device", None) != self.device or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+            raise ValueError(f"weight: expected a [Cout,Cin,3,3,3] tensor on {self.device}")
+        Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+        weight = weight.detach().to(torch.float32).contiguous()
+        if bias is not None:
+            bias = bias.detach().to(torch.float32).contiguous()
+            self._chk(bias, torch.float32, 1, "bias", (Cout,))
+        size = self._conv3d_bytes(Cout, Cin, dt)
+        if size == 0:
+            raise ValueError(f"weight: {Cin} -> {Cout} channels: {self._conv3d_built()}")
+        packed = torch.empty((size,), dtype=torch.uint8, device=self.device)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_conv3d_pack_dev(_ptr(weight), _ptr(bias), Cout, Cin, dt, _ptr(packed), self.ctx.handle))
+        return packed
+
+    def _chk_volumes(self, t, dtype, name, shape=None):
+        """_chk_frames for a [B,C,D,H,W] tensor: every frame contiguous, the frames a frame stride apart -> that stride in cells."""
+        if getattr(t, "device", None) != self.device or t.dtype != dtype or t.dim() != 5:
+            raise ValueError(f"{name}: expected a {dtype} tensor with 5 dims on {self.device}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        B, Cc, D, H, W = t.shape
+        if min(B, Cc, D, H, W) < 1:
+            raise ValueError(f"{name}: empty tensor {tuple(t.shape)}")
+        want = (Cc * D * H * W, D * H * W, H * W, W, 1)
+        st = t.stride()
+        if any(t.shape[d] > 1 and st[d] != want[d] for d in (1, 2, 3, 4)) or (B > 1 and st[0] < want[0]):
+            raise ValueError(f"{name}: every frame must be contiguous (strides {tuple(st)} of shape {tuple(t.shape)})")
+        return int(st[0]) if B > 1 else want[0]
+
+    def conv3d(self, x, packed, cout, residual=None, relu=False, scale=1.0, out=None):
+        """nn.Conv3d(Cin, cout, 3, stride=1, padding=1) on x [B,Cin,D,H,W] (vppx_conv3d_dt_dev; PSMNet's stride-1 3-D convolutions
+        with their BatchNorm3d folded): + bias, + `residual` [B,cout,D,H,W] where there is one, with `relu` torch's ReLU, then
+        * scale.  `packed` is conv3d_pack's, for the dtype of x (float32 or bfloat16).  `out` may be `residual` itself; x, residual
+        and out may be channel slices of wider tensors.  -> [B,cout,D,H,W]; with `out` nothing is allocated."""
+        torch = self.torch
+        cout, relu = int(cout), int(bool(relu))
+        dtype, dt = self._norm_dtype(x, "x")
+        sx = self._chk_volumes(x, dtype, "x")
+        B, Cin, D, H, W = x.shape
+        if getattr(packed, "device", None) != self.device or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+            raise ValueError(f"packed: expected what conv3d_pack returns, a torch.uint8 vector on {self.device}")
+        want = self._conv3d_bytes(cout, Cin, dt)
+        if want == 0 or packed.numel() != want:
+            raise ValueError(f"packed: {packed.numel()} bytes; {Cin} -> {cout} channels of {dtype} take {want or 'no'} bytes ({self._conv3d_built()})")
+        shape = (B, cout, D, H, W)
+        sr = 0 if residual is None else self._chk_volumes(residual, dtype, "residual", shape)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        so = self._chk_volumes(out, dtype, "out", shape)
+        self._bind_stream()
+        _lib.check(self.lib.vppx_conv3d_dt_dev(_ptr(x), sx, Cin, _ptr(packed), cout, B, D, H, W, _ptr(residual), sr, relu, float(scale),
+                                               _ptr(out), so, dt, self.ctx.handle))
+        return out
+
     def psm_spp_pool(self, x, ks=(8, 16, 32, 64)):
         """The average pools of PSMNet's pyramid pooling in one launch (vppx_psm_spp_pool_dt_dev): x [B,C,H,W], float32 or
         bfloat16, possibly a channel slice of a wider tensor, read once -> [nn.AvgPool2d((k, k), stride=(k, k))(x) for k in ks],

@@ -1,4 +1,5 @@
-"""PSMNet's feature_extraction on the library's kernels (INTEGRATION.md has the patch).
+"""PSMNet's feature_extraction and 3-D regularization on the library's kernels (INTEGRATION.md has the patch): FusedFeatureExtraction,
+and FusedRegularization further down.
 
 `FusedFeatureExtraction(fe, dtype=None)` wraps a loaded `feature_extraction` (models/psmnet/submodule.py:131-253): any module
 with `firstconv`, `layer1` .. `layer4`, `branch1` .. `branch4` and `lastconv` of the reference's structure -- convbn groups
@@ -26,7 +27,7 @@ TypeError when wrapping.  The packed weights follow `PackedWeights`' cache rule 
 """
 import torch
 
-from ._convs import PackedWeights, conv_plain, frozen_bn
+from ._convs import PackedWeights, conv3d_plain, conv_plain, frozen_bn, frozen_bn3d
 from .corr import _engine
 from .update import _as
 
@@ -203,3 +204,182 @@ class FusedFeatureExtraction(torch.nn.Module, PackedWeights):
         small = [(self._convbn(eng, br[1], p, relu=True), "interp") for br, p in zip(branches, pooled)]
         eng.raft_gru_assemble(small, out=buf[:, c_raw + c_skip:])
         return buf
+
+
+# ---------------------------------------------------------------------------------------------------
+# the 3-D regularization: dres0 .. dres4 and classif1 .. classif3 (models/psmnet/psmnet.py:93-128, 199-213)
+# ---------------------------------------------------------------------------------------------------
+_WHO3 = "FusedRegularization"
+
+
+def _autocast_bf16():
+    """Whether torch would run a convolution on the device in bfloat16 here."""
+    if hasattr(torch, "get_autocast_dtype"):
+        return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    return torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.bfloat16
+
+
+def _check_convbn3d(pair, where, conv_type=torch.nn.Conv3d):
+    """A convbn_3d group: Sequential(Conv3d, BatchNorm3d in eval mode with running statistics); conv5 and conv6 of an hourglass
+    have a ConvTranspose3d in the convolution's place."""
+    name = conv_type.__name__
+    if not isinstance(pair, torch.nn.Sequential) or len(pair) != 2:
+        raise TypeError(f"{_WHO3}: {where} is not a Sequential({name}, BatchNorm3d)")
+    if not isinstance(pair[0], conv_type):
+        raise TypeError(f"{_WHO3}: {where}[0] is {type(pair[0]).__name__}, not a {name}")
+    frozen_bn3d(pair[1], f"{_WHO3}: {where}[1]")
+    if pair[1].num_features != pair[0].out_channels:
+        raise TypeError(f"{_WHO3}: {where}[1] normalises {pair[1].num_features} channels, {where}[0] makes {pair[0].out_channels}")
+
+
+def _check_seq3(m, kinds, where):
+    """A Sequential whose members are, in order, "convbn" groups, "relu"s and "conv"s (a Conv3d without a norm)."""
+    if not isinstance(m, torch.nn.Sequential) or len(m) != len(kinds):
+        raise TypeError(f"{_WHO3}: {where} is not a Sequential of {len(kinds)}")
+    for k, kind in enumerate(kinds):
+        if kind == "convbn":
+            _check_convbn3d(m[k], f"{where}[{k}]")
+        elif kind == "relu":
+            if not isinstance(m[k], torch.nn.ReLU):
+                raise TypeError(f"{_WHO3}: {where}[{k}] is {type(m[k]).__name__}, not a ReLU")
+        elif not isinstance(m[k], torch.nn.Conv3d):
+            raise TypeError(f"{_WHO3}: {where}[{k}] is {type(m[k]).__name__}, not a Conv3d")
+
+
+class FusedRegularization(torch.nn.Module, PackedWeights):
+    """PSMNet's 3-D regularization with its stride-1 convolutions on the convolution kernel (INTEGRATION.md has the composition).
+
+    `FusedRegularization(model, dtype=None)` wraps a loaded PSMNet, or any module with `dres0` .. `dres4` and `classif1` ..
+    `classif3` of the reference's structure (models/psmnet/psmnet.py:15-128): `dres0` = Sequential(convbn_3d, ReLU, convbn_3d,
+    ReLU), `dres1` = Sequential(convbn_3d, ReLU, convbn_3d), three hourglasses with `conv1`, `conv3`, `conv4` =
+    Sequential(convbn_3d, ReLU), `conv2` = convbn_3d and `conv5`, `conv6` = Sequential(ConvTranspose3d, BatchNorm3d), and
+    classifiers Sequential(convbn_3d, ReLU, Conv3d).  It holds the module, so the weights and the `state_dict` are untouched.
+
+    `forward(cost) -> cost3` [B,1,D,H,W], which `Engine.psmnet_disparity` takes, follows psmnet.py:199-213 and
+    `hourglass.forward` line for line.  Every convolution `conv3d_plain` of _convs.py accepts is one launch of `Engine.conv3d`
+    with its frozen BatchNorm3d folded (`fold_bn3d`), its ReLU and the sum that follows it directly in the epilogue:
+    `dres1(cost0) + cost0`, the hourglass's `relu(conv2(out) + postsqu)`, `classif2(out2) + cost1`, `classif3(out3) + cost2`.
+    Out of scope, and run in torch in the volume's dtype, decided per convolution: the hourglasses' two Conv3d at stride 2 and
+    two ConvTranspose3d with the sums behind them (`relu(conv5 + presqu)`, `out + cost0`), and any convolution `conv3d_plain`
+    refuses.  For the reference's module that is `launches()` = 16 launches per call.  `dtype`: torch.float32 or
+    torch.bfloat16; None keeps the volume's (bfloat16 under autocast).  Inference only, under `torch.no_grad()`; a BatchNorm3d in
+    training mode is a TypeError when wrapping.  The packed weights follow `PackedWeights`' cache rule.  Opt-in: README.md has
+    what was measured."""
+
+    def __init__(self, model, dtype=None):
+        torch.nn.Module.__init__(self)
+        PackedWeights.__init__(self)
+        if dtype not in (None, torch.float32, torch.bfloat16):
+            raise TypeError(f"{_WHO3}: dtype is {dtype}; the kernels store float32 and bfloat16")
+        for name in ("dres0", "dres1", "dres2", "dres3", "dres4", "classif1", "classif2", "classif3"):
+            if not hasattr(model, name):
+                raise TypeError(f"{_WHO3}: the module has no {name!r}")
+        _check_seq3(model.dres0, ("convbn", "relu", "convbn", "relu"), "dres0")
+        _check_seq3(model.dres1, ("convbn", "relu", "convbn"), "dres1")
+        for name in ("dres2", "dres3", "dres4"):
+            hg = getattr(model, name)
+            for part in ("conv1", "conv2", "conv3", "conv4", "conv5", "conv6"):
+                if not hasattr(hg, part):
+                    raise TypeError(f"{_WHO3}: {name} has no {part!r}")
+            for part in ("conv1", "conv3", "conv4"):
+                _check_seq3(getattr(hg, part), ("convbn", "relu"), f"{name}.{part}")
+            _check_convbn3d(hg.conv2, f"{name}.conv2")
+            _check_convbn3d(hg.conv5, f"{name}.conv5", torch.nn.ConvTranspose3d)
+            _check_convbn3d(hg.conv6, f"{name}.conv6", torch.nn.ConvTranspose3d)
+        for name in ("classif1", "classif2", "classif3"):
+            _check_seq3(getattr(model, name), ("convbn", "relu", "conv"), name)
+        self.model = model
+        self.dtype = dtype
+
+    def _plan(self):
+        """(convolution, its input channels) of everything forward() hands to _convbn / _conv, in its order."""
+        m = self.model
+        chain = lambda pairs, cin: [(p[0], c) for p, c in zip(pairs, [cin] + [p[0].out_channels for p in pairs[:-1]])]   # noqa: E731
+        plan = chain([m.dres0[0], m.dres0[2], m.dres1[0], m.dres1[2]], m.dres0[0][0].in_channels)
+        for hg in (m.dres2, m.dres3, m.dres4):
+            plan += chain([hg.conv1[0], hg.conv2, hg.conv3[0], hg.conv4[0]], hg.conv1[0][0].in_channels)
+        for cl in (m.classif1, m.classif2, m.classif3):
+            plan += [(cl[0][0], cl[0][0].in_channels), (cl[2], cl[0][0].out_channels)]
+        return plan
+
+    def launches(self):
+        """Engine.conv3d launches of one forward: the convolutions conv3d_plain accepts."""
+        return sum(1 for conv, cin in self._plan() if conv3d_plain(conv, cin))
+
+    # ---- one convolution ----
+    @staticmethod
+    def _torch(m, x):
+        """A module of the wrapped model on x, in x's dtype whatever the parameters' is."""
+        wd = next(m.parameters()).dtype
+        if wd == x.dtype:
+            y = m(x)
+        elif x.dtype == torch.bfloat16:
+            with torch.autocast(x.device.type, dtype=torch.bfloat16):
+                y = m(x)
+        else:
+            y = m(x.to(wd))
+        return y.to(x.dtype).contiguous()
+
+    def _convbn(self, eng, pair, x, relu=False, residual=None):
+        """[relu](bn(conv(x)) [+ residual]): one launch with the norm folded, or torch."""
+        conv, bn = pair[0], pair[1]
+        if conv3d_plain(conv, x.shape[1]):
+            return eng.conv3d(x, self._packed_conv3d_bn(eng, conv, bn, x.dtype, x.device), conv.out_channels, residual=residual, relu=relu)
+        if bn.training:
+            raise RuntimeError(f"{_WHO3}: a BatchNorm3d went back to training mode; the wrapper is inference only")
+        y = self._torch(pair, x)
+        if residual is not None:
+            y = y + residual
+        return torch.relu_(y) if relu else y
+
+    def _conv(self, eng, conv, x, residual=None):
+        """A convolution without a norm behind it (a classifier's last) [+ residual]."""
+        if conv3d_plain(conv, x.shape[1]):
+            return eng.conv3d(x, self._packed_conv3d(eng, conv, x.dtype, x.device), conv.out_channels, residual=residual)
+        y = self._torch(conv, x)
+        return y if residual is None else y + residual
+
+    def _hourglass(self, eng, hg, x, presqu, postsqu):
+        """hourglass.forward (psmnet.py:64-83)."""
+        out = self._convbn(eng, hg.conv1[0], x, relu=True)                           # in:1/4 out:1/8 (stride 2: torch)
+        pre = self._convbn(eng, hg.conv2, out, relu=True, residual=postsqu)         # relu(conv2(out) + postsqu), or relu(conv2(out))
+        out = self._convbn(eng, hg.conv3[0], pre, relu=True)                         # in:1/8 out:1/16 (stride 2: torch)
+        out = self._convbn(eng, hg.conv4[0], out, relu=True)
+        if hg.conv5[1].training or hg.conv6[1].training:
+            raise RuntimeError(f"{_WHO3}: a BatchNorm3d went back to training mode; the wrapper is inference only")
+        post = torch.relu_(self._torch(hg.conv5, out) + (presqu if presqu is not None else pre))
+        return self._torch(hg.conv6, post), pre, post
+
+    def _classif(self, eng, cl, x, residual=None):
+        return self._conv(eng, cl[2], self._convbn(eng, cl[0], x, relu=True), residual=residual)
+
+    def forward(self, cost):
+        with torch.no_grad():
+            return self._forward(cost)
+
+    def _forward(self, cost):
+        m = self.model
+        if cost.dim() != 5:
+            raise ValueError(f"{_WHO3}: cost is {tuple(cost.shape)}; expected [B,C,D,H,W]")
+        dtype = self.dtype
+        if dtype is None:
+            dtype = torch.bfloat16 if cost.is_cuda and _autocast_bf16() else cost.dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"{_WHO3}: the volume is {dtype}; the kernels store float32 and bfloat16 (pass dtype=)")
+        cost = cost.to(dtype).contiguous()
+        eng = _engine(cost.device)
+        cost0 = self._convbn(eng, m.dres0[2], self._convbn(eng, m.dres0[0], cost, relu=True), relu=True)
+        cost0 = self._convbn(eng, m.dres1[2], self._convbn(eng, m.dres1[0], cost0, relu=True), residual=cost0)
+
+        out1, pre1, post1 = self._hourglass(eng, m.dres2, cost0, None, None)
+        out1 = out1 + cost0
+
+        out2, pre2, post2 = self._hourglass(eng, m.dres3, out1, pre1, post1)
+        out2 = out2 + cost0
+
+        out3, pre3, post3 = self._hourglass(eng, m.dres4, out2, pre1, post2)
+        out3 = out3 + cost0
+
+        cost1 = self._classif(eng, m.classif1, out1)
+        cost2 = self._classif(eng, m.classif2, out2, residual=cost1)
+        return self._classif(eng, m.classif3, out3, residual=cost2)
